@@ -14,6 +14,10 @@ HBM, models from torch.manual_seed(1234).  A "step" is one training iteration (4
 (one (A,B) index = one image, dataset.py:210-213).  Weak scaling: per-GPU batch is fixed.
 ``--image_size 64`` selects the 64 px network (configs[1]: batch 256; configs[2]'s per-GPU shape: --batch_size 64).
 
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR) and the JSON
+line.  The roofline leg, the CPU baseline, everything in `extra` but whole_step_tflops, and the exposed exchange time of N > 1
+are measured only with --full; --no_roofline / --no_extra / --no_cpu_baseline drop parts of a --full run.
+
 One JSON line on rank 0 with the contract fields plus
   roofline     : the dominant kernel family (igemm_kernel, fp32 MFMA): algorithmic conv FLOPs of every launch in one
                  D,G,G cycle / summed HIP-event durations of those launches (events on the launch stream); traffic =
@@ -50,6 +54,10 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps, rounded up to whole D,G,G cycles (default 6 / 9)")
     ap.add_argument("--image_size", type=int, default=512, choices=[64, 512])
     ap.add_argument("--batch_size", type=int, default=None, help="per GPU (default 32 at 512 px, 256 at 64 px)")
+    ap.add_argument("--full", action="store_true", help="also every side measurement (roofline leg, D-step / G-step split, side runs, "
+                    "CPU baseline, exposed exchange time); without it only the headline's timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--no_graph", action="store_true")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--cpu_baseline_batch", type=int, default=0,
@@ -75,6 +83,8 @@ def parse(argv=None):
     ap.add_argument("--overlap", default="auto", choices=["auto", "on", "off", "graph"],
                     help="data-parallel exchange overlapped with compute (eager dispatch) or behind a replayed hipGraph")
     a = ap.parse_args(argv)
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.batch_size is None:
         a.batch_size = 32 if a.image_size == 512 else 256
     if a.steps is None:
@@ -139,16 +149,47 @@ def timed_run(trainer, A, B, steps, warmup, world, start_iter=0, need_losses=Tru
     trainer.finish()
     barrier_sync(world, trainer.xg)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         trainer.train_iteration(A, B, it, need_losses=need_losses)
         it += 1
+    out = trainer.train_iteration(A, B, it, need_losses=need_losses)    # the last step's outputs (--dump-outputs)
+    it += 1
     trainer.finish()
     barrier_sync(world, trainer.xg)
     dt = time.perf_counter() - t0
     if world > 1:
         from discogan_modernized_amd import dp
         dt = max(dp.host_allgather(dt))                            # max over ranks (host-side, through the c10d store)
-    return dt, it
+    return dt, it, out
+
+
+DUMP_BYTES = 60 << 20     # --dump-outputs: data of all arrays together (64 MB with the .npy headers)
+
+
+def dump_outputs(trainer, out, outdir):
+    """--dump-outputs: what the timed path computed in its last step -- every tensor train_iteration returned (losses, translated
+    images, discriminator outputs and feature maps, the loss vector) and both flat parameter buffers after the step's Adam update --
+    as DIR/<name>.npy in float32 (float64 stays float64).  An array larger than its share of DUMP_BYTES is written as a fixed sample
+    of its flattened elements: indices from a generator seeded with 0, so two runs or two builds sample the same elements."""
+    import numpy as np
+    import torch
+    arrays = []
+    for k, v in vars(out).items():
+        if torch.is_tensor(v):
+            arrays.append((k, v))
+        elif isinstance(v, (list, tuple)):
+            arrays += [(f"{k}_{i}", t) for i, t in enumerate(v) if torch.is_tensor(t)]
+    arrays += [("gen_params", trainer.optim_gen.flat_p), ("dis_params", trainer.optim_dis.flat_p)]
+    share = DUMP_BYTES // len(arrays)
+    os.makedirs(outdir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays:
+        x = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        cap = share // x.element_size()
+        if x.numel() > cap:
+            idx = torch.randint(x.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        np.save(os.path.join(outdir, f"{name}.npy"), x.cpu().numpy())
 
 
 def roofline_pass(trainer, A, B, start_iter):
@@ -314,8 +355,9 @@ def make_trainer(a, dev, pg, image_size, mfma_dtype=None, graph=None, overlap=No
     return tr
 
 
-def measure(a, tr, A, B, batch, world, steps, warmup, roofline=True, split_cycles=0, image_size=None, exposed=False):
+def measure(a, tr, A, B, batch, world, steps, warmup, roofline=True, split_cycles=0, image_size=None, exposed=False, dump_dir=None):
     """value + optional roofline leg + optional D/G split for one trainer; returns a dict.
+    dump_dir: the last timed step's outputs go there (dump_outputs) before anything else runs on the trainer.
     exposed (N > 1): the same timed window once more with the collectives stubbed (every rank keeps its own sum; the
     exchange path, buckets, events and Adam slices still run) -- the difference is the exchange time the step actually pays."""
     ui = tr.args.update_interval
@@ -324,7 +366,10 @@ def measure(a, tr, A, B, batch, world, steps, warmup, roofline=True, split_cycle
     # have (conservative by <= 1.5 %), never the most.
     phase = 0 if steps % ui == 0 else 1
     warmup = warmup + (phase - warmup) % ui
-    dt, it = timed_run(tr, A, B, steps, warmup, world)
+    dt, it, out = timed_run(tr, A, B, steps, warmup, world)
+    if dump_dir:
+        dump_outputs(tr, out, dump_dir)
+    del out
     res = dict(images_per_sec=round(batch * world * steps / dt, 2), ms_per_step=round(dt / steps * 1e3, 3), steps=steps,
                warmup=warmup, hipgraph=bool(tr.use_graph), allreduce_overlap=("graph" if tr.graph_overlap else bool(tr.overlap_comm)),
                grouped_launches=bool(tr.group_launch))
@@ -334,7 +379,7 @@ def measure(a, tr, A, B, batch, world, steps, warmup, roofline=True, split_cycle
     if exposed and tr.xg is not None:
         tr.xg.noop = True
         try:
-            dt0, it = timed_run(tr, A, B, steps, (phase - it) % ui + ui, world, start_iter=it)
+            dt0, it, _ = timed_run(tr, A, B, steps, (phase - it) % ui + ui, world, start_iter=it)
         finally:
             tr.xg.noop = False
         res["ms_per_step_exchange_stubbed"] = round(dt0 / steps * 1e3, 3)
@@ -406,8 +451,9 @@ def main():
     tr.time_comm = world > 1
     A, B = synthetic_batch(N, S, 1000 + rank, dev)
     log(f"models built; {a.warmup} warm-up + {a.steps} timed steps @{S}px batch {N} x {world} GPU")
-    head = measure(a, tr, A, B, N, world, a.steps, a.warmup, roofline=not a.no_roofline,
-                   split_cycles=0 if a.no_extra else (2 if S == 512 else 4), exposed=world > 1)
+    head = measure(a, tr, A, B, N, world, a.steps, a.warmup, roofline=a.full and not a.no_roofline,
+                   split_cycles=0 if (a.no_extra or not a.full) else (2 if S == 512 else 4), exposed=a.full and world > 1,
+                   dump_dir=a.dump_outputs if rank == 0 else None)
     log(f"timed region done: {head['ms_per_step']:.3f} ms/step, {head['images_per_sec']:.1f} img/s")
     comm = None
     if world > 1:
@@ -441,7 +487,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- side measurements (1 GPU only) --------------------------------------------------------------------------
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         def side(label, image_size, batch, steps, warmup, **kw):
             t0 = time.time()
             t = make_trainer(a, dev, None, image_size, **{k: v for k, v in kw.items() if k in ("mfma_dtype", "graph", "overlap", "comm", "act_dtype", "group")})
@@ -499,7 +545,7 @@ def main():
                               "losses / master weights / Adam (tests: test_bf16_path_vs_reference_golden_512_n2, test_bf16_activation_storage_training_step)")
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         torch.set_num_threads(min(16, os.cpu_count() or 1))   # the 1-GPU box's CPU share is 16 cores
         log("cpu baseline (oracle) ...")
         cb = 2 if S == 512 else 64

@@ -5,8 +5,9 @@
   * the criteria with the reference's call forms (label TENSORS, HingeEmbeddingLoss(x, ones));
   * the CLI: log-line format, checkpoint file names, ``--resume`` (bitwise continuation with graph replay on),
     ``--load_*`` checkpoints, uint8 image ingest;
-  * the C-ABI exchange group on hardware (1-rank RCCL communicator), the bucketed G-step exchange, and
-    ``python bench.py --gpus N`` starting its own ranks (gloo rehearsal on one GPU).
+  * the C-ABI exchange group on hardware (1-rank RCCL communicator), the bucketed G-step exchange,
+    ``python bench.py --gpus N`` starting its own ranks (gloo rehearsal on one GPU), and a plain ``bench.py`` run with
+    ``--dump-outputs``.
 """
 import json
 import os
@@ -15,6 +16,7 @@ import subprocess
 import sys
 from itertools import chain
 
+import numpy as np
 import pytest
 import torch
 
@@ -377,7 +379,7 @@ def test_bench_starts_its_own_ranks_gloo_rehearsal():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--image_size", "64", "--batch_size", "8",
-                        "--steps", "6", "--warmup", "3", "--no_extra", "--no_cpu_baseline", "--no_roofline"],
+                        "--steps", "6", "--warmup", "3", "--full", "--no_extra", "--no_cpu_baseline", "--no_roofline"],
                        env=env, capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -390,3 +392,23 @@ def test_bench_starts_its_own_ranks_gloo_rehearsal():
     assert d["comm"]["ms_per_step_exchange_stubbed"] > 0 and d["comm"]["exposed_ms_per_step"] is not None
     assert abs(d["comm"]["exposed_ms_per_step"] - (d["ms_per_step"] - d["comm"]["ms_per_step_exchange_stubbed"])) < 2e-3
     assert d["dtype"] == "f32x3" and "three bf16 planes" in d["config"]["workload"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and nothing else (no roofline leg, D/G split, side runs or CPU
+    baseline); --dump-outputs writes the last timed step's outputs and parameters as float32 .npy files, 64 MB at most."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--image_size", "64", "--batch_size", "8",
+                        "--steps", "4", "--warmup", "3", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32x3"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "ms_D_step" not in d["extra"]
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert {"gen_loss", "dis_loss", "recon_loss_A", "AB", "BA", "gen_params", "dis_params"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    for k in ("gen_loss", "dis_loss", "recon_loss_A", "AB", "gen_params", "dis_params"):
+        assert np.isfinite(files[k]).all(), k

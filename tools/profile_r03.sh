@@ -1,4 +1,4 @@
-# on the GPU box: bash tools/profile_r03.sh  -> gpurun_out/r03_* (copy what should be judged into profiles/)
+# on the GPU box: bash tools/profile_r03.sh  -> $OUT/r03_* (default profile_out/; copy what should be judged into profiles/)
 # Round 3: the headline arithmetic is f32x3.  rocprofv3 --kernel-trace --stats of the bench command (2 streams + hipGraph), of the
 # single-stream eager form (isolated kernel durations: what roofline.achieved is measured on) for f32x3, exact f32 and bf16, then the
 # PMC traffic passes (FETCH_SIZE / WRITE_SIZE in their own runs) over tools/bench_ops.py for the three arithmetics, then the SQ
@@ -7,11 +7,13 @@ set -e
 RND=r03
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+OUT=${OUT:-$R/profile_out}
+mkdir -p "$OUT"
 prof() {   # tag, bench flags...
   tag=$1; shift
   rm -rf /tmp/pp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -- python3 $R/bench.py --no_extra --no_cpu_baseline "$@" > $R/gpurun_out/${RND}_bench_under_rocprof_512px_bs32_${tag}.json 2>/tmp/e_${tag}.log
-  cp $(find /tmp/pp -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${RND}_rocprofv3_kernel_stats__512px_bs32_${tag}.csv
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -- python3 $R/bench.py --full --no_extra --no_cpu_baseline "$@" > $OUT/${RND}_bench_under_rocprof_512px_bs32_${tag}.json 2>/tmp/e_${tag}.log
+  cp $(find /tmp/pp -name "*kernel_stats.csv" | head -1) $OUT/${RND}_rocprofv3_kernel_stats__512px_bs32_${tag}.csv
   echo "profile ${tag} done"
 }
 prof f32x3_default_2streams_graph

@@ -1,4 +1,4 @@
-# on the GPU box: bash tools/profile_r04.sh  -> gpurun_out/r04_* (copy what should be judged into profiles/)
+# on the GPU box: bash tools/profile_r04.sh  -> $OUT/r04_* (default profile_out/; copy what should be judged into profiles/)
 # Round 4: rocprofv3 --kernel-trace --stats of the bench command at the headline workload (512 px / batch 32: default dispatch and
 # single-stream eager for f32x3; single-stream eager for exact f32 and bf16), then the PMC traffic passes (FETCH_SIZE / WRITE_SIZE in
 # their own runs) over tools/bench_ops.py at the metric's other configuration, 64 px / batch 64, for exact f32 and f32x3.
@@ -7,11 +7,13 @@ set -e
 RND=r04
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+OUT=${OUT:-$R/profile_out}
+mkdir -p "$OUT"
 prof() {   # tag, bench flags...
   tag=$1; shift
   rm -rf /tmp/pp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -- python3 $R/bench.py --no_extra --no_cpu_baseline "$@" > $R/gpurun_out/${RND}_bench_under_rocprof_512px_bs32_${tag}.json 2>/tmp/e_${tag}.log
-  cp $(find /tmp/pp -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${RND}_rocprofv3_kernel_stats__512px_bs32_${tag}.csv
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -- python3 $R/bench.py --full --no_extra --no_cpu_baseline "$@" > $OUT/${RND}_bench_under_rocprof_512px_bs32_${tag}.json 2>/tmp/e_${tag}.log
+  cp $(find /tmp/pp -name "*kernel_stats.csv" | head -1) $OUT/${RND}_rocprofv3_kernel_stats__512px_bs32_${tag}.csv
   echo "profile ${tag} done"
 }
 prof f32x3_default_2streams_graph
