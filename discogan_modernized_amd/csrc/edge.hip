@@ -406,14 +406,21 @@ extern "C" int dg_conv4x4s2_c3_dgrad_p(const void* dy_nhwc, int dy_bf16, const f
     const float* dyp = (const float*)dy_nhwc;
     return c3_dgrad_run(1, &dyp, dy_bf16, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream);
 }
-// 1 when the fused form below exists for this K under the options in force (the scatter kernel: K == 64, option "kt" != 16)
-extern "C" int dg_c3_dgrad_act_ok(int K) { return K == CD_K && dg_get_option(DG_OPT_KT) != 16 ? 1 : 0; }
+// The scatter form takes dy up to 2^31 bytes (32-bit offsets into one buffer descriptor), counted in dy's own element size.
+static bool c3_dgrad_scatter_fits(int N, int H, int W, int K, int dy_bf16) {
+    return K == CD_K && N >= 1 && (long)N * (H / 2) * (W / 2) * CD_K * (dy_bf16 ? 2 : 4) < (1L << 31);
+}
+// 1 when the fused form below exists for this problem under the options in force: the scatter kernel (K == 64, dy under 2^31 bytes,
+// option "kt" != 16).  Past that size the input-gradient runs on the VALU kernel, which has no fused activation backward.
+extern "C" int dg_c3_dgrad_act_ok(int N, int H, int W, int K, int dy_bf16) {
+    return c3_dgrad_scatter_fits(N, H, W, K, dy_bf16) && dg_get_option(DG_OPT_KT) != 16 ? 1 : 0;
+}
 // conv1's input-gradient with the backward of the layer's fused LeakyReLU applied to dy in the load path: dx = dgrad(dy * (act_out > 0 ? 1 : slope))
 extern "C" int dg_conv4x4s2_c3_dgrad_act_p(const void* dy_nhwc, int dy_bf16, const void* act_out, int in_act, float slope, const float* w, float* dx_nchw,
                                            int N, int H, int W, int K, int act, int prec, void* ws, size_t ws_bytes, dg_stream_t stream) {
     DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_dgrad_act_p: prec=%d", prec);
     DG_CHECK_ARG(act_out && in_act == DG_ACT_LEAKY, "dg_conv4x4s2_c3_dgrad_act_p: needs the saved output of a fused LeakyReLU (in_act=%d)", in_act);
-    DG_CHECK_ARG(dg_c3_dgrad_act_ok(K), "dg_conv4x4s2_c3_dgrad_act_p: the fused form is the scatter kernel (K == 64, option kt != 16)");
+    DG_CHECK_ARG(dg_c3_dgrad_act_ok(N, H, W, K, dy_bf16), "dg_conv4x4s2_c3_dgrad_act_p: the fused form is the scatter kernel (K == 64, dy under 2^31 bytes, option kt != 16)");
     DgPrecScope scope(prec);
     const float* dyp = (const float*)dy_nhwc;
     return c3_dgrad_run(1, &dyp, dy_bf16, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream, act_out, slope);
@@ -440,7 +447,7 @@ static int c3_dgrad_run(int groups, const float* const* dy_tab, int dy_bf16, con
     DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "dg_conv4x4s2_c3_dgrad: tensor too large");
     hipStream_t st = (hipStream_t)stream;
     const int Ho = H / 2, Wo = W / 2;
-    if (K == CD_K && (long)N * Ho * Wo * CD_K * 4 < (1L << 31)) {
+    if (c3_dgrad_scatter_fits(N, H, W, K, dy_bf16)) {
         if (dg_get_option(DG_OPT_KT) != 16) {       // scatter form (dense GEMM + overlap-add); "kt" 16 keeps the gather form testable
             const int tiles_r = (Ho + CS_TR - 1) / CS_TR, tiles_c = (Wo + CS_TC - 1) / CS_TC;
             const long ntiles = (long)N * tiles_r * tiles_c;
@@ -465,6 +472,7 @@ static int c3_dgrad_run(int groups, const float* const* dy_tab, int dy_bf16, con
             return DG_OK;
         }
         DG_CHECK_ARG(groups == 1 && !act_out, "dg_conv4x4s2_c3_dgrad: the gather form takes one problem and no fused activation backward");
+        DG_CHECK_ARG(!dy_bf16, "dg_conv4x4s2_c3_dgrad: the gather form reads an fp32 dy (a bf16 dy needs the scatter form)");
         const int tiles_r = (Ho + CD_TR - 1) / CD_TR, tiles_c = (Wo + CD_TC - 1) / CD_TC;
         const long ntiles = (long)N * tiles_r * tiles_c;
         DG_CHECK_ARG(ntiles < (1L << 31), "dg_conv4x4s2_c3_dgrad: too many tiles");
@@ -479,6 +487,8 @@ static int c3_dgrad_run(int groups, const float* const* dy_tab, int dy_bf16, con
         return DG_OK;
     }
     DG_CHECK_ARG(groups == 1 && !act_out, "dg_conv4x4s2_c3_dgrad: the VALU form takes one problem and no fused activation backward");
+    DG_CHECK_ARG(!dy_bf16, "dg_conv4x4s2_c3_dgrad: the VALU form reads an fp32 dy (a bf16 dy of %ld bytes is past the scatter form's 2^31)",
+                 (long)N * Ho * Wo * K * 2);
     const long nquad = (long)N * Ho * Wo;
     hipLaunchKernelGGL(c3_dgrad_valu_kernel, dim3((unsigned)((nquad + 255) / 256)), dim3(256), 0, st, dy_nhwc, w,
                        dx_nchw, N, H, W, K, dg_ilog2(Ho), dg_ilog2(Wo), act);

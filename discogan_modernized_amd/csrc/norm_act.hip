@@ -906,7 +906,7 @@ static BnRows bn_rows(int M, int C, int cm, int V) {
     g.ok = 1;
     g.tx = 64 / V;                                  // quad-chunk planes: a wave = 4 (8) pixels x 64 channels
     if (!cm) while (g.tx < C / V && g.tx < 64) g.tx <<= 1;
-    g.cchunks = C / (V * g.tx);
+    g.cchunks = (C / V + g.tx - 1) / g.tx;         // ragged last chunk (C = 192, 320, ...): the kernels return on c >= C
     const int ty = 256 / g.tx;
     long rc = M / ((long)ty * BN_U);
     long cap = 4096 / g.cchunks;

@@ -188,7 +188,10 @@ class ConvC3Fn(Function):
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
         act, slope = ctx.act
-        fused_dgrad = FUSE_C3_DGRAD_ACT and act == ops.ACT_LEAKY and ops.c3_dgrad_act_ok(w.shape[0])
+        # the fused input-gradient is the scatter kernel's, which stops at 2^31 bytes of dy (conv1 at 512 px from batch 128 in fp32,
+        # 256 with bf16 feature maps); past it the stand-alone act_bwd pass goes in front of the unfused kernel
+        fused_dgrad = FUSE_C3_DGRAD_ACT and act == ops.ACT_LEAKY and ops.c3_dgrad_act_ok(w.shape[0], x.shape[0], x.shape[2], x.shape[3],
+                                                                                          dy.dtype == torch.bfloat16)
         if act == ops.ACT_NONE or (ctx.needs_input_grad[0] and not fused_dgrad):
             g = ops.act_bwd(dy, y, act, slope) if act != ops.ACT_NONE else ops.as_nhwc(dy)
             fuse = {}

@@ -688,14 +688,16 @@ def c3_fwd(x_nchw, w, act=ACT_NONE, slope=0.2, want_planes=False):
     return y
 
 
-def c3_dgrad_act_ok(k):
-    """Does the input-gradient kernel take the layer's activation backward in its load path (c3_dgrad(..., act_out=...))?"""
-    return bool(_lib.load().dg_c3_dgrad_act_ok(int(k)))
+def c3_dgrad_act_ok(k, n=1, h=2, wd=2, dy_bf16=False):
+    """Does the input-gradient kernel take the layer's activation backward in its load path (c3_dgrad(..., act_out=...)) for
+    dy [n, k, h/2, wd/2] (bf16 or fp32)?  Only the scatter kernel does, and it takes dy up to 2^31 bytes; the defaults ask about
+    the smallest problem, i.e. whether the form exists for this k at all."""
+    return bool(_lib.load().dg_c3_dgrad_act_ok(int(n), int(h), int(wd), int(k), int(bool(dy_bf16))))
 
 
 def c3_dgrad(dy, w, act=ACT_NONE, act_out=None, in_act=ACT_NONE, slope=0.2):
     """dy NHWC-memory [N,K,Ho,Wo], w contiguous [K,3,4,4] -> contiguous NCHW [N,3,2Ho,2Wo] (act fused).
-    With ``act_out`` (the saved output of the layer's fused LeakyReLU; needs c3_dgrad_act_ok(K)) dy is taken through the activation
+    With ``act_out`` (the saved output of the layer's fused LeakyReLU; needs c3_dgrad_act_ok(K, N, H, W, bf16 dy)) dy is taken through the activation
     backward on the fly -- bitwise c3_dgrad(act_bwd(dy, act_out, in_act, slope), w, act) without the pass in front."""
     _check_dev(dy, act_out, allow16=True)
     _check_dev(w)
@@ -713,6 +715,11 @@ def c3_dgrad(dy, w, act=ACT_NONE, act_out=None, in_act=ACT_NONE, slope=0.2):
             _lib.check(L.dg_conv4x4s2_c3_dgrad_act_p(_ptr(dy), int(_is16(dy)), _ptr(ao), in_act, float(slope), _ptr(w), _ptr(dx), n, 2 * ho, 2 * wo, k,
                                                      act, _CUR.cprec, _ptr(ws), wsb, _stream()), "dg_conv4x4s2_c3_dgrad_act_p")
         return dx
+    if _is16(dy) and not L.dg_c3_dgrad_act_ok(n, 2 * ho, 2 * wo, k, 1):
+        # only the scatter kernel reads a bf16 dy; past its 2^31-byte limit (or with option "kt" 16) the fp32 kernels get an fp32 copy
+        dyf = torch.empty_like(dy, dtype=torch.float32)
+        dyf.copy_(dy)
+        dy = dyf
     with _hbm("edge_c3_dgrad", dy.numel() * dy.element_size() + 4.0 * dx.numel()):
         _lib.check(L.dg_conv4x4s2_c3_dgrad_p(_ptr(dy), int(_is16(dy)), _ptr(w), _ptr(dx), n, 2 * ho, 2 * wo, k, act, _CUR.cprec, _ptr(ws), wsb,
                                              _stream()), "dg_conv4x4s2_c3_dgrad_p")

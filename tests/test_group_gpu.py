@@ -93,28 +93,31 @@ def test_heads_group(g):
     """The 4x4 valid heads: K = 1 (discriminator, plain reductions) and K = 100 (generator bottleneck), and the 1x1 -> 4x4 transposed head."""
     N, C = 8, 512
     xs = [nhwc(rnd(N, C, 4, 4, seed=80 + i)) for i in range(g)]
+    plan = ops.current().group_plan
     ops.current().group_plan = "single"
-    for K in (1, 100):
-        ws = [ops.krsc_param(rnd(K, C, 4, 4, seed=90 + i, scale=0.02).to(DEV)) for i in range(g)]
-        dys = [nhwc(rnd(N, K, 1, 1, seed=95 + i)) for i in range(g)]
-        y1 = [ops.conv_fwd(x, w, 1, 0) for x, w in zip(xs, ws)]
-        yg = ops.conv_fwd_g(xs, ws, 1, 0)
-        d1 = [ops.conv_dgrad(d, w, (4, 4), 1, 0) for d, w in zip(dys, ws)]
-        dg = ops.conv_dgrad_g(dys, ws, (4, 4), 1, 0)
-        share = 2 if g == 4 else 1
-        nout = g // share
-        base = [torch.zeros(K, C, 4, 4, device=DEV).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2) for _ in range(nout)]
-        ref = [b.clone() for b in base]
-        for i in range(g):
-            ops.conv_wgrad(dys[i], xs[i], 1, 0, out=ref[i // share], accumulate=True)
-        got = [b.clone() for b in base]
-        ops.conv_wgrad_g(dys, xs, 1, 0, [got[i // share] for i in range(g)], True, share=share)
-        for i in range(g):
-            same(yg[i], y1[i], f"head K={K} forward {i}")
-            same(dg[i], d1[i], f"head K={K} input-grad {i}")
-        for z in range(nout):
-            same(got[z], ref[z], f"head K={K} weight-grad {z}")
-    ops.current().group_plan = "launch"
+    try:
+        for K in (1, 100):
+            ws = [ops.krsc_param(rnd(K, C, 4, 4, seed=90 + i, scale=0.02).to(DEV)) for i in range(g)]
+            dys = [nhwc(rnd(N, K, 1, 1, seed=95 + i)) for i in range(g)]
+            y1 = [ops.conv_fwd(x, w, 1, 0) for x, w in zip(xs, ws)]
+            yg = ops.conv_fwd_g(xs, ws, 1, 0)
+            d1 = [ops.conv_dgrad(d, w, (4, 4), 1, 0) for d, w in zip(dys, ws)]
+            dg = ops.conv_dgrad_g(dys, ws, (4, 4), 1, 0)
+            share = 2 if g == 4 else 1
+            nout = g // share
+            base = [torch.zeros(K, C, 4, 4, device=DEV).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2) for _ in range(nout)]
+            ref = [b.clone() for b in base]
+            for i in range(g):
+                ops.conv_wgrad(dys[i], xs[i], 1, 0, out=ref[i // share], accumulate=True)
+            got = [b.clone() for b in base]
+            ops.conv_wgrad_g(dys, xs, 1, 0, [got[i // share] for i in range(g)], True, share=share)
+            for i in range(g):
+                same(yg[i], y1[i], f"head K={K} forward {i}")
+                same(dg[i], d1[i], f"head K={K} input-grad {i}")
+            for z in range(nout):
+                same(got[z], ref[z], f"head K={K} weight-grad {z}")
+    finally:
+        ops.current().group_plan = plan
 
 
 @pytest.mark.parametrize("prec", [ops.PREC_F32, ops.PREC_F32X3])

@@ -675,7 +675,8 @@ def test_batchnorm_writes_plane_triples(N, C, H, act):
         ops.planes_clear()
 
 
-@pytest.mark.parametrize("N,C,H", [(4, 64, 16), (3, 256, 8), (1, 128, 6), (5, 1024, 2), (2, 2048, 4), (32, 64, 64)])
+@pytest.mark.parametrize("N,C,H", [(4, 64, 16), (3, 256, 8), (1, 128, 6), (5, 1024, 2), (2, 2048, 4), (32, 64, 64),
+                                   (4, 192, 8), (2, 320, 8), (3, 384, 4)])
 def test_batchnorm_row_geometry_kernels_equal_item_kernels(N, C, H):
     """The fp32 BatchNorm apply passes run in the reduction passes' geometry (fixed channels per thread; csrc/norm_act.hip
     bn_act_fwd_rows_kernel / bn_bwd_apply_rows_kernel) wherever C % 64 == 0 and M % 4 == 0; option "bn_items" 1 puts them back on the
