@@ -1180,6 +1180,21 @@ static int check_geom(const char* who, int N, int H, int W, int C, int K, int st
     return DG_OK;
 }
 
+// The channel rules every launch entry point applies on top of check_geom (the K == 1 head aside, which has no plan at all).
+static int check_channels(const char* who, int op, const ConvGeom& g) {
+    if (op == 0) DG_CHECK_ARG(g.C % 32 == 0, "%s: C=%d must be a multiple of 32", who, g.C);
+    if (op == 1 && g.stride == 2) DG_CHECK_ARG(g.K % 32 == 0, "%s: K=%d must be a multiple of 32", who, g.K);
+    return DG_OK;
+}
+// Planning queries: is there a plan to ask about?  Not for an op outside 0..2, a geometry or channel count the launch entry points refuse,
+// or the K == 1 head (plain reductions: no workspace, no split, no statistics).  The queries then answer "nothing": 0 bytes / rows / not ok,
+// 1 split -- never a plan for a shape that cannot be launched (make_plan's K-tile counts assume the channel rules).
+static bool query_has_plan(const char* who, int op, int N, int H, int W, int C, int K, int stride, int pad, ConvGeom* g) {
+    if (op < 0 || op > 2) { dg_fail(DG_ERR_INVALID, "%s: op=%d (0 forward, 1 input gradient, 2 weight gradient)", who, op); return false; }
+    if (check_geom(who, N, H, W, C, K, stride, pad, g) != DG_OK || K == 1) return false;
+    return check_channels(who, op, *g) == DG_OK;
+}
+
 struct Plan {
     int mode, wm, wn, kt;
     IgemmArgs a;
@@ -1483,8 +1498,7 @@ static int run_plan(const char* who, Plan& pl, void* ws, size_t ws_bytes, hipStr
 
 extern "C" size_t dg_conv_workspace_bytes(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (check_geom("dg_conv_workspace_bytes", N, H, W, C, K, stride, pad, &g) != DG_OK) return 0;
-    if (K == 1) return 0;
+    if (!query_has_plan("dg_conv_workspace_bytes", op, N, H, W, C, K, stride, pad, &g)) return 0;
     Plan pl;
     make_plan(op, g, &pl);
     size_t ws = pl.ws_bytes;
@@ -1569,8 +1583,7 @@ static int conv_g(int op, int groups, int share, const float* const* a_in, const
         DG_CHECK_ARG(stride == 1, "%s: K==1 only for the 4x4 head", who);
         return head1_g(op, groups, share, (const void* const*)a_in, 0, (const void* const*)b_in, 0, (void* const*)out, 0, N, C, accumulate, st, who);
     }
-    if (op == 0) DG_CHECK_ARG(C % 32 == 0, "%s: C=%d must be a multiple of 32", who, C);
-    if (op == 1 && stride == 2) DG_CHECK_ARG(K % 32 == 0, "%s: K=%d must be a multiple of 32", who, K);
+    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
     Plan pl;
     make_plan(op, g, &pl);
     IgemmArgs& a = pl.a;
@@ -1678,10 +1691,11 @@ static int conv_mixed(int op, const void* a_in, int a16, const void* b_in, int b
     // caller's arithmetic
     DgPrecScope scope((a16 || b16 || out16) ? DG_PREC_BF16 : dg_cur_prec());
     DG_CHECK_ARG(!(out16 && op == 2), "%s: the weight gradient is always fp32", who);
-    if (op == 0) DG_CHECK_ARG(C % 32 == 0, "%s: C=%d must be a multiple of 32", who, C);
-    if (op == 1 && stride == 2) DG_CHECK_ARG(K % 32 == 0, "%s: K=%d must be a multiple of 32", who, K);
+    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
     // 8-element granules must not straddle a row end: the A operand of the plain GEMM forms has rows of K elements
     if (a16 && op != 0 && K % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 gradient operand needs K %% 8 == 0 (K=%d)", who, K);
+    // the same for the weight gradient's x (B operand: columns are (tap, channel), a tap's run is C elements)
+    if (b16 && op == 2 && C % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 x needs C %% 8 == 0 (C=%d)", who, C);
     Plan pl;
     make_plan(op, g, &pl, a16, b16);
     if (pl.a.prec != 1 && (a16 || b16 || out16)) return dg_fail(DG_ERR_INVALID, "%s: this shape has no bf16 tile kernel", who);
@@ -1698,7 +1712,7 @@ static int conv_mixed(int op, const void* a_in, int a16, const void* b_in, int b
 }
 extern "C" int dg_conv_mixed_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad, int a_bf16, int b_bf16) {
     ConvGeom g;
-    if ((op != 0 && op != 1) || check_geom("dg_conv_mixed_bnstats_rows", N, H, W, C, K, stride, pad, &g) != DG_OK || K == 1 || stride != 2) return 0;
+    if (op == 2 || !query_has_plan("dg_conv_mixed_bnstats_rows", op, N, H, W, C, K, stride, pad, &g) || stride != 2) return 0;
     DgPrecScope scope(DG_PREC_BF16);
     Plan pl;
     make_plan(op, g, &pl, a_bf16, b_bf16);
@@ -1720,7 +1734,7 @@ extern "C" int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, i
 // 2 = with BOTH operands bf16 the LDS-DMA kernel of igemm_dma.hip runs)
 extern "C" int dg_conv_bf16_operands_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (check_geom("dg_conv_bf16_operands_ok", N, H, W, C, K, stride, pad, &g) != DG_OK || K == 1) return 0;
+    if (!query_has_plan("dg_conv_bf16_operands_ok", op, N, H, W, C, K, stride, pad, &g)) return 0;
     DgPrecScope scope(DG_PREC_BF16);
     Plan pl;
     make_plan(op, g, &pl, 1, 1);
@@ -1750,6 +1764,7 @@ static int conv_x3(int op, const void* a3, long a_plane, const void* b3, long b_
     DG_CHECK_ARG(a3 && b3 && out, "%s: null pointer", who);
     DgPrecScope scope(DG_PREC_F32X3);       // plane operands ARE the f32x3 arithmetic: no process-wide switch involved
     DG_CHECK_ARG(K > 1, "%s: the K == 1 head has no plane form", who);
+    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;      // the same channel rules as the fp32 forms: dg_conv_x3_planes_ok answers 0 there
     Plan pl;
     // forward with plain (not transposed) weight planes where the window forward kernel would apply: the register-staged tiles read
     // the planes instead (igemm_kernel<.., PREC 2, A16, B16>)
@@ -1790,7 +1805,7 @@ extern "C" int dg_conv_dgrad_x3(const void* dy3, long dy_plane, int dy_layout, c
 // partial-statistics rows the plane kernel of (op, shape) emits (0: none -- no plane kernel, or one without the epilogue)
 extern "C" int dg_conv_x3_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (op == 2 || check_geom("dg_conv_x3_bnstats_rows", N, H, W, C, K, stride, pad, &g) != DG_OK || K == 1) return 0;
+    if (op == 2 || !query_has_plan("dg_conv_x3_bnstats_rows", op, N, H, W, C, K, stride, pad, &g)) return 0;
     DgPrecScope scope(DG_PREC_F32X3);
     Plan pl;
     make_plan(op, g, &pl, 3, 3);
@@ -1806,7 +1821,7 @@ extern "C" int dg_conv_wgrad_x3(const void* dy3, long dy_plane, int dy_layout, c
 // wants its gradient operand in the quad-chunk layout (plane_layout 1 of dg_bn_act_*_x3)
 extern "C" int dg_conv_x3_planes_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (check_geom("dg_conv_x3_planes_ok", N, H, W, C, K, stride, pad, &g) != DG_OK || K == 1) return 0;
+    if (!query_has_plan("dg_conv_x3_planes_ok", op, N, H, W, C, K, stride, pad, &g)) return 0;
     DgPrecScope scope(DG_PREC_F32X3);
     Plan pl;
     make_plan(op, g, &pl, 3, 3);
@@ -1826,8 +1841,7 @@ static int conv_bias_act(int op, const float* a_in, const float* w, const float*
     DG_CHECK_ARG(a_in && w && out, "%s: null pointer", who);
     DG_CHECK_ARG(K > 1, "%s: K == 1 head has no folded form", who);
     DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "%s: bad act %d", who, act);
-    if (op == 0) DG_CHECK_ARG(C % 32 == 0, "%s: C=%d must be a multiple of 32", who, C);
-    if (op == 1 && stride == 2) DG_CHECK_ARG(K % 32 == 0, "%s: K=%d must be a multiple of 32", who, K);
+    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
     Plan pl;
     make_plan(op, g, &pl);
     pl.a.A = a_in; pl.a.B = w; pl.a.C = out;
@@ -1847,15 +1861,14 @@ extern "C" int dg_conv_dgrad_bias_act(const float* dy, const float* w, const flo
 // ---- conv + fused BatchNorm partial statistics -------------------------------------------------------
 extern "C" int dg_conv_plan_splits(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (check_geom("dg_conv_plan_splits", N, H, W, C, K, stride, pad, &g) != DG_OK || K == 1) return 0;
+    if (!query_has_plan("dg_conv_plan_splits", op, N, H, W, C, K, stride, pad, &g)) return 1;
     Plan pl;
     make_plan(op, g, &pl);
     return pl.a.splits;
 }
 extern "C" int dg_conv_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
     ConvGeom g;
-    if (check_geom("dg_conv_bnstats_rows", N, H, W, C, K, stride, pad, &g) != DG_OK) return 0;
-    if (K == 1 || stride != 2 || (op != 0 && op != 1)) return 0;
+    if (op == 2 || !query_has_plan("dg_conv_bnstats_rows", op, N, H, W, C, K, stride, pad, &g) || stride != 2) return 0;
     Plan pl;
     make_plan(op, g, &pl);
     return pl.stat_rows;

@@ -645,7 +645,8 @@ def conv_wgrad(dy, x, stride, pad, out=None, accumulate=False):
     if k == 1:
         x16 = int(_is16(x))
     elif _bf16_ok(2, n, h, wd, c, k, stride, pad) or _is16(x) or _is16(dy):
-        xa, x16 = _mixed_operand(x)
+        if c % 8 == 0:                   # (8-element granules of a bf16 x must not straddle a tap: its rows are C channels long)
+            xa, x16 = _mixed_operand(x)
         if k % 8 == 0:
             da, d16 = _mixed_operand(dy)
     if (_is16(dy) and not d16) or (_is16(x) and not x16):

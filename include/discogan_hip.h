@@ -118,6 +118,12 @@ int dg_conv_wgrad(const float* dy, const float* x, float* dw, int N, int H, int 
  * plan_groups: 1 = every problem gets the split-K plan of a launch of its own (results bitwise those of the one-problem call);
  * `groups` = the plan is sized for the whole launch -- the group fills the chip, so each problem is cut into fewer K-slabs (less slab
  * traffic, shorter reduction): the same products in another, equally fixed, summation order. */
+/* Shapes without a plan.  The launch entry points refuse: a forward with C % 32 != 0, a stride-2 input gradient with K % 32 != 0, K neither 1 nor
+ * a multiple of 4, C % 4 != 0, an op outside 0..2 and every geometry dg_conv_fwd refuses (the plane forms dg_conv_*_x3 apply the same channel
+ * rules).  For such a shape, and for the K == 1 head (plain reductions), EVERY planning query (dg_conv_workspace_bytes[_p],
+ * dg_conv_plan_splits[_p], dg_conv_bnstats_rows[_p], dg_conv_bf16_operands_ok, dg_conv_x3_planes_ok, dg_conv_x3_bnstats_rows,
+ * dg_conv_mixed_bnstats_rows) answers "nothing": 0 bytes, 0 rows, not ok (0), 1 split.  No query plans a shape that cannot be launched, and
+ * none fails for any argument tuple; the refusal itself, with its message, comes from the launch entry point. */
 size_t dg_conv_workspace_bytes_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups);
 int dg_conv_bnstats_rows_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec);
 int dg_conv_plan_splits_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups);
@@ -142,7 +148,7 @@ int dg_conv_dgrad_bias_act(const float* dy, const float* w, const float* bias, f
  * pass of dg_bn_train_stats.  stat: [rows][3*cols + 4] floats with rows = dg_conv_bnstats_rows(op,...)
  * and cols = K (op 0, fwd) or C (op 1, dgrad); consume with dg_bn_stats_from_partials. */
 int dg_conv_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad);
-/* number of K splits the plan for this shape uses (1 = no split-K reduction kernel); 0 on bad geometry */
+/* number of K splits the plan for this shape uses (1 = no split-K reduction kernel, also for a shape without a plan: see above) */
 int dg_conv_plan_splits(int op, int N, int H, int W, int C, int K, int stride, int pad);
 int dg_conv_fwd_bnstats(const float* x, const float* w, float* y, int N, int H, int W, int C, int K,
                         float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream);
@@ -379,7 +385,9 @@ int dg_image_prep(const uint8_t* src, float* dst, int N, int H, int W, int x0, i
  * form is passed).  With BOTH operands bf16 and a GEMM of at least 192 rows and columns the work goes to the LDS-DMA kernel
  * (csrc/igemm_dma.hip: 256x256 tile, operand tiles global -> LDS by `buffer_load ... lds`; option "no_dma" 1 keeps the
  * register-staged tiles).  dg_conv_bf16_operands_ok: 0 = the shape has no bf16 kernel, 1 = register-staged bf16 tiles,
- * 2 = the LDS-DMA kernel when both operands are bf16. */
+ * 2 = the LDS-DMA kernel when both operands are bf16.  A bf16 operand is read in 16-byte granules of 8 elements, which must not
+ * straddle a row of its GEMM operand: a bf16 dy (input gradient, weight gradient) needs K % 8 == 0, a bf16 x of the weight gradient
+ * C % 8 == 0 -- otherwise that operand flag is refused (pass the fp32 tensor: the kernel rounds it itself, the same values). */
 int dg_adam_step_flat_bf16(float* p, const float* g, float* m, float* v, size_t n, const double* state,
                            float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                            void* p_bf16, dg_stream_t s);

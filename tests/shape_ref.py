@@ -48,12 +48,37 @@ def conv_ref(op, a, b, stride=2, pad=1, wshape=None):
 
 def taps(op, C, K, stride=2, nz_rows=None):
     """Longest reduction of one output element: forward 16 C; stride-2 input gradient 4 K (four of the sixteen taps land on a
-    pixel); weight gradient = the number of nonzero gradient pixels (nz_rows)."""
+    pixel); the 4 x 4 head's input gradient K (its gradient has one pixel: one tap per input pixel); weight gradient = the number of
+    nonzero gradient pixels (nz_rows)."""
     if op == "fwd":
         return 16 * C
     if op == "dgrad":
-        return (4 if stride == 2 else 16) * K
+        return (4 if stride == 2 else 1) * K
     return nz_rows
+
+
+SIGMOID_TERMS = 8
+
+
+def with_epilogue(n, absref, bias=None, act="none", scaled=False):
+    """(terms, absolute reference) of a sum of n products with a fused epilogue or prologue, for `bound`:
+      bias    one more term of every sum; |bias| (broadcastable to absref) joins the absolute reference;
+      scaled  one factor of every product is itself a rounded product (a gradient taken through an activation's derivative on the
+              way in, dy * act'): one more rounding per product, counted as one more term;
+      act     "relu" / "leaky": slope <= 1, so the bound of the sum holds for the activated value; leaky's multiplication by the slope
+              is one more rounding (one more term).  "sigmoid": slope <= 1/4, and its own evaluation 1 / (1 + exp(-v)) -- exp, add,
+              divide, each a few roundings of values <= 1 -- is covered by SIGMOID_TERMS more terms on an absolute reference raised by 1."""
+    if bias is not None:
+        n, absref = n + 1, absref + bias.abs()
+    if scaled:
+        n = n + 1
+    if act == "leaky":
+        n = n + 1
+    elif act == "sigmoid":
+        n, absref = n + SIGMOID_TERMS, absref + 1.0
+    else:
+        assert act in ("none", "relu"), act
+    return n, absref
 
 
 def bound(ref, absref, n, mult=1, out16=False):
@@ -96,6 +121,41 @@ def shift_h(t):
 def shifted(t):
     """The input moved by one pixel along each spatial axis that has more than one pixel."""
     return [torch.roll(t, 1, dims=d) for d in (-1, -2) if t.shape[d] > 1]
+
+
+def rot_out(w):
+    """A weight [K, C, 4, 4] with its OUTPUT channels rotated by one: what a kernel that mis-indexes a ragged column tile computes."""
+    return torch.roll(w, 1, dims=0)
+
+
+def rot_in(w):
+    """The same weight with its INPUT channels rotated by one: a K-tile (reduction chunk) paired with the wrong channels."""
+    return torch.roll(w, 1, dims=1)
+
+
+def wrong_problems(op, a, b):
+    """(a', b') operand pairs of wrongly indexed problems of conv_ref(op, a, b): the first operand moved by one pixel along each
+    spatial axis (`shifted`), and both channel rotations -- of the weight for "fwd" / "dgrad"; for "wgrad", whose operands are x and dy,
+    x with its channels rotated (= the result's input channels) and dy with its channels rotated (= the result's output channels).
+    A rotation over an axis of one element would be the right problem and is left out."""
+    out = [(s, b) for s in shifted(a)]
+    if op == "wgrad":
+        if a.shape[1] > 1:
+            out.append((torch.roll(a, 1, dims=1), b))
+        if b.shape[1] > 1:
+            out.append((a, torch.roll(b, 1, dims=1)))
+    else:
+        if b.shape[0] > 1:
+            out.append((a, rot_out(b)))
+        if b.shape[1] > 1:
+            out.append((a, rot_in(b)))
+    return out
+
+
+def rnd(*shape, seed=0, scale=1.0):
+    """Uniform in [-scale, scale) from a fixed seed (CPU)."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(*shape, generator=g) * 2 - 1) * scale
 
 
 # ---- BatchNorm (training mode) + activation -------------------------------------------------------------------------

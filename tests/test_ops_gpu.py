@@ -901,6 +901,23 @@ def test_errors_are_reported_not_fatal():
         ops.conv_fwd(nhwc(rnd(2, 64, 8, 8)), krsc(rnd(64, 64, 4, 4)), 1, 1)
     with pytest.raises(_lib.DiscoganHipError, match="CPU"):
         ops.conv_fwd(rnd(2, 64, 8, 8), rnd(64, 64, 4, 4), 2, 1)
+    # stride-2 input gradient with K = 4, C = 96: the plan queries ops.conv_dgrad asks BEFORE it launches used to divide by zero
+    # (the process died with SIGFPE); the entry point's refusal must arrive as an exception, in every arithmetic and grouped too
+    w4 = krsc(rnd(4, 96, 4, 4))
+    for prec in (ops.PREC_F32, ops.PREC_BF16, ops.PREC_F32X3):
+        with ops.use(ops.Context(prec=prec)):
+            with pytest.raises(_lib.DiscoganHipError, match="multiple of 32"):
+                ops.conv_dgrad(nhwc(rnd(2, 4, 4, 4)), w4, (8, 8), 2, 1)
+            with pytest.raises(_lib.DiscoganHipError, match="multiple of 32"):
+                ops.conv_dgrad_g([nhwc(rnd(2, 4, 4, 4))] * 2, [w4] * 2, (8, 8), 2, 1)
+    # ... and through the modules: ConvTranspose2d(4, 96) forward and the backward of Conv2d(96, 4) are that input gradient
+    from discogan_modernized_amd import model
+    with pytest.raises(_lib.DiscoganHipError, match="multiple of 32"):
+        model.ConvTranspose2d(4, 96).to(DEV)(nhwc(rnd(2, 4, 4, 4)))
+    conv, xin = model.Conv2d(96, 4).to(DEV), nhwc(rnd(2, 96, 8, 8)).requires_grad_(True)
+    y = conv(xin)                                      # (the forward takes K % 4 == 0)
+    with pytest.raises(_lib.DiscoganHipError, match="multiple of 32"):
+        y.backward(nhwc(rnd(2, 4, 4, 4)))
 
 
 # ---- bf16 activation storage (the *_t entry points): bf16 in / bf16 out, fp32 arithmetic inside --------------------------
