@@ -16,6 +16,10 @@ Data sources (``--data_source``):
   synthetic  uniform tensors (``--synthetic_size`` images per domain): what the benchmark metric is defined on
   auto       tensors if --data_A/--data_B are given, shards if --shard_A/--shard_B, files if the task's directory exists, else synthetic
 
+Sample grids (samples.py): every ``--image_save_interval`` iterations (0 = never) the four generator passes run on the held-out split
+-- the files source's test lists, else ``--test_A/--test_B`` -- and ``results/.../samples/samples_iter_{i}.png`` is written.  As in the
+reference these passes move the generators' BatchNorm running statistics.
+
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
 distributed_image_translation.py:203-216,451-452 -- ONE permutation per epoch from a seed shared by all ranks
@@ -67,6 +71,10 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     # additions of this implementation
     p.add_argument("--data_A", type=str, default=None, help="torch.save'd float tensor [n,3,S,S] for domain A")
     p.add_argument("--data_B", type=str, default=None, help="torch.save'd float tensor [n,3,S,S] for domain B")
+    p.add_argument("--test_A", type=str, default=None,
+                   help="held-out images of domain A for the sample grids (tensor file like --data_A: float [n,3,S,S] or uint8 [n,S,S,3], "
+                        "first --n_test used); the files source takes its test lists instead")
+    p.add_argument("--test_B", type=str, default=None, help="held-out images of domain B (see --test_A)")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -247,6 +255,11 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     data_size = data.size
     if is_main:
         print(f"data source: {data_kind} ({data_size} images per domain)", flush=True)
+    # the held-out split of the sample grids (samples.py), resident on the device for the run; the saving rank alone loads it and samples
+    split = None
+    if is_main:
+        from . import samples
+        split = samples.load_split(args, data_kind, device, world_size)
     n_batches = batches_per_epoch(args, data_size, world_size)
     if n_batches < 1:
         raise ValueError(f"batch_size {args.batch_size} leaves no full batch in {data_size} images on {world_size} rank(s)")
@@ -289,6 +302,10 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                 print(msg + f"  [{(iters - start_iters + 1) * args.batch_size * world_size / max(dt, 1e-9):.1f} img/s]", flush=True)
                 with open(log_file, "a") as f:
                     f.write(msg + "\n")
+            if split is not None and iters % args.image_save_interval == 0:
+                # before the model save of the same iteration (image_translation.py:411-424): the passes move the generators' BatchNorm
+                # running statistics, and a checkpoint written at `iters` carries them
+                samples.save_samples(trainer, split, result_path / "samples", iters)
             if is_main and iters % args.model_save_interval == 0:
                 save_models(trainer, model_path, str(iters), iters + 1, getattr(args, "save_train_state", False),
                             loader=dict(epoch=epoch, batch=i + 1))

@@ -217,6 +217,38 @@ def u8hwc_to_f32chw(x_u8, bgr=False):
     return y
 
 
+def sample_grid(batches, rows, gap=2, bg=255):
+    """1..8 float32 NCHW batches [n_c,3,S,S] (n_c >= rows) -> ONE uint8 canvas [rows*(S+gap)+gap, cols*(S+gap)+gap, 3] on the device:
+    cell (r, c) = image r of batches[c], pixel = rint(clamp(x, 0, 1) * 255) (half to even, NaN -> 0), every other byte ``bg``
+    (image_translation.py:170-209).  One launch writes the whole canvas (dg_sample_grid_u8)."""
+    import ctypes as C
+    batches = list(batches)
+    if not batches:
+        raise _lib.DiscoganHipError("sample_grid needs at least one batch")
+    _check_dev(*batches)
+    xs = [b.contiguous() for b in batches]
+    S = xs[0].shape[-1]
+    for x in xs:
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != S or x.shape[3] != S or x.device != xs[0].device:
+            raise _lib.DiscoganHipError(f"sample_grid needs [n,3,S,S] batches of one S on one device, got {tuple(x.shape)}")
+        if x.shape[0] < rows:
+            raise _lib.DiscoganHipError(f"sample_grid: a batch of {x.shape[0]} images cannot fill {rows} rows")
+    cols, pitch = len(xs), S + int(gap)
+    canvas = torch.empty((max(rows, 0) * pitch + int(gap), cols * pitch + int(gap), 3), device=xs[0].device, dtype=torch.uint8)
+    tab = (C.c_void_p * cols)(*[x.data_ptr() for x in xs])
+    _lib.check(_lib.load().dg_sample_grid_u8(tab, cols, int(rows), S, int(gap), int(bg), _ptr(canvas), _stream()), "dg_sample_grid_u8")
+    return canvas
+
+
+def f32chw_to_u8hwc(x):
+    """float32 NCHW [n,3,S,S] -> uint8 [n,S,S,3] = rint(clamp(x, 0, 1) * 255): the inverse of ``u8hwc_to_f32chw`` (a one-column
+    grid without gutters is exactly the images one under the other)."""
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise _lib.DiscoganHipError(f"f32chw_to_u8hwc needs a square [n,3,S,S] batch, got {tuple(x.shape)}")
+    n, S = x.shape[0], x.shape[3]
+    return sample_grid([x], n, gap=0, bg=0).view(n, S, S, 3)
+
+
 def krsc_param(w_logical):
     """[K,C,4,4] contiguous -> same logical tensor whose memory is [K,4,4,C] (dim 1 innermost)."""
     return w_logical.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)

@@ -695,6 +695,32 @@ class DiscoGANTrainer:
         if self._ev_dis_ready is not None:
             torch.cuda.current_stream(self.device).wait_event(self._ev_dis_ready)
 
+    def sample(self, test_A, test_B):
+        """The four generator passes of a sampling event on the held-out split (image_translation.py:170-184):
+        ``AB = G_B(test_A); BA = G_A(test_B); ABA = G_A(AB); BAB = G_B(BA)``, returned as device tensors [n,3,S,S].
+
+        Like the reference: under ``no_grad`` but in whatever mode the generators are in -- training mode in a training run, so every
+        pass normalises with the statistics of the whole split (ONE batch per pass) and each generator's BatchNorm buffers advance by
+        two forward calls.  Nothing else changes: the passes run eagerly on the main stream between iterations under this trainer's own
+        arithmetic, write no gradient, touch no optimiser or discriminator state and no captured graph or its static inputs."""
+        if test_A.dim() != 4 or test_B.dim() != 4 or test_A.shape[0] < 2 or test_B.shape[0] < 2:
+            raise ValueError("sample() needs two batches [n,3,S,S] with n >= 2 (train-mode BatchNorm needs more than one value per "
+                             f"channel at the bottleneck), got {tuple(test_A.shape)} and {tuple(test_B.shape)}")
+        self.finish()
+        from . import ops as _ops
+        self.ctx.prec = {"f32": _ops.PREC_F32, "bf16": _ops.PREC_BF16, "f32x3": _ops.PREC_F32X3}[self.mfma_dtype]
+        self.ctx.shadow, self.ctx.act16, self.ctx.x3 = bool(self.bf16_shadow), self.act_dtype == "bf16", bool(self.x3_planes)
+        self.ctx.clear()
+        try:
+            with torch.no_grad(), _ops.use(self.ctx):
+                AB = self.generator_B(test_A)
+                BA = self.generator_A(test_B)
+                ABA = self.generator_A(AB)
+                BAB = self.generator_B(BA)
+        finally:
+            self.ctx.clear()                   # no bf16 shadow or plane triple of a sampling pass outlives it
+        return AB, BA, ABA, BAB
+
     # ---------------------------------------------------------------------------------------------
     def losses_to_floats(self, out):
         vals = torch.stack([getattr(out, k).detach().reshape(()) for k in LOG_KEYS]).cpu().tolist()

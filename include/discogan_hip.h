@@ -375,6 +375,14 @@ int dg_u8hwc_to_f32chw(const uint8_t* src, float* dst, int N, int H, int W, int 
  * and edge clamp (dataset.py:62), / 255 and CHW (dataset.py:65-66).  mode 0: float arithmetic, unrounded (what the
  * reference's float64 domain-'A' image gets); mode 1: cv2's 8-bit fixed-point path, result rounded to uint8 before / 255. */
 int dg_image_prep(const uint8_t* src, float* dst, int N, int H, int W, int x0, int cw, int erode, int mode, int S, dg_stream_t s);
+/* ---- sample grids (image_translation.py:170-209): the inverse of the ingest, tiled -------------------------
+   src: HOST table of `cols` device pointers, each a float batch [n_c][3][S][S] (NCHW, n_c >= rows).
+   canvas: device uint8 [Hc][Wc][3], Hc = rows*(S+gap)+gap, Wc = cols*(S+gap)+gap.
+   Cell (r, c) holds image r of src[c]; every byte outside the cells is `bg`.
+   pixel = (uint8) rintf(clamp(x, 0, 1) * 255.0f)   (round half to even; NaN -> 0)
+   1 <= cols <= 8, rows >= 1, S >= 1 (any S), gap >= 0, 0 <= bg <= 255.  One launch writes the whole canvas, gutters included.
+   cols = 1, gap = 0 is float [n][3][S][S] -> uint8 [n][S][S][3], the inverse of dg_u8hwc_to_f32chw for all 256 values. */
+int dg_sample_grid_u8(const float* const* src, int cols, int rows, int S, int gap, int bg, uint8_t* canvas, dg_stream_t s);
 
 /* ---- bf16 shadow operands for the bf16 matrix path (option "bf16" = 1; BASELINE configs[4]) ---------------------
  * A shadow is a bf16 (RNE) copy of an fp32 tensor with the same logical layout, written by the tensor's PRODUCER so that
