@@ -1,4 +1,5 @@
-"""fp64 CPU references and the elementwise error bound of tests/test_shapes_gpu.py (imported by the CPU tests too).
+"""fp64 CPU references and the elementwise error bound of tests/test_shapes_gpu.py, tests/test_channels_gpu.py and
+tests/test_reductions_gpu.py (imported by the CPU tests too).
 
 Convolutions: a sum of n products evaluated in fp32 in ANY order (split-K, trees, MFMA blocks) is within
     gamma(n) * sum |a_i * b_i|,   gamma(n) = n u / (1 - n u),  u = 2^-24
@@ -223,3 +224,168 @@ def bn_dx_violations(got, ref, tol=BN_TOL, out16=False):
 def bn_roll_channels(t, k=1):
     """The same tensor with its channels rotated by k: what a kernel that reads the parameters of the wrong channel block writes."""
     return torch.roll(t, k, dims=1)
+
+
+# ---- reductions past their grid caps and second stages (tests/test_reductions_*.py) ------------------------------------
+def exceeds(err, b):
+    """Number of elements of err past the bound b; a non-finite error counts as past it (NaN compares false both ways)."""
+    return int((~err.le(b)).sum())
+
+
+# BatchNorm statistics from partial rows (include/discogan_hip.h, csrc/norm_act.hip "Finalize from the conv kernels' partial rows"):
+# a row is {count, -, -, -, shift[C], sum(y - shift)[C], sum((y - shift)^2)[C]}; row 0 has count > 0; rows with count 0 are skipped
+# and their other fields are never written by the producers.
+def partial_rows(y, counts, sentinel=float("nan")):
+    """fp32 rows [P, 3 C + 4] of y [M, C] (fp32) cut into consecutive runs of counts[p] samples: sums in fp64 about the run's first
+    sample, rounded to fp32 once.  A count-0 row holds `sentinel` in every other field -- what an uninitialised buffer may hold there."""
+    y64 = f64(y)
+    M, C = y64.shape
+    cnt = torch.as_tensor(counts, dtype=torch.long)
+    P = cnt.numel()
+    assert int(cnt.sum()) == M and int(cnt[0]) > 0
+    ne = cnt > 0
+    first = torch.cumsum(cnt, 0) - cnt
+    rid = torch.repeat_interleave(torch.arange(P), cnt)
+    shift = torch.zeros(P, C, dtype=torch.float64)
+    shift[ne] = y64[first[ne]]
+    d = y64 - shift[rid]
+    rows = torch.full((P, 3 * C + 4), sentinel, dtype=torch.float64)
+    rows[:, 0] = cnt.double()
+    rows[ne, 1:4] = 0.0
+    rows[:, 4:4 + C] = torch.where(ne[:, None], shift, rows[:, 4:4 + C])
+    s = torch.zeros(P, C, dtype=torch.float64).index_add_(0, rid, d)
+    q = torch.zeros(P, C, dtype=torch.float64).index_add_(0, rid, d * d)
+    rows[:, 4 + C:4 + 2 * C] = torch.where(ne[:, None], s, rows[:, 4 + C:4 + 2 * C])
+    rows[:, 4 + 2 * C:] = torch.where(ne[:, None], q, rows[:, 4 + 2 * C:])
+    return rows.float()
+
+
+def stats_dict(mean, var, M, momentum=0.1):
+    """mean, biased var (fp64 [C]) -> also the running buffers after one step from (0, 1) with the unbiased M / (M - 1)."""
+    return dict(mean=mean, var=var, rmean=momentum * mean, rvar=(1 - momentum) + momentum * var * M / (M - 1))
+
+
+def partial_rows_merge(rows, M, drop=None, count_empty=None, rotate_shift=False):
+    """fp64 merge of partial rows, every row re-referenced to row 0's shift as the kernels do.  The wrong problems: `drop` leaves one
+    row out, `count_empty` takes a count-0 row's fields as data, `rotate_shift` pairs every row's sums with the shifts of the
+    neighbouring channel."""
+    r = f64(rows)
+    C = (r.shape[1] - 4) // 3
+    use = r[:, 0] > 0
+    if drop is not None:
+        use[drop] = False
+    if count_empty is not None:
+        use[count_empty] = True
+    n, sh, s, q = r[use, 0:1], r[use, 4:4 + C], r[use, 4 + C:4 + 2 * C], r[use, 4 + 2 * C:]
+    if rotate_shift:
+        sh = torch.roll(sh, 1, dims=1)
+    G = sh[0] if rotate_shift else r[0, 4:4 + C]
+    d = sh - G
+    S, Q = (s + n * d).sum(0), (q + d * (2.0 * s + n * d)).sum(0)
+    dm = S / M
+    return stats_dict(G + dm, (Q / M - dm * dm).clamp_min(0.0), M)
+
+
+# (P, C, data): "plain" y in [-1, 1); "offset" y + 100 (a mean far larger than the deviation); "ramp" y + 0.01 * row index (the rows'
+# shifts differ by far more than the deviation within a row: the re-referencing term d * (2 s + n d) carries the variance)
+PARTIALS_CASES = [(1, 4, "plain"), (2, 4, "plain"), (255, 12, "plain"), (256, 12, "plain"), (257, 12, "plain"), (4095, 64, "plain"),
+                  (4096, 192, "plain"), (4097, 100, "offset"), (5119, 12, "ramp"), (5120, 12, "ramp"), (33000, 8, "offset")]
+PARTIALS_TWO_LEVEL_FROM = 4096        # dg_bn_partials_workspace_bytes(P, C) > 0 exactly from here
+PARTIALS_TOL = 2.0 ** -20             # GPU results against the fp64 statistics of y (see stats_violations)
+PARTIALS_REF_TOL = 2.0 ** -22         # fp64 merge of the once-rounded rows against the same
+
+_PARTIALS = {}
+
+
+def partials_case(P, C, data):
+    """One case, built once: counts in 1..7, about a tenth of the rows empty (never row 0), one run of 260 empty rows and an empty
+    last row wherever P allows; sentinel NaN / 3e38 by turns.  dict: y, M, rows, ref (fp64 statistics of y), merged, wrong (list of
+    (name, merge of a wrong problem))."""
+    key = (P, C, data)
+    if key in _PARTIALS:
+        return _PARTIALS[key]
+    g = torch.Generator().manual_seed(1000 + P)
+    cnt = torch.randint(1, 8, (P,), generator=g)
+    empty = torch.rand(P, generator=g) < 0.1
+    if P >= 600:
+        empty[P // 3:P // 3 + 260] = True
+    if P >= 3:
+        empty[-1] = True
+    if P < 16:
+        empty[:-1] = False
+    empty[0] = False
+    cnt[empty] = 0
+    if P == 1:
+        cnt[0] = max(int(cnt[0]), 2)                   # training-mode statistics take M >= 2
+    M = int(cnt.sum())
+    y = rnd(M, C, seed=2000 + P)
+    rid = torch.repeat_interleave(torch.arange(P), cnt)
+    if data == "offset":
+        y = y + 100.0
+    elif data == "ramp":
+        y = y + 0.01 * rid[:, None].float()
+    else:
+        assert data == "plain"
+    sentinel = float("nan") if PARTIALS_CASES.index(key) % 2 == 0 else 3e38
+    rows = partial_rows(y, cnt, sentinel)
+    y64 = f64(y)
+    mean = y64.mean(0)
+    ref = stats_dict(mean, ((y64 - mean) ** 2).mean(0), M)
+    nonempty = (cnt > 0).nonzero().flatten()
+    wrong = []
+    if nonempty.numel() > 1:
+        wrong.append(("row dropped", partial_rows_merge(rows, M, drop=int(nonempty[nonempty.numel() // 2]))))
+    wrong.append(("shifts rotated", partial_rows_merge(rows, M, rotate_shift=True)))
+    if bool(empty.any()):
+        wrong.append(("empty row counted", partial_rows_merge(rows, M, count_empty=int(empty.nonzero()[0]))))
+    out = dict(y=y, M=M, counts=cnt, rows=rows, ref=ref, merged=partial_rows_merge(rows, M), wrong=wrong, sentinel=sentinel)
+    _PARTIALS[key] = out
+    return out
+
+
+def stats_violations(got, ref, tol, eps=1e-5):
+    """got: dict of mean, var, rmean, rvar (fp64 [C]).  mean and running_mean within tol of (|mean| + std), var within tol of
+    (var + eps), running_var within tol of (var + 1) -- the scales of test_batchnorm_channels_rows_forms.  Number of violations."""
+    sc = ref["mean"].abs() + ref["var"].sqrt()
+    return (exceeds((got["mean"] - ref["mean"]).abs(), tol * sc) + exceeds((got["var"] - ref["var"]).abs(), tol * (ref["var"] + eps))
+            + exceeds((got["rmean"] - ref["rmean"]).abs(), tol * sc) + exceeds((got["rvar"] - ref["rvar"]).abs(), tol * (ref["var"] + 1.0)))
+
+
+def stats_worst(got, ref, tol, eps=1e-5):
+    """Largest error / bound ratio of stats_violations' four comparisons."""
+    sc = ref["mean"].abs() + ref["var"].sqrt()
+    return max(float(((got["mean"] - ref["mean"]).abs() / (tol * sc)).max()), float(((got["var"] - ref["var"]).abs() / (tol * (ref["var"] + eps))).max()),
+               float(((got["rmean"] - ref["rmean"]).abs() / (tol * sc)).max()), float(((got["rvar"] - ref["rvar"]).abs() / (tol * (ref["var"] + 1.0))).max()))
+
+
+# Feature matching, one layer: loss = mean_j (mean_n real - mean_n fake)^2 (csrc/loss.hip).
+def fm_ref(real, fake, drop_last=False, swap=0):
+    """fp64 reference on logical [N, C, H, W] tensors: dict of diff [C, H, W], absdiff (= mean_n |real| + mean_n |fake|), loss.
+    Wrong problems: drop_last leaves the last image out of real's sum (still divided by N: what a dropped batch chunk computes);
+    swap > 0 exchanges real and fake in the first `swap` images."""
+    r, f = f64(real), f64(fake)
+    N = r.shape[0]
+    if swap:
+        r, f = torch.cat([f[:swap], r[swap:]]), torch.cat([r[:swap], f[swap:]])
+    rsum = r[:-1].sum(0) if drop_last else r.sum(0)
+    diff = rsum / N - f.sum(0) / N
+    return dict(diff=diff, absdiff=r.abs().sum(0) / N + f.abs().sum(0) / N, loss=(diff * diff).mean(), N=N, J=diff.numel())
+
+
+def fm_diff_bound(ref):
+    """N - 1 additions per mean in any order (batch chunks, then chunks), the rounded 1 / N and the product with it, the subtraction."""
+    return gamma(ref["N"] + 2) * ref["absdiff"] + TINY
+
+
+def fm_loss_bound(ref, terms):
+    """`terms` squares per fp32 thread sum (fp64 above that): each square one rounding, terms - 1 additions, the result's rounding to
+    fp32 and the scale 1 / J -> gamma(terms + 4) on the fp64 mean of squares; plus what the error b of diff moves it by:
+    |(d + e)^2 - d^2| <= 2 |d| b + b^2."""
+    b = fm_diff_bound(ref)
+    return gamma(terms + 4) * float(ref["loss"]) * (1 + gamma(terms + 4)) + float((2 * ref["diff"].abs() * b + b * b).mean()) * (1 + gamma(terms + 4))
+
+
+def capped_grid(work, cap, per_block=256):
+    """Blocks of a capped streaming launch over `work` items, and the most trips any thread takes."""
+    g = max(1, min((work + per_block - 1) // per_block, cap))
+    return g, (work + g * per_block - 1) // (g * per_block)

@@ -852,11 +852,11 @@ def test_adam_flat_matches_torch():
     assert float(mo.state[0]) == 5.0
 
 
-@pytest.mark.parametrize("n,off", [(8 * 1000 + 5, 0), (4096, 4), (37, 0), (100003, 12), (1 << 20, 0)])
-def test_adam_forms_agree(n, off):
+def adam_forms(n, off):
     """The Adam kernel's three forms -- plain, + bf16 shadow, + three bf16 planes (8 parameters per trip with 16-byte plane stores where
     the range starts on a 16-byte plane granule, else 4) -- update p / m / v bit for bit alike on ranges of any length and offset; the
-    shadow is the rounded parameter, the planes are dg_f32_to_bf16x3 of it."""
+    shadow is the rounded parameter, the planes are dg_f32_to_bf16x3 of it.  Returns (the four inputs, the three runs' (p, m, v, shadow,
+    planes), the step state)."""
     tot = n + off + 16
     base = [torch.randn(tot, generator=torch.Generator().manual_seed(i)).to(DEV) * 0.05 for i in range(4)]
     base[3].abs_()
@@ -882,6 +882,13 @@ def test_adam_forms_agree(n, off):
     ops.f32_to_bf16x3(p[off:off + n].clone(), ref3)
     got3 = runs[2][4]
     assert torch.equal(got3[:, off:off + n], ref3[:, :n]) and not bool(got3[:, off + n:].float().any()) and not bool(got3[:, :off].float().any())
+    return base, runs, state
+
+
+@pytest.mark.parametrize("n,off", [(8 * 1000 + 5, 0), (4096, 4), (37, 0), (100003, 12), (1 << 20, 0)])
+def test_adam_forms_agree(n, off):
+    """adam_forms on ranges of any length and offset (tests/test_reductions_gpu.py runs it past the kernel's grid cap and against float64)."""
+    adam_forms(n, off)
 
 
 def test_layout_roundtrip():
