@@ -119,6 +119,8 @@ SIGNATURES = {
     "dg_u8hwc_to_f32chw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "dg_image_prep": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dg_sample_grid_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
+    "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
     "dg_adam_step_flat_bf16": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _p]),
     "dg_f32_to_bf16": (_i, [_p, _p, _z, _p]),
     "dg_bn_act_fwd_bf16": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _p]),

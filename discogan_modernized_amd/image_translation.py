@@ -20,6 +20,10 @@ Sample grids (samples.py): every ``--image_save_interval`` iterations (0 = never
 -- the files source's test lists, else ``--test_A/--test_B`` -- and ``results/.../samples/samples_iter_{i}.png`` is written.  As in the
 reference these passes move the generators' BatchNorm running statistics.
 
+Held-out evaluation (evaluate.py): every ``--eval_interval`` iterations (0 = never, the default) the same split is scored -- PSNR, SSIM
+and MAE of the reconstructions, and of the translations when the split is paired (``--eval_paired``) -- and one line goes to
+``results/.../eval_log.txt``.  An iteration that also writes a sample grid runs the four passes once for both.
+
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
 distributed_image_translation.py:203-216,451-452 -- ONE permutation per epoch from a seed shared by all ranks
@@ -75,6 +79,11 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
                    help="held-out images of domain A for the sample grids (tensor file like --data_A: float [n,3,S,S] or uint8 [n,S,S,3], "
                         "first --n_test used); the files source takes its test lists instead")
     p.add_argument("--test_B", type=str, default=None, help="held-out images of domain B (see --test_A)")
+    p.add_argument("--eval_interval", type=int, default=0,
+                   help="every N iterations score the held-out split (PSNR / SSIM / MAE, evaluate.py) into eval_log.txt; 0 = never")
+    p.add_argument("--eval_paired", type=str, default="auto", choices=["auto", "on", "off"],
+                   help="image i of test A and of test B show the same thing, so the translations are scored too; auto: the files "
+                        "source of edges2shoes / edges2handbags")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -239,6 +248,10 @@ def batches_per_epoch(args, data_size, world_size):
 def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=None):
     if args.task_name not in TASKS:
         raise ValueError(f"unknown task_name {args.task_name}; choose from {TASKS}")
+    eval_interval = int(getattr(args, "eval_interval", 0) or 0)
+    if eval_interval > 0:
+        from . import evaluate
+        evaluate.check_size(args.image_size)
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible: this implementation has no CPU path (use the reference for CPU runs)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -255,11 +268,13 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     data_size = data.size
     if is_main:
         print(f"data source: {data_kind} ({data_size} images per domain)", flush=True)
-    # the held-out split of the sample grids (samples.py), resident on the device for the run; the saving rank alone loads it and samples
+    # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
+    # saving rank alone loads it, samples and evaluates
     split = None
     if is_main:
         from . import samples
         split = samples.load_split(args, data_kind, device, world_size)
+    eval_paired = eval_interval > 0 and evaluate.paired_default(args, data_kind)
     n_batches = batches_per_epoch(args, data_size, world_size)
     if n_batches < 1:
         raise ValueError(f"batch_size {args.batch_size} leaves no full batch in {data_size} images on {world_size} rank(s)")
@@ -302,10 +317,20 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                 print(msg + f"  [{(iters - start_iters + 1) * args.batch_size * world_size / max(dt, 1e-9):.1f} img/s]", flush=True)
                 with open(log_file, "a") as f:
                     f.write(msg + "\n")
-            if split is not None and iters % args.image_save_interval == 0:
+            sampling = split is not None and args.image_save_interval > 0 and iters % args.image_save_interval == 0
+            evaluating = split is not None and eval_interval > 0 and iters % eval_interval == 0
+            if sampling or evaluating:
                 # before the model save of the same iteration (image_translation.py:411-424): the passes move the generators' BatchNorm
-                # running statistics, and a checkpoint written at `iters` carries them
-                samples.save_samples(trainer, split, result_path / "samples", iters)
+                # running statistics, and a checkpoint written at `iters` carries them; they run once for both events
+                outs = trainer.sample(*split)
+                if sampling:
+                    samples.save_samples(trainer, split, result_path / "samples", iters, outs=outs)
+                if evaluating:
+                    res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs)
+                    msg = evaluate.format_eval(iters, res)
+                    print(msg, flush=True)
+                    with open(result_path / "eval_log.txt", "a") as f:
+                        f.write(msg + "\n")
             if is_main and iters % args.model_save_interval == 0:
                 save_models(trainer, model_path, str(iters), iters + 1, getattr(args, "save_train_state", False),
                             loader=dict(epoch=epoch, batch=i + 1))

@@ -249,6 +249,25 @@ def f32chw_to_u8hwc(x):
     return sample_grid([x], n, gap=0, bg=0).view(n, S, S, 3)
 
 
+def image_metrics(x, y):
+    """Two float32 NCHW batches [n,3,S,S] (S >= 11) -> float32 [n,3] on the device: row i = (MSE, MAE, SSIM) of the pair (x[i], y[i]),
+    values taken as they are (data range 1; SSIM: 11 x 11 Gaussian window, sigma 1.5, valid windows).  Row i depends on pair i alone
+    and is bitwise repeatable (dg_image_metrics)."""
+    _check_dev(x, y)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or tuple(y.shape) != tuple(x.shape) or y.device != x.device:
+        raise _lib.DiscoganHipError(f"image_metrics needs two [n,3,S,S] batches of one shape on one device, got {tuple(x.shape)} and "
+                                    f"{tuple(y.shape)}")
+    n, S = int(x.shape[0]), int(x.shape[3])
+    if n < 1 or S < 11:
+        raise _lib.DiscoganHipError(f"image_metrics needs n >= 1 images of S >= 11 pixels (the 11 x 11 window), got n={n}, S={S}")
+    xc, yc = x.contiguous(), y.contiguous()
+    out = torch.empty((n, 3), device=x.device, dtype=torch.float32)
+    L = _lib.load()
+    ws, ws_bytes = _ws(L.dg_image_metrics_workspace_bytes(n, S), x.device)
+    _lib.check(L.dg_image_metrics(_ptr(xc), _ptr(yc), n, S, _ptr(out), _ptr(ws), ws_bytes, _stream()), "dg_image_metrics")
+    return out
+
+
 def krsc_param(w_logical):
     """[K,C,4,4] contiguous -> same logical tensor whose memory is [K,4,4,C] (dim 1 innermost)."""
     return w_logical.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)

@@ -49,10 +49,13 @@ def _load_tensor_split(path, n_test, image_size, device):
 
 
 def load_split(args, data_kind, device, world_size=1):
-    """(test_A, test_B) float [n,3,S,S] on the device, or None when this run does not sample (one printed line says why when a
-    split was asked for and is too small).  Call it on the rank that saves only."""
+    """(test_A, test_B) float [n,3,S,S] on the device, or None when this run neither samples (--image_save_interval) nor evaluates
+    (--eval_interval, evaluate.py) (one printed line per event kind says why when a split was asked for and is too small).  Call it on
+    the rank that saves only."""
     from . import dataset as ds
-    if int(getattr(args, "image_save_interval", 0) or 0) <= 0:
+    sampling = int(getattr(args, "image_save_interval", 0) or 0) > 0
+    evaluating = int(getattr(args, "eval_interval", 0) or 0) > 0
+    if not (sampling or evaluating):
         return None
     test_A, test_B = getattr(args, "test_A", None), getattr(args, "test_B", None)
     if data_kind == "files":
@@ -72,7 +75,9 @@ def load_split(args, data_kind, device, world_size=1):
     else:
         return None
     if min(len(split[0]), len(split[1])) < 2:
-        print(f"sampling off: the test split holds {len(split[0])} / {len(split[1])} usable images (two per side are needed)", flush=True)
+        for on, what in ((sampling, "sampling"), (evaluating, "evaluation")):
+            if on:
+                print(f"{what} off: the test split holds {len(split[0])} / {len(split[1])} usable images (two per side are needed)", flush=True)
         return None
     return split[0], split[1]
 
@@ -96,10 +101,11 @@ def write_png(canvas, path):
     return path
 
 
-def save_samples(trainer, split, save_dir, iteration):
-    """One sampling event: four passes, grid kernel, one D2H copy, PNG.  Returns the path written."""
+def save_samples(trainer, split, save_dir, iteration, outs=None):
+    """One sampling event: four passes (unless the caller already ran them for this iteration: ``outs``), grid kernel, one D2H copy,
+    PNG.  Returns the path written."""
     test_A, test_B = split
-    AB, BA, ABA, BAB = trainer.sample(test_A, test_B)
+    AB, BA, ABA, BAB = trainer.sample(test_A, test_B) if outs is None else outs
     canvas = compose(test_A, test_B, AB, BA, ABA, BAB).cpu()
     save_dir = Path(save_dir)
     save_dir.mkdir(parents=True, exist_ok=True)

@@ -383,6 +383,16 @@ int dg_image_prep(const uint8_t* src, float* dst, int N, int H, int W, int x0, i
    1 <= cols <= 8, rows >= 1, S >= 1 (any S), gap >= 0, 0 <= bg <= 255.  One launch writes the whole canvas, gutters included.
    cols = 1, gap = 0 is float [n][3][S][S] -> uint8 [n][S][S][3], the inverse of dg_u8hwc_to_f32chw for all 256 values. */
 int dg_sample_grid_u8(const float* const* src, int cols, int rows, int S, int gap, int bg, uint8_t* canvas, dg_stream_t s);
+/* ---- held-out image metrics (evaluate.py): per image pair MSE, MAE and SSIM of two float batches [n][3][S][S] (NCHW, any 4-byte
+   alignment), values taken as they are (no clamp, no quantisation; data range 1).
+   out: device float [n][3] = { mean (x-y)^2, mean |x-y|, SSIM }.  SSIM (Wang et al. 2004): 11 x 11 Gaussian window, sigma 1.5
+   (normalised in double, rounded once to fp32, 2-D weight g[i] g[j]), the (S-10)^2 "valid" windows per channel, C1 = 0.01^2,
+   C2 = 0.03^2, mean over the 3 channels and all windows.  S >= 11, n >= 1.
+   ws: dg_image_metrics_workspace_bytes(n, S) bytes, 8-byte aligned (fp64 partials, n times a function of S).
+   fp32 inside a thread, fp64 from the wave sum on, fixed order, no atomics: bitwise repeatable, and row i does not depend on n or on
+   the other pairs (a NaN / inf in pair i reaches row i only). */
+size_t dg_image_metrics_workspace_bytes(int n, int S);
+int dg_image_metrics(const float* x, const float* y, int n, int S, float* out /* [n][3] */, void* ws, size_t ws_bytes, dg_stream_t s);
 
 /* ---- bf16 shadow operands for the bf16 matrix path (option "bf16" = 1; BASELINE configs[4]) ---------------------
  * A shadow is a bf16 (RNE) copy of an fp32 tensor with the same logical layout, written by the tensor's PRODUCER so that
