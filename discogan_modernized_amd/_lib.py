@@ -101,6 +101,8 @@ SIGNATURES = {
     "dg_loss_mix_bwd": (_i, [_p, _p, _i, _f, _i, _i, _p]),
     "dg_adam_advance": (_i, [_p, _d, _d, _d, _p]),
     "dg_adam_step_flat": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p]),
+    "dg_ema_update_flat": (_i, [_p, _p, _z, _f, _p]),
+    "dg_swap_flat": (_i, [_p, _p, _z, _p]),
     "dg_bce_target_fwd": (_i, [_p, _p, _i, _p, _p]),
     "dg_bce_target_bwd": (_i, [_p, _p, _i, _p, _p, _p]),
     "dg_hinge_fwd": (_i, [_p, _p, _z, _f, _p, _p, _z, _p]),

@@ -209,3 +209,70 @@ extern "C" int dg_f32_to_bf16x3(const float* x, void* y3, size_t n, size_t plane
     DG_CHECK_LAUNCH("f32_to_bf16x3");
     return DG_OK;
 }
+
+// ---- exponential moving average of a flat parameter buffer (optim.EMA) ---------------------------------------------------------
+// ema += (p - ema) * w with w = 1 - decay, one launch over the whole flat generator group: 12 B/param (read p, read + write ema).
+// Lerp form, every operation rounded on its own: p == ema leaves ema bitwise unchanged for every w (a generator outside the loss of
+// recongan / gan keeps its EMA equal to itself), and the kernel's two code paths (16-byte trips, scalar tail) give the same bits as a
+// host that rounds op by op.  Geometry of the Adam kernel above.
+__device__ __forceinline__ float ema_one(float e, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float s = d * w;
+    return e + s;
+}
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        f32x4 ee = *(const f32x4*)(ema + i * 4);
+        const f32x4 pp = *(const f32x4*)(p + i * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ee[j] = ema_one(ee[j], pp[j], w);
+        *(f32x4*)(ema + i * 4) = ee;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long e = n4 * 4; e < n; ++e) ema[e] = ema_one(ema[e], p[e], w);
+}
+// exchange the contents of two disjoint flat buffers bit for bit (integer lanes: NaN payloads pass untouched)
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void swap_flat_kernel(unsigned int* __restrict__ a, unsigned int* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const u32x4 x = *(const u32x4*)(a + i * 4);
+        const u32x4 y = *(const u32x4*)(b + i * 4);
+        *(u32x4*)(a + i * 4) = y;
+        *(u32x4*)(b + i * 4) = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long e = n4 * 4; e < n; ++e) {
+            const unsigned int x = a[e];
+            a[e] = b[e];
+            b[e] = x;
+        }
+}
+static inline int flat_grid(size_t n) {
+    size_t grid = (n / 4 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    return (int)grid;
+}
+extern "C" int dg_ema_update_flat(float* ema, const float* p, size_t n, float w, dg_stream_t stream) {
+    DG_CHECK_ARG(ema && p, "dg_ema_update_flat: null pointer");
+    DG_CHECK_ARG((((size_t)ema | (size_t)p) & 15) == 0, "dg_ema_update_flat: pointers must be 16-byte aligned (ema %p, p %p)", (void*)ema,
+                 (const void*)p);
+    DG_CHECK_ARG(w >= 0.f && w <= 1.f, "dg_ema_update_flat: weight %g outside [0, 1]", (double)w);      // (false for NaN)
+    if (n == 0) return DG_OK;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, w);
+    DG_CHECK_LAUNCH("ema_update");
+    return DG_OK;
+}
+extern "C" int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t stream) {
+    DG_CHECK_ARG(a && b, "dg_swap_flat: null pointer");
+    DG_CHECK_ARG((((size_t)a | (size_t)b) & 15) == 0, "dg_swap_flat: pointers must be 16-byte aligned (a %p, b %p)", (void*)a, (void*)b);
+    if (n == 0 || a == b) return DG_OK;
+    const size_t lo = (size_t)a < (size_t)b ? (size_t)a : (size_t)b, hi = (size_t)a < (size_t)b ? (size_t)b : (size_t)a;
+    DG_CHECK_ARG((hi - lo) / sizeof(float) >= n, "dg_swap_flat: the two ranges of %zu floats overlap", n);
+    hipLaunchKernelGGL(swap_flat_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, (unsigned int*)a, (unsigned int*)b, (long)n);
+    DG_CHECK_LAUNCH("swap_flat");
+    return DG_OK;
+}

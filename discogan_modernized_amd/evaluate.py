@@ -101,6 +101,7 @@ def parse_args(argv=None):
     p.add_argument("--paired", action="store_true", help="image i of A and of B show the same thing: also score the translations")
     p.add_argument("--use_extra_layers", action="store_true")
     p.add_argument("--no_fold", action="store_true", help="run the training modules in eval() mode instead of the folded form")
+    p.add_argument("--use_ema", action="store_true", help="score gen_A_ema_final.pth / gen_B_ema_final.pth (a run with --ema_decay)")
     p.add_argument("--output", type=str, default="eval.json")
     return p.parse_args(argv)
 
@@ -114,7 +115,8 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     gens = []
     for direction in ("AtoB", "BtoA"):
-        g, path = inference.load_generator(args.model_path, direction, args.image_size, device, args.use_extra_layers, fold=not args.no_fold)
+        g, path = inference.load_generator(args.model_path, direction, args.image_size, device, args.use_extra_layers, fold=not args.no_fold,
+                                             ema=args.use_ema)
         if g is None:
             raise FileNotFoundError(f"{path} not found")
         gens.append(g)

@@ -24,6 +24,11 @@ Held-out evaluation (evaluate.py): every ``--eval_interval`` iterations (0 = nev
 and MAE of the reconstructions, and of the translations when the split is paired (``--eval_paired``) -- and one line goes to
 ``results/.../eval_log.txt``.  An iteration that also writes a sample grid runs the four passes once for both.
 
+Weight EMA (optim.EMA): ``--ema_decay D`` (0 = off) keeps ``ema = D * ema + (1 - D) * w`` of both generators' weights, updated behind every
+generator step from ``--ema_start_iter`` on; every model save also writes ``gen_A_ema_{tag}.pth`` / ``gen_B_ema_{tag}.pth`` (EMA weights, live
+BatchNorm buffers) for ``inference.py --use_ema`` / ``evaluate.py --use_ema``.  ``--ema_samples`` runs the sample-grid and evaluation passes
+on the EMA weights (``trainer.ema_weights()``); the live weights and running statistics are then left exactly as without those passes.
+
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
 distributed_image_translation.py:203-216,451-452 -- ONE permutation per epoch from a seed shared by all ranks
@@ -35,6 +40,7 @@ shard may be short (no drop_last); a final batch of a single sample is skipped (
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import time
 from datetime import datetime
@@ -84,6 +90,12 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--eval_paired", type=str, default="auto", choices=["auto", "on", "off"],
                    help="image i of test A and of test B show the same thing, so the translations are scored too; auto: the files "
                         "source of edges2shoes / edges2handbags")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of both generators' weights with this decay (e.g. 0.999; 0 = off) and "
+                        "save it as gen_A_ema_*.pth / gen_B_ema_*.pth next to the live checkpoints")
+    p.add_argument("--ema_start_iter", type=int, default=0, help="the first generator step at or after this iteration starts the EMA with a copy")
+    p.add_argument("--ema_samples", action="store_true",
+                   help="sample grids and evaluation events run on the EMA weights once the EMA has started (eval lines end in ' [ema]')")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -214,6 +226,7 @@ def run_dirs(args, rank_suffix=""):
 
 
 def save_models(trainer, model_path, tag, next_iter=None, with_state=False, loader=None):
+    """The four live networks as ``{net}_{tag}.pth``; with the EMA on and started also ``gen_A_ema_{tag}.pth`` / ``gen_B_ema_{tag}.pth``."""
     trainer.finish()                      # join the communication stream before reading parameters
     if with_state and next_iter is not None:
         torch.save(trainer.train_state(next_iter, extra=loader), model_path / f"train_state_{tag}.pth")
@@ -222,6 +235,12 @@ def save_models(trainer, model_path, tag, next_iter=None, with_state=False, load
     for k, net in names.items():
         sd = {n: (t.detach().contiguous().cpu()) for n, t in net.state_dict().items()}
         torch.save(sd, model_path / f"{k}_{tag}.pth")
+    ema = getattr(trainer, "ema", None)
+    if ema is not None and ema.ready:
+        for k, sd in trainer.ema_state_dicts().items():
+            torch.save(sd, model_path / f"{k}_ema_{tag}.pth")
+    elif ema is not None and tag == "final":
+        print("EMA: no generator step ran at or after --ema_start_iter, so no gen_*_ema_final.pth is written", flush=True)
 
 
 def epoch_batches(args, epoch, data_size, rank, world_size, gperm, device):
@@ -322,12 +341,15 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
             if sampling or evaluating:
                 # before the model save of the same iteration (image_translation.py:411-424): the passes move the generators' BatchNorm
                 # running statistics, and a checkpoint written at `iters` carries them; they run once for both events
-                outs = trainer.sample(*split)
+                # --ema_samples: on the EMA weights once there are any; the context puts weights and running statistics back
+                on_ema = bool(getattr(args, "ema_samples", False)) and getattr(trainer, "ema", None) is not None and trainer.ema.ready
+                with (trainer.ema_weights() if on_ema else contextlib.nullcontext()):
+                    outs = trainer.sample(*split)
                 if sampling:
                     samples.save_samples(trainer, split, result_path / "samples", iters, outs=outs)
                 if evaluating:
                     res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs)
-                    msg = evaluate.format_eval(iters, res)
+                    msg = evaluate.format_eval(iters, res) + (" [ema]" if on_ema else "")
                     print(msg, flush=True)
                     with open(result_path / "eval_log.txt", "a") as f:
                         f.write(msg + "\n")

@@ -28,7 +28,7 @@ from . import ops
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="HIP/MI355X implementation of DiscoGAN inference")
     p.add_argument("--device", type=str, default="cuda")
-    p.add_argument("--model_path", type=str, required=True, help="directory with gen_A_final.pth / gen_B_final.pth")
+    p.add_argument("--model_path", type=str, required=True, help="directory with gen_A_final.pth / gen_B_final.pth (--use_ema: gen_*_ema_final.pth)")
     p.add_argument("--input_path", type=str, required=True, help="tensor file (.pt), image file, or directory of images")
     p.add_argument("--output_dir", type=str, default="./inference_results")
     p.add_argument("--image_size", type=int, default=64)
@@ -38,6 +38,8 @@ def parse_args(argv=None):
                    choices=["edges2handbags", "edges2shoes", "handbags2shoes", "celebA", None])
     p.add_argument("--domain", type=str, default=None, choices=["A", "B", None])
     p.add_argument("--no_fold", action="store_true", help="run the training modules in eval() mode instead of the folded form")
+    p.add_argument("--use_ema", action="store_true",
+                   help="load the EMA weights (gen_A_ema_final.pth / gen_B_ema_final.pth of a run with --ema_decay) instead of the last iterate")
     return p.parse_args(argv)
 
 
@@ -93,10 +95,12 @@ class FoldedGenerator:
         return h
 
 
-def load_generator(model_dir, direction, image_size, device, use_extra_layers=False, fold=True, reverse=False):
-    """inference.py:127-136: AtoB uses gen_B_final.pth, BtoA gen_A_final.pth (the naming trap of SURVEY Appendix B)."""
-    fwd = "gen_B_final.pth" if direction == "AtoB" else "gen_A_final.pth"
-    rev = "gen_A_final.pth" if direction == "AtoB" else "gen_B_final.pth"
+def load_generator(model_dir, direction, image_size, device, use_extra_layers=False, fold=True, reverse=False, ema=False):
+    """inference.py:127-136: AtoB uses gen_B_final.pth, BtoA gen_A_final.pth (the naming trap of SURVEY Appendix B).
+    ema=True: the same two networks' EMA weights, gen_B_ema_final.pth / gen_A_ema_final.pth."""
+    tail = "_ema_final.pth" if ema else "_final.pth"
+    fwd = ("gen_B" if direction == "AtoB" else "gen_A") + tail
+    rev = ("gen_A" if direction == "AtoB" else "gen_B") + tail
     path = Path(model_dir) / (rev if reverse else fwd)
     if not path.exists():
         return None, path
@@ -144,13 +148,14 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     out_dir = Path(args.output_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
-    gen, path = load_generator(args.model_path, args.direction, args.image_size, device, args.use_extra_layers, fold=not args.no_fold)
+    gen, path = load_generator(args.model_path, args.direction, args.image_size, device, args.use_extra_layers, fold=not args.no_fold,
+                               ema=args.use_ema)
     if gen is None:
         print(f"model load failed: {path} not found; available:", [p.name for p in Path(args.model_path).glob('*.pth')])
         return None
     print(f"model loaded: {path}")
     rev, _ = load_generator(args.model_path, args.direction, args.image_size, device, args.use_extra_layers, fold=not args.no_fold,
-                            reverse=True)
+                            reverse=True, ema=args.use_ema)
     results = []
     for stem, x in _load_inputs(Path(args.input_path), args.image_size, device):
         with torch.no_grad():

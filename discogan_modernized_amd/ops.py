@@ -1106,6 +1106,26 @@ def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scal
                                                  eps, weight_decay, grad_scale, _stream()), "dg_adam_step_flat")
 
 
+def _flat_pair(a, b, who):
+    _check_dev(a, b)
+    if a.dim() != 1 or b.dim() != 1 or a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who}: two contiguous 1-D fp32 tensors of one length required, got {tuple(a.shape)} and {tuple(b.shape)}")
+
+
+def ema_update_flat(ema, p, w):
+    """ema += (p - ema) * w in place (w = 1 - decay), each operation rounded on its own: p == ema leaves ema bitwise unchanged."""
+    _flat_pair(ema, p, "ema_update_flat")
+    with _hbm("ema", 12.0 * p.numel()):
+        _lib.check(_lib.load().dg_ema_update_flat(_ptr(ema), _ptr(p), p.numel(), float(w), _stream()), "dg_ema_update_flat")
+
+
+def swap_flat(a, b):
+    """Exchange the contents of two flat fp32 buffers bit for bit."""
+    _flat_pair(a, b, "swap_flat")
+    with _hbm("swap", 16.0 * a.numel()):
+        _lib.check(_lib.load().dg_swap_flat(_ptr(a), _ptr(b), a.numel(), _stream()), "dg_swap_flat")
+
+
 # ---- grouped launches (round 4) -------------------------------------------------------------------------------------------
 # The reference issues the passes of an iteration in independent pairs of identical shape -- G_B(A) | G_A(B), G_A(AB) | G_B(BA),
 # D_A(A) | D_B(B), D_A(BA) | D_B(AB) (image_translation.py:342-361) -- and each discriminator sees real and fake images with the same

@@ -41,7 +41,16 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
             "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")
 
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
-                starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan")
+                starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
+                ema_decay=0.0, ema_start_iter=0)
+
+
+def check_ema_decay(decay):
+    """``ema_decay``: 0 = no EMA of the generator weights, else a decay in (0, 1).  Returns it as a float."""
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"ema_decay must be 0 (off) or in (0, 1), got {decay}")
+    return decay
 
 
 def default_args(**over):
@@ -58,6 +67,7 @@ class DiscoGANTrainer:
         for k, v in DEFAULTS.items():
             if not hasattr(self.args, k):
                 setattr(self.args, k, v)
+        ema_decay = check_ema_decay(self.args.ema_decay)
         self.device = torch.device(device)
         self.image_size = image_size
         self.pg = process_group
@@ -90,6 +100,10 @@ class DiscoGANTrainer:
                                     lr=a.learning_rate, betas=(a.beta1, a.beta2), weight_decay=a.weight_decay)
         self.optim_dis = optim.Adam(chain(self.discriminator_A.parameters(), self.discriminator_B.parameters()),
                                     lr=a.learning_rate, betas=(a.beta1, a.beta2), weight_decay=a.weight_decay)
+        # Exponential moving average of both generators' weights (ema_decay > 0; optim.EMA): a second flat buffer, updated by one
+        # launch behind every generator Adam step from iteration ema_start_iter on -- eagerly on the main stream, never captured.
+        # Sampling, evaluation and the gen_*_ema_*.pth checkpoints read it (ema_weights / ema_state_dicts); training never does.
+        self.ema = optim.EMA(self.optim_gen, ema_decay) if ema_decay > 0.0 else None
         self._graphs = {}
         self._static = None
         # The A-side chain (G_A, D_A) runs on a second HIP stream next to the B-side chain (G_B, D_B):
@@ -624,6 +638,7 @@ class DiscoGANTrainer:
                 F_.FINAL_HOOK = None
         if bucketed:
             self._buckets.finish()
+            self._ema_update(iters)                           # (finish() made the main stream wait for every bucket's update)
             return out
         # gradients of the stepped side only: one flat message, summed; the /W rides in the Adam kernel
         if self.overlap_comm and dstep and do_step:
@@ -640,7 +655,14 @@ class DiscoGANTrainer:
         scale = self._exchange(opt, "D" if dstep else "G")
         if do_step:
             opt.step(grad_scale=scale, active=self.active_ranges(dstep))
+            if not dstep:
+                self._ema_update(iters)
         return out
+
+    def _ema_update(self, iters):
+        """Behind a generator Adam step that is ordered before this point on the current (main) stream."""
+        if self.ema is not None and iters >= self.args.ema_start_iter:
+            self.ema.update()
 
     def _train_iteration_graph_overlap(self, A, B, iters, do_step, need_losses):
         """overlap_comm="graph": see __init__.  Results are bitwise those of the plain schedule: the all-reduce and the Adam kernel are
@@ -664,6 +686,7 @@ class DiscoGANTrainer:
             # the backward was not cut (two-chain schedule): the generators' update is needed by the very next kernel -- main stream
             scale = self._exchange(opt, "G")
             opt.step(grad_scale=scale, active=self.active_ranges(dstep))
+            self._ema_update(iters)
             return out
         ev = torch.cuda.Event()
         ev.record(main)
@@ -678,6 +701,7 @@ class DiscoGANTrainer:
                 self._exchange_and_step_ranges(opt, self._gen_ranges()[0], "G")      # the encoders: the exposed part
         if not dstep:
             main.wait_stream(self.comm_stream)                # the next iteration's first kernels read the generators' weights
+            self._ema_update(iters)                           # ... and so does the EMA: decoders' and encoders' slices are both in
         return out
 
     def comm_ms(self):
@@ -721,6 +745,40 @@ class DiscoGANTrainer:
             self.ctx.clear()                   # no bf16 shadow or plane triple of a sampling pass outlives it
         return AB, BA, ABA, BAB
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body with the EMA weights in both generators: ``ema.swap()`` on entry and again on exit (also on an exception), the
+        generators' buffers (BatchNorm running statistics, counters) saved and put back.  Afterwards the live weights, the EMA, every
+        derived operand form and every generator buffer are bit for bit what they were -- a train-mode ``sample()`` inside does not
+        move the live running statistics."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): this trainer keeps no EMA (ema_decay = 0)")
+        if not self.ema.ready:
+            raise RuntimeError("ema_weights(): the EMA holds nothing yet (no generator step at iteration >= ema_start_iter so far)")
+        self.finish()
+        saved = [(b, b.clone()) for net in (self.generator_A, self.generator_B) for b in net.buffers()]
+        self.ema.swap()
+        try:
+            yield self
+        finally:
+            self.ema.swap()
+            with torch.no_grad():
+                for b, old in saved:
+                    b.copy_(old)
+
+    def ema_state_dicts(self):
+        """``dict(gen_A=..., gen_B=...)`` of host tensors in the key order of ``Generator.state_dict()``: parameters from the EMA,
+        buffers from the live generators (running statistics are averages already)."""
+        if self.ema is None or not self.ema.ready:
+            raise RuntimeError("ema_state_dicts(): no EMA weights (ema_decay = 0, or no qualifying generator step yet)")
+        self.finish()
+        out = {}
+        for key, net in (("gen_A", self.generator_A), ("gen_B", self.generator_B)):
+            params = dict(net.named_parameters())
+            out[key] = {n: (self.ema.view_of(params[n]) if n in params else t).detach().contiguous().cpu()
+                        for n, t in net.state_dict().items()}
+        return out
+
     # ---------------------------------------------------------------------------------------------
     def losses_to_floats(self, out):
         vals = torch.stack([getattr(out, k).detach().reshape(()) for k in LOG_KEYS]).cpu().tolist()
@@ -746,6 +804,8 @@ class DiscoGANTrainer:
         st = dict(iters=int(next_iter), nets={k: {n: t.detach().contiguous().cpu() for n, t in v.state_dict().items()}
                                               for k, v in self.nets.items()},
                   optim_gen=self.optim_gen.state_dict(), optim_dis=self.optim_dis.state_dict())
+        if self.ema is not None:
+            st["ema"] = self.ema.state_dict()
         if extra:
             st["loader"] = dict(extra)
         return st
@@ -755,6 +815,11 @@ class DiscoGANTrainer:
             v.load_state_dict(st["nets"][k])
         self.optim_gen.load_state_dict(st["optim_gen"])
         self.optim_dis.load_state_dict(st["optim_dis"])
+        if self.ema is not None:
+            if "ema" in st:
+                self.ema.load_state_dict(st["ema"])
+            else:                                  # a state written without the EMA: the next qualifying G-step starts it with a copy
+                self.ema.ready, self.ema.updates = False, 0
         self._graphs = {}
         start = int(st["iters"])
         # like a fresh run, the first D,G,G cycle after a resume is dispatched eagerly before anything is captured

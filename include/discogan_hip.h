@@ -330,6 +330,11 @@ int dg_adam_advance(double* state, double lr, double beta1, double beta2, dg_str
 int dg_adam_step_flat(float* p, const float* g, float* m, float* v, size_t n, const double* state,
                       float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                       dg_stream_t s);
+/* Exponential moving average of a flat parameter buffer: ema += (p - ema) * w, w = 1 - decay in [0, 1], the three operations
+ * rounded one by one (p == ema leaves ema bitwise unchanged for every w).  dg_swap_flat exchanges the contents of two buffers
+ * bit for bit; a == b is a no-op, ranges that overlap otherwise are refused.  Pointers 16-byte aligned; n == 0 launches nothing. */
+int dg_ema_update_flat(float* ema, const float* p, size_t n, float w, dg_stream_t s);
+int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t s);
 
 /* nn.BCELoss against a target TENSOR (image_translation.py:157-166 materialises ones / zeros label tensors);
  * same -100 log clamp and 1e-12 backward guard as dg_bce_fwd/_bwd.  p, target: [n]. */
