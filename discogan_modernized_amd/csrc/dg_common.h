@@ -34,22 +34,15 @@ static inline bool dg_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline size_t dg_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int dg_get_option(int idx);
-// Arithmetic of the conv products for the CURRENT call (DG_PREC_*): the `prec` argument of the *_g / *_p entry points -- held in a
-// thread-local for the duration of that call (DgPrecScope) so that planning helpers and the edge kernels' launchers see it -- else the
-// process default dg_set_option("bf16", n), which only the entry points WITHOUT the argument fall back to.
+// Arithmetic of the conv products (DG_PREC_*) for the launchers of the 3-channel edge kernels (edge.hip, and their entry points at the
+// end of igemm.hip): the `prec` argument of a *_g / *_p entry point there, held in a thread-local for the duration of that call
+// (DgPrecScope); without a scope, the process default dg_set_option("bf16", n).  The interior convs (igemm.hip's planner and launch path)
+// do not read it: they take the arithmetic as an argument.
 int dg_cur_prec();
 struct DgPrecScope {
     int old;
     explicit DgPrecScope(int prec);
     ~DgPrecScope();
-};
-// Problems the split-K plan of the CURRENT call is sized for (plan_groups of the *_g conv entry points): 1 = every problem planned as if
-// launched alone (bitwise the one-problem result), g = the whole grouped launch fills the chip, so fewer K-splits per problem.
-int dg_cur_plan_groups();
-struct DgPlanScope {
-    int old;
-    explicit DgPlanScope(int plan_groups);
-    ~DgPlanScope();
 };
 enum { DG_OPT_SPLITK = 0, DG_OPT_KT = 1, DG_OPT_TARGET_WGS = 2, DG_OPT_RESERVED = 3, DG_OPT_SPLIT_BELOW = 4, DG_OPT_POINTER_PATH = 5, DG_OPT_BF16 = 6, DG_OPT_DBG_ZERO = 7, DG_OPT_NO_DMA = 8, DG_OPT_DMA_MFMA = 9, DG_OPT_X3_MFMA = 10, DG_OPT_DGW_PERSIST = 11, DG_OPT_UNDERSTORY = 12, DG_OPT_BN_ITEMS = 13, DG_OPT_COUNT = 14 };
 

@@ -1186,14 +1186,20 @@ static int check_channels(const char* who, int op, const ConvGeom& g) {
     if (op == 1 && g.stride == 2) DG_CHECK_ARG(g.K % 32 == 0, "%s: K=%d must be a multiple of 32", who, g.K);
     return DG_OK;
 }
-// Planning queries: is there a plan to ask about?  Not for an op outside 0..2, a geometry or channel count the launch entry points refuse,
-// or the K == 1 head (plain reductions: no workspace, no split, no statistics).  The queries then answer "nothing": 0 bytes / rows / not ok,
-// 1 split -- never a plan for a shape that cannot be launched (make_plan's K-tile counts assume the channel rules).
-static bool query_has_plan(const char* who, int op, int N, int H, int W, int C, int K, int stride, int pad, ConvGeom* g) {
-    if (op < 0 || op > 2) { dg_fail(DG_ERR_INVALID, "%s: op=%d (0 forward, 1 input gradient, 2 weight gradient)", who, op); return false; }
-    if (check_geom(who, N, H, W, C, K, stride, pad, g) != DG_OK || K == 1) return false;
-    return check_channels(who, op, *g) == DG_OK;
-}
+// DG_PREC_DEFAULT -> the process default (option "bf16").  Resolved once, where a call enters the library: below that the arithmetic is
+// an argument.
+static int resolve_prec(int prec) { return prec >= 0 ? prec : dg_get_option(DG_OPT_BF16); }
+
+// Everything a plan depends on, the named tuning options that make_plan reads (dg_get_option) aside.
+struct PlanReq {
+    int op;             // 0 forward, 1 input gradient, 2 weight gradient
+    ConvGeom g;
+    int prec;           // DG_PREC_F32 | DG_PREC_BF16 | DG_PREC_F32X3 (resolved: never DG_PREC_DEFAULT)
+    int plan_groups;    // problems the split-K plan is sized for: 1 = every problem planned as if launched alone (bitwise the one-problem
+                        // result), g = the whole grouped launch fills the chip, so fewer K-splits per problem
+    int a16, b16;       // operand forms: 0 fp32 tensor, 1 bf16 tensor (only honoured on the bf16 tile path), 3 three bf16 planes
+    int allow_fww;      // 0: not the window forward kernel (it reads TRANSPOSED weight planes; experiments library only)
+};
 
 struct Plan {
     int mode, wm, wn, kt;
@@ -1243,8 +1249,9 @@ static int choose_splits(int base_wgs, int nIt, int dflt_target = 0) {
     return s;
 }
 
-// op: 0 fwd, 1 dgrad, 2 wgrad;  a16 / b16: that operand is a bf16 tensor (only honoured on the bf16 tile path)
-static void make_plan(int op, const ConvGeom& g, Plan* pl, int a16 = 0, int b16 = 0, int allow_fww = 1) {
+static void make_plan(const PlanReq& rq, Plan* pl) {
+    const int op = rq.op, a16 = rq.a16, b16 = rq.b16;
+    const ConvGeom& g = rq.g;
     IgemmArgs& a = pl->a;
     a = IgemmArgs();
     a.N = g.N; a.H = g.H; a.W = g.W; a.Cc = g.C; a.K = g.K;
@@ -1258,9 +1265,8 @@ static void make_plan(int op, const ConvGeom& g, Plan* pl, int a16 = 0, int b16 
     pl->wm = 2; pl->wn = 2; pl->kt = (kt_opt == 16 || (kt_opt == 0 && op == 2)) ? 16 : 32;
     // bf16 MFMA operands (option "bf16"): bf16 LDS tiles, K-tile 64 (32 with the 256x64 tile, whose LDS would
     // otherwise allow one workgroup per CU only); needs the buffer-descriptor kernels and whole K-tiles per tap
-    const int popt = dg_cur_prec();      // this call's arithmetic: 0 exact fp32 MFMA, 1 bf16 operands, 2 fp32 as three bf16 planes
-    bool want_bf16 = popt == 1;
-    const bool want_x3 = popt == 2;
+    bool want_bf16 = rq.prec == DG_PREC_BF16;       // this call's arithmetic: else exact fp32 MFMA, or fp32 as three bf16 planes
+    const bool want_x3 = rq.prec == DG_PREC_F32X3;
     if (want_bf16 && op == 0 && g.C % 64 != 0) want_bf16 = false;
     if (want_bf16 && op == 1 && g.stride == 2 && g.K % 64 != 0) want_bf16 = false;
     if (want_bf16) pl->kt = 64;
@@ -1343,7 +1349,7 @@ static void make_plan(int op, const ConvGeom& g, Plan* pl, int a16 = 0, int b16 
         // forward with <= 128 output channels: the input window of one (chunk, parity class) in LDS, re-used by the class's four taps
         // (igemm_dma_x3_fww.hip); whole output rows per 256-pixel tile, transposed weight planes; no split-K
 #ifdef DG_EXPERIMENTS      // the window forward kernel: not faster than the register-staged tiles, experiments library only
-        else if (allow_fww && pl->mode == MODE_FWD && g.stride == 2 && g.pad == 1 && g.K <= 128 && g.K % 8 == 0 && g.C % 16 == 0 && g.Wo >= 32 &&
+        else if (rq.allow_fww && pl->mode == MODE_FWD && g.stride == 2 && g.pad == 1 && g.K <= 128 && g.K % 8 == 0 && g.C % 16 == 0 && g.Wo >= 32 &&
                  g.Wo <= 128 && (g.Ho * g.Wo) % 256 == 0 && dg_get_option(DG_OPT_DMA_MFMA) != 1) {
             pl->dma = 5;
             pl->ncls = 4;
@@ -1356,7 +1362,7 @@ static void make_plan(int op, const ConvGeom& g, Plan* pl, int a16 = 0, int b16 
     a.tilesN = (a.Ng + BN - 1) / BN;
     // workgroups of the launch before any K split; a grouped launch planned as a whole (plan_groups of the *_g entry points) counts all
     // its problems: the chip is filled by the group, each problem needs fewer splits (fewer slabs written and re-read)
-    const int base = a.tilesM * a.tilesN * (pl->dma >= 3 ? 4 / pl->ncls : zmul) * (pl->dma ? 1 : dg_cur_plan_groups());
+    const int base = a.tilesM * a.tilesN * (pl->dma >= 3 ? 4 / pl->ncls : zmul) * (pl->dma ? 1 : rq.plan_groups);
     a.splits = pl->dma == 5 ? 1 : choose_splits(base, a.nIt, pl->dma == 2 && pl->wm * pl->wn == 4 ? 512 : (pl->dma ? 256 : 0));
     a.itPerSplit = (a.nIt + a.splits - 1) / a.splits;
     a.splits = (a.nIt + a.itPerSplit - 1) / a.itPerSplit;  // no empty split
@@ -1419,16 +1425,12 @@ extern "C" int dg_debug_igemm_stamps(void* buf, size_t bytes) {
     return DG_OK;
 }
 
-static int run_plan(const char* who, Plan& pl, void* ws, size_t ws_bytes, hipStream_t st) {
+// launch the kernels of a plan whose arguments are filled in (a split plan: a.part included)
+static int run_plan(const char* who, Plan& pl, hipStream_t st) {
     IgemmArgs& a = pl.a;
     {
         const size_t grid = (size_t)a.tilesM * a.tilesN * (pl.mode == MODE_DGRAD_S2 ? 4 : 1) * a.splits;
         a.stamps = (g_stamp_buf != nullptr && g_stamp_cap >= grid * 64) ? g_stamp_buf : nullptr;
-    }
-    if (a.splits > 1) {
-        if (ws == nullptr || ws_bytes < pl.ws_bytes)
-            return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, pl.ws_bytes);
-        a.part = (float*)ws;
     }
     const int zmul = pl.mode == MODE_DGRAD_S2 ? 4 : 1;
     const int ngrp = a.groups > 1 ? a.groups : 1;
@@ -1496,29 +1498,131 @@ static int run_plan(const char* who, Plan& pl, void* ws, size_t ws_bytes, hipStr
     return DG_OK;
 }
 
-extern "C" size_t dg_conv_workspace_bytes(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (!query_has_plan("dg_conv_workspace_bytes", op, N, H, W, C, K, stride, pad, &g)) return 0;
+// ---- planning queries ----------------------------------------------------------------------------------------------------
+// Is there a plan to ask about?  Not for an op outside 0..2, a geometry or channel count the launch entry points refuse, or the K == 1
+// head (plain reductions: no workspace, no split, no statistics).  The queries then answer "nothing": 0 bytes / rows / not ok, 1 split
+// -- never a plan for a shape that cannot be launched (make_plan's K-tile counts assume the channel rules).  Else *pl is the plan of the
+// request (and *keep the request, for a caller that plans further operand forms of it).
+static bool query_plan(const char* who, int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups, int a16, int b16,
+                       Plan* pl, PlanReq* keep = nullptr) {
+    if (op < 0 || op > 2) { dg_fail(DG_ERR_INVALID, "%s: op=%d (0 forward, 1 input gradient, 2 weight gradient)", who, op); return false; }
+    PlanReq rq = {op, ConvGeom(), resolve_prec(prec), plan_groups >= 1 ? plan_groups : 1, a16, b16, 1};
+    if (check_geom(who, N, H, W, C, K, stride, pad, &rq.g) != DG_OK || K == 1 || check_channels(who, op, rq.g) != DG_OK) return false;
+    make_plan(rq, pl);
+    if (keep) *keep = rq;
+    return true;
+}
+// the forms without a precision argument read the process default
+extern "C" size_t dg_conv_workspace_bytes_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups) {
     Plan pl;
-    make_plan(op, g, &pl);
+    PlanReq rq;
+    if (!query_plan("dg_conv_workspace_bytes_p", op, N, H, W, C, K, stride, pad, prec, plan_groups, 0, 0, &pl, &rq)) return 0;
     size_t ws = pl.ws_bytes;
-    if (dg_cur_prec() == 1) {      // the bf16-operand forms (dg_conv_*_mixed) may plan a different tile / split
-        for (int v = 1; v < 4; ++v) {
-            make_plan(op, g, &pl, v & 1, v >> 1);
-            if (pl.ws_bytes > ws) ws = pl.ws_bytes;
-        }
-    }
-    if (dg_cur_prec() == 2) {      // the plane-operand forms (dg_conv_*_x3)
-        make_plan(op, g, &pl, 3, 3);
+    // the largest over the operand forms this arithmetic can be called with: the bf16-operand forms (dg_conv_*_mixed) and the
+    // plane-operand forms (dg_conv_*_x3) may plan a different tile / split
+    for (int v = 1; v < (rq.prec == DG_PREC_BF16 ? 4 : (rq.prec == DG_PREC_F32X3 ? 2 : 1)); ++v) {
+        rq.a16 = rq.prec == DG_PREC_BF16 ? (v & 1) : 3;
+        rq.b16 = rq.prec == DG_PREC_BF16 ? (v >> 1) : 3;
+        make_plan(rq, &pl);
         if (pl.ws_bytes > ws) ws = pl.ws_bytes;
     }
     return ws;
 }
+extern "C" size_t dg_conv_workspace_bytes(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    return dg_conv_workspace_bytes_p(op, N, H, W, C, K, stride, pad, DG_PREC_DEFAULT, 1);
+}
+extern "C" int dg_conv_plan_splits_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups) {
+    Plan pl;
+    return query_plan("dg_conv_plan_splits_p", op, N, H, W, C, K, stride, pad, prec, plan_groups, 0, 0, &pl) ? pl.a.splits : 1;
+}
+extern "C" int dg_conv_plan_splits(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    return dg_conv_plan_splits_p(op, N, H, W, C, K, stride, pad, DG_PREC_DEFAULT, 1);
+}
+// partial-statistics rows of the fused BatchNorm statistics (0: none): the fp32-tensor forms, ...
+extern "C" int dg_conv_bnstats_rows_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec) {
+    Plan pl;
+    return (op != 2 && stride == 2 && query_plan("dg_conv_bnstats_rows_p", op, N, H, W, C, K, stride, pad, prec, 1, 0, 0, &pl)) ? pl.stat_rows : 0;
+}
+extern "C" int dg_conv_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    return dg_conv_bnstats_rows_p(op, N, H, W, C, K, stride, pad, DG_PREC_DEFAULT);
+}
+// ... the bf16-operand forms, ...
+extern "C" int dg_conv_mixed_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad, int a_bf16, int b_bf16) {
+    Plan pl;
+    return (op != 2 && stride == 2 && query_plan("dg_conv_mixed_bnstats_rows", op, N, H, W, C, K, stride, pad, DG_PREC_BF16, 1, a_bf16, b_bf16, &pl))
+               ? pl.stat_rows : 0;
+}
+// ... and the plane kernel of (op, shape) (0 also: no plane kernel, or one without the epilogue)
+extern "C" int dg_conv_x3_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    Plan pl;
+    return (op != 2 && query_plan("dg_conv_x3_bnstats_rows", op, N, H, W, C, K, stride, pad, DG_PREC_F32X3, 1, 3, 3, &pl) && (pl.dma == 2 || pl.dma == 3))
+               ? pl.stat_rows : 0;
+}
+// can this (op, shape) take bf16 operands at all?  (host planning aid: 0 = no, 1 = the register-staged bf16 tile kernel,
+// 2 = with BOTH operands bf16 the LDS-DMA kernel of igemm_dma.hip runs)
+extern "C" int dg_conv_bf16_operands_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    Plan pl;
+    if (!query_plan("dg_conv_bf16_operands_ok", op, N, H, W, C, K, stride, pad, DG_PREC_BF16, 1, 1, 1, &pl)) return 0;
+    return pl.a.prec == 1 ? (pl.dma ? 2 : 1) : 0;
+}
+// forward, stride 2, no LDS-DMA plane kernel for the shape (fewer than 192 output channels or rows): the register-staged 128 x 128
+// tiles can read plane triples (16-byte granules of 8 bf16: C % 8 == 0; buffer-descriptor kernels only)
+static bool x3_register_staged_planes_ok(int op, const Plan& pl) {
+#ifndef DG_EXPERIMENTS
+    return false;           // (the plane-reading register-staged tiles exist in the experiments library only)
+#endif
+    return op == 0 && pl.a.stride == 2 && pl.a.prec == 2 && pl.mode == MODE_FWD && pl.wm == 2 && pl.wn == 2 && pl.kt == 16 && pl.a.Cc % 16 == 0 &&
+           pl.a.abytes != 0 && pl.a.bbytes != 0;
+}
+// does this (op, shape) have a plane kernel under option bf16 = 2?  (host planning aid)  0: no; 1: yes; 3: yes -- the window
+// FORWARD kernel with the transposed weight planes (w_transposed = 1 of dg_conv_fwd_x3), the register-staged plane reader with the
+// plain ones; 4: yes -- the register-staged tiles read the (plain) planes; 2: yes, and it is the window input-grad kernel, which
+// wants its gradient operand in the quad-chunk layout (plane_layout 1 of dg_bn_act_*_x3)
+extern "C" int dg_conv_x3_planes_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
+    Plan pl;
+    if (!query_plan("dg_conv_x3_planes_ok", op, N, H, W, C, K, stride, pad, DG_PREC_F32X3, 1, 3, 3, &pl)) return 0;
+    if (pl.dma == 0 && x3_register_staged_planes_ok(op, pl)) return 4;
+    return pl.dma == 5 ? 3 : (pl.dma == 3 ? (K % 64 == 0 ? 2 : 1) : (pl.dma == 2 ? 1 : 0));
+}
 
-// ---- the three fp32-tensor ops, grouped form -------------------------------------------------------------------------------
-// `groups` problems of identical geometry go out as ONE launch per kernel of the plan (blockIdx.z = problem); a_in / b_in / out / ws /
+// ---- one conv call ---------------------------------------------------------------------------------------------------------
+// Every conv entry point below describes its call in a ConvCall; conv_launch validates, plans and launches it.
+// `groups` problems of identical geometry go out as ONE launch per kernel of the plan (blockIdx.z = problem); a / b / out / ws /
 // stat hold one pointer per problem.  share (op 2 only): `share` consecutive problems accumulate into the same dw (out[z*share + j]
 // all equal): one main launch over all problems, the split-K reduction adds their slab sums in problem order.
+struct ConvCall {
+    const char* who;                         // the entry point's public name, for messages
+    int op, groups, share;                   // op: 0 forward, 1 input gradient, 2 weight gradient
+    const void *const *a, *const *b;         // per problem: operand A (x of the forward, else dy) and B (w; x of the weight gradient),
+    void* const* out;                        // the output
+    int a16, b16, out16;                     // their forms: 0 fp32 tensor, 1 bf16 tensor, 3 (operands only) three bf16 planes
+    int N, H, W, C, K, stride, pad;
+    int prec, plan_groups;                   // as in PlanReq
+    bool has_head;                           // the form takes the K == 1 head (plain reductions: no plan)
+    long a_plane, b_plane;                   // plane operands: bytes from one plane to the next,
+    int a_layout, b_transposed;              // A in the quad-chunk layout, B the transposed copy of the weight planes
+    const float* bias;                       // folded BatchNorm (inference): bias per output channel (nullptr: none), then act
+    int act, accumulate;
+    float slope;
+    float* const* stat;                      // per problem: fused BatchNorm partial statistics of the output (nullptr: off)
+    void* const* ws;                         // and the split-K workspace
+    size_t stat_floats, ws_bytes;
+    hipStream_t st;
+    // rules that this form alone has: on its arguments (applied in front of the shared channel rules) and on its plan
+    int (*arg_rules)(const ConvCall&);
+    int (*plan_rules)(const ConvCall&, const Plan&);
+};
+// one problem, fp32 tensors, the process-default arithmetic, every extra off: an entry point overwrites what it differs in
+static ConvCall conv_call(const char* who, int op, const void* const* a, const void* const* b, void* const* out, int N, int H, int W, int C, int K,
+                          int stride, int pad, void* const* ws, size_t ws_bytes, dg_stream_t stream) {
+    ConvCall c = ConvCall();
+    c.who = who; c.op = op; c.a = a; c.b = b; c.out = out;
+    c.N = N; c.H = H; c.W = W; c.C = C; c.K = K; c.stride = stride; c.pad = pad;
+    c.groups = c.share = c.plan_groups = 1; c.prec = resolve_prec(DG_PREC_DEFAULT); c.has_head = true;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    return c;
+}
+
 static int head1_g(int op, int groups, int share, const void* const* a_in, int a16, const void* const* b_in, int b16, void* const* out, int out16,
                    int N, int C, int accumulate, hipStream_t st, const char* who) {
     const int J = 16 * C;
@@ -1552,401 +1656,292 @@ static int head1_g(int op, int groups, int share, const void* const* a_in, int a
     return DG_OK;
 }
 
-// fill the group fields of a plan's arguments from per-problem pointer arrays (problem 0's pointers are already set)
-static void set_group_deltas(IgemmArgs& a, int groups, const void* const* A, const void* const* B, void* const* C) {
-    a.groups = groups;
-    for (int g = 1; g < groups; ++g) {
-        a.gdA[g - 1] = (const char*)A[g] - (const char*)A[0];
-        a.gdB[g - 1] = (const char*)B[g] - (const char*)B[0];
-        a.gdC[g - 1] = (const char*)C[g] - (const char*)C[0];
+// fill the plan's arguments from the call, check the statistics buffers and the workspaces it needs, launch
+static int conv_issue(const ConvCall& c, Plan pl) {
+    const char* who = c.who;
+    IgemmArgs& a = pl.a;
+    a.A = (const float*)c.a[0]; a.B = (const float*)c.b[0]; a.C = (float*)c.out[0];
+    a.groups = c.groups; a.share = c.share > 1 ? c.share : 1;
+    for (int i = 1; i < c.groups; ++i) {        // problem i's tensors: byte distances from problem 0's
+        a.gdA[i - 1] = (const char*)c.a[i] - (const char*)c.a[0];
+        a.gdB[i - 1] = (const char*)c.b[i] - (const char*)c.b[0];
+        a.gdC[i - 1] = (const char*)c.out[i] - (const char*)c.out[0];
     }
+    a.accumulate = c.accumulate; a.out16 = c.out16;
+    a.a_plane = c.a_plane; a.b_plane = c.b_plane; a.a_cm = c.a_layout; a.b_transposed = c.b_transposed ? 1 : 0;
+    a.bias = c.bias; a.act = c.act; a.slope = c.slope; a.bias_mod = (pl.mode == MODE_DGRAD_PLAIN) ? c.C : a.Ng;
+    if (c.stat != nullptr) {
+        const int ncols = c.op == 0 ? c.K : c.C;
+        DG_CHECK_ARG(c.op != 2 && pl.stat_rows > 0 && c.stat_floats >= (size_t)pl.stat_rows * (3 * ncols + 4),
+                     "%s: statistics buffer too small or no fused statistics for this plan (ask this form's *_bnstats_rows query)", who);
+        for (int i = 0; i < c.groups; ++i) DG_CHECK_ARG(c.stat[i], "%s: null statistics pointer (problem %d)", who, i);
+        a.stat = c.stat[0]; a.stat_rs = 3 * ncols + 4;
+        for (int i = 1; i < c.groups; ++i) a.gdStat[i - 1] = (const char*)c.stat[i] - (const char*)c.stat[0];
+    }
+    if (a.splits > 1) {
+        DG_CHECK_ARG(c.ws != nullptr, "%s: this plan splits K and needs a workspace per problem", who);
+        for (int i = 0; i < c.groups; ++i)
+            if (c.ws[i] == nullptr || c.ws_bytes < pl.ws_bytes)
+                return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < required %zu (problem %d)", who, c.ws_bytes, pl.ws_bytes, i);
+        a.part = (float*)c.ws[0];
+        for (int i = 1; i < c.groups; ++i) a.gdPart[i - 1] = (const char*)c.ws[i] - (const char*)c.ws[0];
+    }
+    return run_plan(who, pl, c.st);
 }
 
-static int conv_g(int op, int groups, int share, const float* const* a_in, const float* const* b_in, float* const* out, int N, int H, int W, int C,
-                  int K, int stride, int pad, int prec, int plan_groups, int accumulate, float* const* stat, size_t stat_floats, void* const* ws,
-                  size_t ws_bytes, hipStream_t st, const char* who) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS, "%s: groups=%d (1..%d)", who, groups, DG_MAX_GROUPS);
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "%s: prec=%d (DG_PREC_F32 | DG_PREC_BF16 | DG_PREC_F32X3)", who, prec);
-    DG_CHECK_ARG(share <= 1 || (op == 2 && groups % share == 0), "%s: share=%d needs the weight gradient and groups %% share == 0", who, share);
+// THE launch path: geometry, null checks, the K == 1 head, the form's and the shared channel rules, the plan, the form's rules on it,
+// then conv_issue
+static int conv_launch(const ConvCall& c) {
+    const char* who = c.who;
     ConvGeom g;
-    int rc = check_geom(who, N, H, W, C, K, stride, pad, &g);
-    if (rc) return rc;
-    DG_CHECK_ARG(a_in && b_in && out, "%s: null pointer table", who);
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(a_in[i] && b_in[i] && out[i], "%s: null pointer (problem %d)", who, i);
-    if (share > 1)
-        for (int i = 0; i < groups; ++i) DG_CHECK_ARG(out[i] == out[i / share * share], "%s: problems of one share set must name the same dw", who);
-    if (plan_groups < 0) plan_groups = -plan_groups;          // internal: a member launch of a share set keeps its parent's plan
-    else DG_CHECK_ARG(plan_groups == 1 || plan_groups == groups, "%s: plan_groups=%d (1 or groups=%d)", who, plan_groups, groups);
-    DgPrecScope scope(prec);
-    DgPlanScope pscope(plan_groups);
-    if (K == 1) {
-        DG_CHECK_ARG(stride == 1, "%s: K==1 only for the 4x4 head", who);
-        return head1_g(op, groups, share, (const void* const*)a_in, 0, (const void* const*)b_in, 0, (void* const*)out, 0, N, C, accumulate, st, who);
+    int rc;
+    if ((rc = check_geom(who, c.N, c.H, c.W, c.C, c.K, c.stride, c.pad, &g)) != DG_OK) return rc;
+    DG_CHECK_ARG(c.a && c.b && c.out, "%s: null pointer table", who);
+    for (int i = 0; i < c.groups; ++i) DG_CHECK_ARG(c.a[i] && c.b[i] && c.out[i], "%s: null pointer (problem %d)", who, i);
+    if (c.share > 1)
+        for (int i = 0; i < c.groups; ++i)
+            DG_CHECK_ARG(c.out[i] == c.out[i / c.share * c.share], "%s: problems of one share set must name the same dw", who);
+    DG_CHECK_ARG(c.plan_groups == 1 || c.plan_groups == c.groups, "%s: plan_groups=%d (1 or groups=%d)", who, c.plan_groups, c.groups);
+    if (c.K == 1) {
+        DG_CHECK_ARG(c.has_head, "%s: the K == 1 head has no such form", who);
+        DG_CHECK_ARG(c.stride == 1, "%s: K==1 only for the 4x4 head", who);
+        return head1_g(c.op, c.groups, c.share, c.a, c.a16, c.b, c.b16, c.out, c.out16, c.N, c.C, c.accumulate, c.st, who);
     }
-    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
+    if (c.arg_rules && (rc = c.arg_rules(c)) != DG_OK) return rc;
+    if ((rc = check_channels(who, c.op, g)) != DG_OK) return rc;
+    // (plain weight planes: the register-staged tiles read them where the window forward kernel, which takes transposed ones, would apply)
+    const PlanReq rq = {c.op, g, c.prec, c.plan_groups, c.a16, c.b16, (c.op == 0 && !c.b_transposed) ? 0 : 1};
     Plan pl;
-    make_plan(op, g, &pl);
-    IgemmArgs& a = pl.a;
-    if (share > 1 && a.splits <= 1) {
-        // no reduction kernel to merge the shared outputs in: member j of every share set per launch, in order
-        const int nout = groups / share;
-        for (int j = 0; j < share; ++j) {
-            const float *aa[DG_MAX_GROUPS], *bb[DG_MAX_GROUPS];
-            float* oo[DG_MAX_GROUPS];
-            for (int z = 0; z < nout; ++z) { aa[z] = a_in[z * share + j]; bb[z] = b_in[z * share + j]; oo[z] = out[z * share + j]; }
-            void* wj[DG_MAX_GROUPS];
-            for (int z = 0; z < nout; ++z) wj[z] = ws ? ws[z * share + j] : nullptr;
-            // (plan_groups handed on unchanged: the same unsplit plan for every member launch)
-            rc = conv_g(op, nout, 1, aa, bb, oo, N, H, W, C, K, stride, pad, prec, -plan_groups, (accumulate || j > 0) ? 1 : 0, nullptr, 0, wj, ws_bytes, st, who);
-            if (rc) return rc;
+    make_plan(rq, &pl);
+    if (c.plan_rules && (rc = c.plan_rules(c, pl)) != DG_OK) return rc;
+    if (c.share > 1 && pl.a.splits <= 1) {
+        // no reduction kernel to merge the shared outputs in: member j of every share set per launch, in order, all with this plan
+        const int nout = c.groups / c.share;
+        for (int j = 0; j < c.share; ++j) {
+            const void *aa[DG_MAX_GROUPS], *bb[DG_MAX_GROUPS];
+            void* oo[DG_MAX_GROUPS];
+            for (int z = 0; z < nout; ++z) { aa[z] = c.a[z * c.share + j]; bb[z] = c.b[z * c.share + j]; oo[z] = c.out[z * c.share + j]; }
+            ConvCall m = c;
+            m.groups = nout; m.share = 1; m.a = aa; m.b = bb; m.out = oo;
+            m.accumulate = (c.accumulate || j > 0) ? 1 : 0; m.stat = nullptr;
+            if ((rc = conv_issue(m, pl)) != DG_OK) return rc;
         }
         return DG_OK;
     }
-    a.A = a_in[0]; a.B = b_in[0]; a.C = out[0]; a.accumulate = accumulate;
-    set_group_deltas(a, groups, (const void* const*)a_in, (const void* const*)b_in, (void* const*)out);
-    a.share = share > 1 ? share : 1;
-    if (stat != nullptr) {
-        const int ncols = op == 0 ? K : C;
-        DG_CHECK_ARG(op != 2 && pl.stat_rows > 0 && stat_floats >= (size_t)pl.stat_rows * (3 * ncols + 4),
-                     "%s: statistics buffer too small or no fused statistics for this plan (ask dg_conv_bnstats_rows_p)", who);
-        for (int i = 0; i < groups; ++i) DG_CHECK_ARG(stat[i], "%s: null statistics pointer (problem %d)", who, i);
-        a.stat = stat[0];
-        a.stat_rs = 3 * ncols + 4;
-        for (int i = 1; i < groups; ++i) a.gdStat[i - 1] = (const char*)stat[i] - (const char*)stat[0];
-    }
-    void* ws0 = nullptr;
-    if (a.splits > 1) {
-        DG_CHECK_ARG(ws != nullptr, "%s: this plan splits K and needs a workspace per problem", who);
-        for (int i = 0; i < groups; ++i)
-            if (ws[i] == nullptr || ws_bytes < pl.ws_bytes) return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < required %zu (problem %d)", who, ws_bytes, pl.ws_bytes, i);
-        ws0 = ws[0];
-        for (int i = 1; i < groups; ++i) a.gdPart[i - 1] = (const char*)ws[i] - (const char*)ws[0];
-    }
-    return run_plan(who, pl, ws0, ws_bytes, st);
+    return conv_issue(c, pl);
 }
 
+// ---- the three fp32-tensor ops: grouped form, and the one-problem forms without a precision argument (the process default) ----
+static int conv_g(const char* who, int op, int groups, int share, const float* const* a_in, const float* const* b_in, float* const* out, int N, int H,
+                  int W, int C, int K, int stride, int pad, int prec, int plan_groups, int accumulate, float* const* stat, size_t stat_floats,
+                  void* const* ws, size_t ws_bytes, dg_stream_t stream) {
+    // (in front of everything else: the tables are read up to `groups`)
+    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS, "%s: groups=%d (1..%d)", who, groups, DG_MAX_GROUPS);
+    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "%s: prec=%d (DG_PREC_F32 | DG_PREC_BF16 | DG_PREC_F32X3)", who, prec);
+    DG_CHECK_ARG(share <= 1 || (op == 2 && groups % share == 0), "%s: share=%d needs the weight gradient and groups %% share == 0", who, share);
+    ConvCall c = conv_call(who, op, (const void* const*)a_in, (const void* const*)b_in, (void* const*)out, N, H, W, C, K, stride, pad, ws, ws_bytes,
+                           stream);
+    c.groups = groups; c.share = share; c.prec = resolve_prec(prec); c.plan_groups = plan_groups;
+    c.accumulate = accumulate; c.stat = stat; c.stat_floats = stat_floats;
+    return conv_launch(c);
+}
 extern "C" int dg_conv_fwd_g(int groups, const float* const* x, const float* const* w, float* const* y, int N, int H, int W, int C, int K, int stride,
                              int pad, int prec, int plan_groups, float* const* stat, size_t stat_floats, void* const* ws, size_t ws_bytes,
                              dg_stream_t stream) {
-    return conv_g(0, groups, 1, x, w, y, N, H, W, C, K, stride, pad, prec, plan_groups, 0, stat, stat_floats, ws, ws_bytes, (hipStream_t)stream, "dg_conv_fwd_g");
+    return conv_g("dg_conv_fwd_g", 0, groups, 1, x, w, y, N, H, W, C, K, stride, pad, prec, plan_groups, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad_g(int groups, const float* const* dy, const float* const* w, float* const* dx, int N, int H, int W, int C, int K, int stride,
                                int pad, int prec, int plan_groups, float* const* stat, size_t stat_floats, void* const* ws, size_t ws_bytes,
                                dg_stream_t stream) {
-    return conv_g(1, groups, 1, dy, w, dx, N, H, W, C, K, stride, pad, prec, plan_groups, 0, stat, stat_floats, ws, ws_bytes, (hipStream_t)stream, "dg_conv_dgrad_g");
+    return conv_g("dg_conv_dgrad_g", 1, groups, 1, dy, w, dx, N, H, W, C, K, stride, pad, prec, plan_groups, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_wgrad_g(int groups, int share, const float* const* dy, const float* const* x, float* const* dw, int N, int H, int W, int C, int K,
                                int stride, int pad, int prec, int plan_groups, int accumulate, void* const* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g(2, groups, share, dy, x, dw, N, H, W, C, K, stride, pad, prec, plan_groups, accumulate, nullptr, 0, ws, ws_bytes, (hipStream_t)stream, "dg_conv_wgrad_g");
+    return conv_g("dg_conv_wgrad_g", 2, groups, share, dy, x, dw, N, H, W, C, K, stride, pad, prec, plan_groups, accumulate, nullptr, 0, ws, ws_bytes, stream);
 }
-// planning queries with the arithmetic as an argument (the forms without it read the process default)
-extern "C" size_t dg_conv_workspace_bytes_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups) {
-    DgPrecScope scope(prec);
-    DgPlanScope pscope(plan_groups);
-    return dg_conv_workspace_bytes(op, N, H, W, C, K, stride, pad);
-}
-extern "C" int dg_conv_bnstats_rows_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec) {
-    DgPrecScope scope(prec);
-    return dg_conv_bnstats_rows(op, N, H, W, C, K, stride, pad);
-}
-extern "C" int dg_conv_plan_splits_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups) {
-    DgPrecScope scope(prec);
-    DgPlanScope pscope(plan_groups);
-    return dg_conv_plan_splits(op, N, H, W, C, K, stride, pad);
-}
-
-// the one-problem forms without a precision argument: the process default arithmetic (dg_set_option("bf16"))
 extern "C" int dg_conv_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K,
                            int stride, int pad, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g(0, 1, 1, &x, &w, &y, N, H, W, C, K, stride, pad, dg_cur_prec(), 1, 0, nullptr, 0, &ws, ws_bytes, (hipStream_t)stream, "dg_conv_fwd");
+    return conv_g("dg_conv_fwd", 0, 1, 1, &x, &w, &y, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K,
                              int stride, int pad, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g(1, 1, 1, &dy, &w, &dx, N, H, W, C, K, stride, pad, dg_cur_prec(), 1, 0, nullptr, 0, &ws, ws_bytes, (hipStream_t)stream, "dg_conv_dgrad");
+    return conv_g("dg_conv_dgrad", 1, 1, 1, &dy, &w, &dx, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_wgrad(const float* dy, const float* x, float* dw, int N, int H, int W, int C, int K,
                              int stride, int pad, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g(2, 1, 1, &dy, &x, &dw, N, H, W, C, K, stride, pad, dg_cur_prec(), 1, accumulate, nullptr, 0, &ws, ws_bytes, (hipStream_t)stream, "dg_conv_wgrad");
+    return conv_g("dg_conv_wgrad", 2, 1, 1, &dy, &x, &dw, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, accumulate, nullptr, 0, &ws, ws_bytes, stream);
 }
 
 // ---- bf16 shadow operands (option "bf16" = 1 only) -------------------------------------------------------------------
 // The same three ops with either operand given as a bf16 tensor of the same logical layout.  Producers write the shadow
 // next to the fp32 tensor (dg_adam_step_flat_bf16 for weights, dg_bn_act_fwd_bf16 / dg_bn_act_bwd_bf16 / the c3 forward for
 // activations and gradients); the result is bit-identical to passing the fp32 tensors (same RNE rounding, same order).
-static int conv_mixed(int op, const void* a_in, int a16, const void* b_in, int b16, void* out, int out16, int N, int H, int W, int C, int K,
-                      int stride, int pad, int accumulate, void* ws, size_t ws_bytes, hipStream_t st, float* stat = nullptr,
-                      size_t stat_floats = 0) {
-    const char* who = op == 0 ? "dg_conv_fwd_mixed" : (op == 1 ? "dg_conv_dgrad_mixed" : "dg_conv_wgrad_mixed");
-    ConvGeom g;
-    int rc = check_geom(who, N, H, W, C, K, stride, pad, &g);
-    if (rc) return rc;
-    DG_CHECK_ARG(a_in && b_in && out, "%s: null pointer", who);
-    if (K == 1) {
-        // the discriminator's 4x4 head (plain reductions): only the ACTIVATION side may be bf16 (x of forward / weight-grad, dx of
-        // input-grad); the [N] vector and the weights are fp32
-        DG_CHECK_ARG(stride == 1, "%s: K==1 only for the 4x4 head", who);
-        return head1_g(op, 1, 1, &a_in, a16, &b_in, b16, &out, out16, N, C, accumulate, st, who);
-    }
-    // bf16 operands / outputs imply the bf16 matrix path for this call (no process-wide switch involved); an all-fp32 call keeps the
-    // caller's arithmetic
-    DgPrecScope scope((a16 || b16 || out16) ? DG_PREC_BF16 : dg_cur_prec());
-    DG_CHECK_ARG(!(out16 && op == 2), "%s: the weight gradient is always fp32", who);
-    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
+// The K == 1 head (the discriminator's 4x4 head, plain reductions) takes only the ACTIVATION side as bf16 (x of forward / weight-grad,
+// dx of input-grad); the [N] vector and the weights are fp32.
+static int mixed_plan_rules(const ConvCall& c, const Plan& pl) {
+    // (the first two are rules on the arguments; they rank behind the shared channel rules)
     // 8-element granules must not straddle a row end: the A operand of the plain GEMM forms has rows of K elements
-    if (a16 && op != 0 && K % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 gradient operand needs K %% 8 == 0 (K=%d)", who, K);
+    if (c.a16 && c.op != 0 && c.K % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 gradient operand needs K %% 8 == 0 (K=%d)", c.who, c.K);
     // the same for the weight gradient's x (B operand: columns are (tap, channel), a tap's run is C elements)
-    if (b16 && op == 2 && C % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 x needs C %% 8 == 0 (C=%d)", who, C);
-    Plan pl;
-    make_plan(op, g, &pl, a16, b16);
-    if (pl.a.prec != 1 && (a16 || b16 || out16)) return dg_fail(DG_ERR_INVALID, "%s: this shape has no bf16 tile kernel", who);
-    pl.a.A = (const float*)a_in; pl.a.B = (const float*)b_in; pl.a.C = (float*)out; pl.a.accumulate = accumulate;
-    pl.a.out16 = out16;
-    if (stat) {     // fused BatchNorm partial statistics of the output (from the fp32 accumulators): rows from dg_conv_mixed_bnstats_rows
-        const int ncols = op == 0 ? K : C;
-        DG_CHECK_ARG(op != 2 && pl.stat_rows > 0 && stat_floats >= (size_t)pl.stat_rows * (3 * ncols + 4),
-                     "%s: statistics buffer too small or no fused statistics for this plan (ask dg_conv_mixed_bnstats_rows)", who);
-        pl.a.stat = stat;
-        pl.a.stat_rs = 3 * ncols + 4;
-    }
-    return run_plan(who, pl, ws, ws_bytes, st);
+    if (c.b16 && c.op == 2 && c.C % 8 != 0) return dg_fail(DG_ERR_INVALID, "%s: a bf16 x needs C %% 8 == 0 (C=%d)", c.who, c.C);
+    if (pl.a.prec != 1 && (c.a16 || c.b16 || c.out16)) return dg_fail(DG_ERR_INVALID, "%s: this shape has no bf16 tile kernel", c.who);
+    return DG_OK;
 }
-extern "C" int dg_conv_mixed_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad, int a_bf16, int b_bf16) {
-    ConvGeom g;
-    if (op == 2 || !query_has_plan("dg_conv_mixed_bnstats_rows", op, N, H, W, C, K, stride, pad, &g) || stride != 2) return 0;
-    DgPrecScope scope(DG_PREC_BF16);
-    Plan pl;
-    make_plan(op, g, &pl, a_bf16, b_bf16);
-    return pl.stat_rows;
+static int conv_mixed(const char* who, int op, const void* a_in, int a16, const void* b_in, int b16, void* out, int out16, int N, int H, int W, int C,
+                      int K, int stride, int pad, int accumulate, float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    ConvCall c = conv_call(who, op, &a_in, &b_in, &out, N, H, W, C, K, stride, pad, &ws, ws_bytes, stream);
+    // bf16 operands / outputs imply the bf16 matrix path for this call (no process-wide switch involved); an all-fp32 call keeps the
+    // process default
+    if (a16 || b16 || out16) c.prec = DG_PREC_BF16;
+    c.a16 = a16; c.b16 = b16; c.out16 = out16;      // (the weight gradient is always fp32: dg_conv_wgrad_mixed has no such flag)
+    c.accumulate = accumulate;
+    c.stat = stat ? &stat : nullptr; c.stat_floats = stat_floats;     // rows from dg_conv_mixed_bnstats_rows (from the fp32 accumulators)
+    c.plan_rules = mixed_plan_rules;
+    return conv_launch(c);
 }
 extern "C" int dg_conv_fwd_mixed(const void* x, int x_bf16, const void* w, int w_bf16, void* y, int y_bf16, int N, int H, int W, int C, int K,
                                  int stride, int pad, float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_mixed(0, x, x_bf16, w, w_bf16, y, y_bf16, N, H, W, C, K, stride, pad, 0, ws, ws_bytes, (hipStream_t)stream, stat, stat_floats);
+    return conv_mixed("dg_conv_fwd_mixed", 0, x, x_bf16, w, w_bf16, y, y_bf16, N, H, W, C, K, stride, pad, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad_mixed(const void* dy, int dy_bf16, const void* w, int w_bf16, void* dx, int dx_bf16, int N, int H, int W, int C, int K,
                                    int stride, int pad, float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_mixed(1, dy, dy_bf16, w, w_bf16, dx, dx_bf16, N, H, W, C, K, stride, pad, 0, ws, ws_bytes, (hipStream_t)stream, stat, stat_floats);
+    return conv_mixed("dg_conv_dgrad_mixed", 1, dy, dy_bf16, w, w_bf16, dx, dx_bf16, N, H, W, C, K, stride, pad, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, int x_bf16, float* dw, int N, int H, int W, int C, int K,
                                    int stride, int pad, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_mixed(2, dy, dy_bf16, x, x_bf16, dw, 0, N, H, W, C, K, stride, pad, accumulate, ws, ws_bytes, (hipStream_t)stream);
-}
-// can this (op, shape) take bf16 operands at all?  (host planning aid: 0 = no, 1 = the register-staged bf16 tile kernel,
-// 2 = with BOTH operands bf16 the LDS-DMA kernel of igemm_dma.hip runs)
-extern "C" int dg_conv_bf16_operands_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (!query_has_plan("dg_conv_bf16_operands_ok", op, N, H, W, C, K, stride, pad, &g)) return 0;
-    DgPrecScope scope(DG_PREC_BF16);
-    Plan pl;
-    make_plan(op, g, &pl, 1, 1);
-    return pl.a.prec == 1 ? (pl.dma ? 2 : 1) : 0;
+    return conv_mixed("dg_conv_wgrad_mixed", 2, dy, dy_bf16, x, x_bf16, dw, 0, N, H, W, C, K, stride, pad, accumulate, nullptr, 0, ws, ws_bytes, stream);
 }
 
 // ---- fp32 operands as three bf16 planes (option "bf16" = 2 only): igemm_dma_x3.hip -----------------------------------------
 // a3 / b3 point at plane 0 (hi) of an operand; planes 1 (mid) and 2 (lo) follow a_plane / b_plane BYTES further on (>= the
 // tensor's 2 * numel; a weight inside a flat parameter group has the group's plane distance).  Written by dg_f32_to_bf16x3 or
 // by the fused producers (dg_adam_step_flat_x3, dg_bn_act_fwd_x3, dg_bn_act_bwd_x3); outputs are fp32.
-// forward, stride 2, no LDS-DMA plane kernel for the shape (fewer than 192 output channels or rows): the register-staged 128 x 128
-// tiles can read plane triples (16-byte granules of 8 bf16: C % 8 == 0; buffer-descriptor kernels only)
-static bool x3_register_staged_planes_ok(int op, const ConvGeom& g, const Plan& pl) {
-#ifndef DG_EXPERIMENTS
-    return false;           // (the plane-reading register-staged tiles exist in the experiments library only)
-#endif
-    return op == 0 && g.stride == 2 && pl.a.prec == 2 && pl.mode == MODE_FWD && pl.wm == 2 && pl.wn == 2 && pl.kt == 16 && g.C % 16 == 0 &&
-           pl.a.abytes != 0 && pl.a.bbytes != 0;
-}
-static int conv_x3(int op, const void* a3, long a_plane, const void* b3, long b_plane, int b_transposed, float* out, int N, int H, int W, int C, int K,
-                   int stride, int pad, int accumulate, void* ws, size_t ws_bytes, hipStream_t st, int a_layout = 0, float* stat = nullptr,
-                   size_t stat_floats = 0) {
-    const char* who = op == 0 ? "dg_conv_fwd_x3" : (op == 1 ? "dg_conv_dgrad_x3" : "dg_conv_wgrad_x3");
-    ConvGeom g;
-    int rc = check_geom(who, N, H, W, C, K, stride, pad, &g);
-    if (rc) return rc;
-    DG_CHECK_ARG(a3 && b3 && out, "%s: null pointer", who);
-    DgPrecScope scope(DG_PREC_F32X3);       // plane operands ARE the f32x3 arithmetic: no process-wide switch involved
-    DG_CHECK_ARG(K > 1, "%s: the K == 1 head has no plane form", who);
-    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;      // the same channel rules as the fp32 forms: dg_conv_x3_planes_ok answers 0 there
-    Plan pl;
-    // forward with plain (not transposed) weight planes where the window forward kernel would apply: the register-staged tiles read
-    // the planes instead (igemm_kernel<.., PREC 2, A16, B16>)
-    make_plan(op, g, &pl, 3, 3, (op == 0 && !b_transposed) ? 0 : 1);
-    const bool rs_planes = pl.dma == 0 && x3_register_staged_planes_ok(op, g, pl);
+static int x3_plan_rules(const ConvCall& c, const Plan& pl) {
+    const char* who = c.who;
+    const bool rs_planes = pl.dma == 0 && x3_register_staged_planes_ok(c.op, pl);
     if (pl.dma != 2 && pl.dma != 3 && pl.dma != 5 && !rs_planes)
         return dg_fail(DG_ERR_INVALID, "%s: this shape has no plane kernel (ask dg_conv_x3_planes_ok)", who);
-    DG_CHECK_ARG(!(rs_planes && b_transposed), "%s: the register-staged plane reader takes the PLAIN weight planes", who);
-    DG_CHECK_ARG(a_plane >= (long)pl.a.abytes && b_plane >= (long)pl.a.bbytes && a_plane % 16 == 0 && b_plane % 16 == 0,
-                 "%s: plane distances %ld / %ld (operands are %u / %u bytes per plane)", who, a_plane, b_plane, pl.a.abytes, pl.a.bbytes);
-    pl.a.A = (const float*)a3; pl.a.B = (const float*)b3; pl.a.C = out; pl.a.accumulate = accumulate;
-    pl.a.a_plane = a_plane; pl.a.b_plane = b_plane;
-    DG_CHECK_ARG(!b_transposed || op == 0, "%s: only the forward form takes transposed weight planes", who);
-    pl.a.b_transposed = b_transposed ? 1 : 0;
+    DG_CHECK_ARG(!(rs_planes && c.b_transposed), "%s: the register-staged plane reader takes the PLAIN weight planes", who);
+    DG_CHECK_ARG(c.a_plane >= (long)pl.a.abytes && c.b_plane >= (long)pl.a.bbytes && c.a_plane % 16 == 0 && c.b_plane % 16 == 0,
+                 "%s: plane distances %ld / %ld (operands are %u / %u bytes per plane)", who, c.a_plane, c.b_plane, pl.a.abytes, pl.a.bbytes);
+    DG_CHECK_ARG(!c.b_transposed || c.op == 0, "%s: only the forward form takes transposed weight planes", who);
     // quad-chunk gradient planes [pixels / 4][K / 16][4][16]: read by the window input-grad kernel and by the plane weight-grad kernel
-    DG_CHECK_ARG(a_layout == 0 || a_layout == 1, "%s: plane layout %d", who, a_layout);
-    DG_CHECK_ARG(a_layout == 0 || (K % 64 == 0 && ((op == 1 && pl.dma == 3) || (op == 2 && pl.dma == 2))),
+    DG_CHECK_ARG(c.a_layout == 0 || c.a_layout == 1, "%s: plane layout %d", who, c.a_layout);
+    DG_CHECK_ARG(c.a_layout == 0 || (c.K % 64 == 0 && ((c.op == 1 && pl.dma == 3) || (c.op == 2 && pl.dma == 2))),
                  "%s: quad-chunk planes are only read by the window input-grad and the plane weight-grad kernels (K %% 64 == 0)", who);
-    pl.a.a_cm = a_layout;
-    if (stat) {     // fused BatchNorm partial statistics of the output (forward / input-grad): rows from dg_conv_x3_bnstats_rows
-        const int ncols = op == 0 ? K : C;
-        DG_CHECK_ARG(op != 2 && pl.stat_rows > 0 && stat_floats >= (size_t)pl.stat_rows * (3 * ncols + 4),
-                     "%s: statistics buffer too small or no fused statistics for this plan (ask dg_conv_x3_bnstats_rows)", who);
-        pl.a.stat = stat;
-        pl.a.stat_rs = 3 * ncols + 4;
-    }
-    return run_plan(who, pl, ws, ws_bytes, st);
+    return DG_OK;
+}
+static int conv_x3(const char* who, int op, const void* a3, long a_plane, int a_layout, const void* b3, long b_plane, int b_transposed, float* out, int N,
+                   int H, int W, int C, int K, int stride, int pad, int accumulate, float* stat, size_t stat_floats, void* ws, size_t ws_bytes,
+                   dg_stream_t stream) {
+    ConvCall c = conv_call(who, op, &a3, &b3, (void* const*)&out, N, H, W, C, K, stride, pad, &ws, ws_bytes, stream);
+    c.prec = DG_PREC_F32X3;       // plane operands ARE the f32x3 arithmetic: no process-wide switch involved
+    c.has_head = false;
+    c.a16 = c.b16 = 3;
+    c.a_plane = a_plane; c.b_plane = b_plane; c.a_layout = a_layout; c.b_transposed = b_transposed;
+    c.accumulate = accumulate;
+    c.stat = stat ? &stat : nullptr; c.stat_floats = stat_floats;     // forward / input-grad: rows from dg_conv_x3_bnstats_rows
+    c.plan_rules = x3_plan_rules;
+    return conv_launch(c);
 }
 // w_transposed: w3 is the transposed copy wT[(r, s, c)][k] of the weight planes (dg_x3_transpose_planes) -- the faster form
 extern "C" int dg_conv_fwd_x3(const void* x3, long x_plane, const void* w3, long w_plane, int w_transposed, float* y, int N, int H, int W,
                               int C, int K, int stride, int pad, float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_x3(0, x3, x_plane, w3, w_plane, w_transposed, y, N, H, W, C, K, stride, pad, 0, ws, ws_bytes, (hipStream_t)stream, 0, stat, stat_floats);
+    return conv_x3("dg_conv_fwd_x3", 0, x3, x_plane, 0, w3, w_plane, w_transposed, y, N, H, W, C, K, stride, pad, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad_x3(const void* dy3, long dy_plane, int dy_layout, const void* w3, long w_plane, float* dx, int N, int H, int W, int C, int K,
                                 int stride, int pad, float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_x3(1, dy3, dy_plane, w3, w_plane, 0, dx, N, H, W, C, K, stride, pad, 0, ws, ws_bytes, (hipStream_t)stream, dy_layout, stat, stat_floats);
-}
-// partial-statistics rows the plane kernel of (op, shape) emits (0: none -- no plane kernel, or one without the epilogue)
-extern "C" int dg_conv_x3_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (op == 2 || !query_has_plan("dg_conv_x3_bnstats_rows", op, N, H, W, C, K, stride, pad, &g)) return 0;
-    DgPrecScope scope(DG_PREC_F32X3);
-    Plan pl;
-    make_plan(op, g, &pl, 3, 3);
-    return (pl.dma == 2 || pl.dma == 3) ? pl.stat_rows : 0;
+    return conv_x3("dg_conv_dgrad_x3", 1, dy3, dy_plane, dy_layout, w3, w_plane, 0, dx, N, H, W, C, K, stride, pad, 0, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_wgrad_x3(const void* dy3, long dy_plane, int dy_layout, const void* x3, long x_plane, float* dw, int N, int H, int W, int C, int K,
                                 int stride, int pad, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_x3(2, dy3, dy_plane, x3, x_plane, 0, dw, N, H, W, C, K, stride, pad, accumulate, ws, ws_bytes, (hipStream_t)stream, dy_layout);
-}
-// does this (op, shape) have a plane kernel under option bf16 = 2?  (host planning aid)  0: no; 1: yes; 3: yes -- the window
-// FORWARD kernel with the transposed weight planes (w_transposed = 1 of dg_conv_fwd_x3), the register-staged plane reader with the
-// plain ones; 4: yes -- the register-staged tiles read the (plain) planes; 2: yes, and it is the window input-grad kernel, which
-// wants its gradient operand in the quad-chunk layout (plane_layout 1 of dg_bn_act_*_x3)
-extern "C" int dg_conv_x3_planes_ok(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (!query_has_plan("dg_conv_x3_planes_ok", op, N, H, W, C, K, stride, pad, &g)) return 0;
-    DgPrecScope scope(DG_PREC_F32X3);
-    Plan pl;
-    make_plan(op, g, &pl, 3, 3);
-    if (pl.dma == 0 && x3_register_staged_planes_ok(op, g, pl)) return 4;
-    return pl.dma == 5 ? 3 : (pl.dma == 3 ? (K % 64 == 0 ? 2 : 1) : (pl.dma == 2 ? 1 : 0));
+    return conv_x3("dg_conv_wgrad_x3", 2, dy3, dy_plane, dy_layout, x3, x_plane, 0, dw, N, H, W, C, K, stride, pad, accumulate, nullptr, 0, ws, ws_bytes, stream);
 }
 
 // ---- inference path: conv with BatchNorm folded in (scale in the weights, shift as a bias) + activation ----------
 // Replaces [Conv2d | ConvTranspose2d] -> BatchNorm2d(eval) -> LeakyReLU/ReLU of inference.py:149,172-187 by ONE kernel:
 // the caller multiplies the weights by gamma*invstd per output channel and passes bias = beta - mean*gamma*invstd.
-static int conv_bias_act(int op, const float* a_in, const float* w, const float* bias, float* out, int N, int H, int W, int C, int K,
-                         int stride, int pad, int act, float slope, void* ws, size_t ws_bytes, hipStream_t st) {
-    const char* who = op == 0 ? "dg_conv_fwd_bias_act" : "dg_conv_dgrad_bias_act";
-    ConvGeom g;
-    int rc = check_geom(who, N, H, W, C, K, stride, pad, &g);
-    if (rc) return rc;
-    DG_CHECK_ARG(a_in && w && out, "%s: null pointer", who);
-    DG_CHECK_ARG(K > 1, "%s: K == 1 head has no folded form", who);
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "%s: bad act %d", who, act);
-    if ((rc = check_channels(who, op, g)) != DG_OK) return rc;
-    Plan pl;
-    make_plan(op, g, &pl);
-    pl.a.A = a_in; pl.a.B = w; pl.a.C = out;
-    pl.a.bias = bias; pl.a.act = act; pl.a.slope = slope;
-    pl.a.bias_mod = (pl.mode == MODE_DGRAD_PLAIN) ? C : pl.a.Ng;
-    return run_plan(who, pl, ws, ws_bytes, st);
+static int bias_act_arg_rules(const ConvCall& c) {
+    DG_CHECK_ARG(c.act == DG_ACT_NONE || c.act == DG_ACT_LEAKY || c.act == DG_ACT_RELU, "%s: bad act %d", c.who, c.act);
+    return DG_OK;
+}
+static int conv_bias_act(const char* who, int op, const float* a_in, const float* w, const float* bias, float* out, int N, int H, int W, int C, int K,
+                         int stride, int pad, int act, float slope, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    ConvCall c = conv_call(who, op, (const void* const*)&a_in, (const void* const*)&w, (void* const*)&out, N, H, W, C, K, stride, pad, &ws, ws_bytes, stream);
+    c.has_head = false;
+    c.bias = bias; c.act = act; c.slope = slope;
+    c.arg_rules = bias_act_arg_rules;
+    return conv_launch(c);
 }
 extern "C" int dg_conv_fwd_bias_act(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, int K,
                                     int stride, int pad, int act, float slope, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_bias_act(0, x, w, bias, y, N, H, W, C, K, stride, pad, act, slope, ws, ws_bytes, (hipStream_t)stream);
+    return conv_bias_act("dg_conv_fwd_bias_act", 0, x, w, bias, y, N, H, W, C, K, stride, pad, act, slope, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad_bias_act(const float* dy, const float* w, const float* bias, float* dx, int N, int H, int W, int C, int K,
                                       int stride, int pad, int act, float slope, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_bias_act(1, dy, w, bias, dx, N, H, W, C, K, stride, pad, act, slope, ws, ws_bytes, (hipStream_t)stream);
+    return conv_bias_act("dg_conv_dgrad_bias_act", 1, dy, w, bias, dx, N, H, W, C, K, stride, pad, act, slope, ws, ws_bytes, stream);
 }
 
-// ---- conv + fused BatchNorm partial statistics -------------------------------------------------------
-extern "C" int dg_conv_plan_splits(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (!query_has_plan("dg_conv_plan_splits", op, N, H, W, C, K, stride, pad, &g)) return 1;
-    Plan pl;
-    make_plan(op, g, &pl);
-    return pl.a.splits;
+// ---- conv + fused BatchNorm partial statistics: the stride-2 layers, statistics always on ---------------------------------
+static int bnstats_arg_rules(const ConvCall& c) {
+    DG_CHECK_ARG(c.stat, "%s: null pointer", c.who);
+    DG_CHECK_ARG(c.K % 32 == 0 && c.C % 32 == 0, "%s: C and K must be multiples of 32", c.who);
+    return DG_OK;
 }
-extern "C" int dg_conv_bnstats_rows(int op, int N, int H, int W, int C, int K, int stride, int pad) {
-    ConvGeom g;
-    if (op == 2 || !query_has_plan("dg_conv_bnstats_rows", op, N, H, W, C, K, stride, pad, &g) || stride != 2) return 0;
-    Plan pl;
-    make_plan(op, g, &pl);
-    return pl.stat_rows;
-}
-static int conv_with_stats(int op, const float* a_in, const float* w, float* out, int N, int H, int W, int C, int K,
-                           float* stat, size_t stat_floats, void* ws, size_t ws_bytes, hipStream_t st) {
-    const char* who = op == 0 ? "dg_conv_fwd_bnstats" : "dg_conv_dgrad_bnstats";
-    ConvGeom g;
-    int rc = check_geom(who, N, H, W, C, K, 2, 1, &g);
-    if (rc) return rc;
-    DG_CHECK_ARG(a_in && w && out && stat, "%s: null pointer", who);
-    DG_CHECK_ARG(K % 32 == 0 && C % 32 == 0, "%s: C and K must be multiples of 32", who);
-    Plan pl;
-    make_plan(op, g, &pl);
-    const int ncols = op == 0 ? K : C;
-    DG_CHECK_ARG(pl.stat_rows > 0 && stat_floats >= (size_t)pl.stat_rows * (3 * ncols + 4), "%s: statistics buffer too small", who);
-    pl.a.A = a_in; pl.a.B = w; pl.a.C = out;
-    pl.a.stat = stat; pl.a.stat_rs = 3 * ncols + 4;
-    return run_plan(who, pl, ws, ws_bytes, st);
+static int conv_with_stats(const char* who, int op, const float* a_in, const float* w, float* out, int N, int H, int W, int C, int K,
+                           float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    ConvCall c = conv_call(who, op, (const void* const*)&a_in, (const void* const*)&w, (void* const*)&out, N, H, W, C, K, 2, 1, &ws, ws_bytes, stream);
+    c.has_head = false;
+    c.stat = stat ? &stat : nullptr; c.stat_floats = stat_floats;
+    c.arg_rules = bnstats_arg_rules;
+    return conv_launch(c);
 }
 extern "C" int dg_conv_fwd_bnstats(const float* x, const float* w, float* y, int N, int H, int W, int C, int K,
                                    float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_with_stats(0, x, w, y, N, H, W, C, K, stat, stat_floats, ws, ws_bytes, (hipStream_t)stream);
+    return conv_with_stats("dg_conv_fwd_bnstats", 0, x, w, y, N, H, W, C, K, stat, stat_floats, ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad_bnstats(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K,
                                      float* stat, size_t stat_floats, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_with_stats(1, dy, w, dx, N, H, W, C, K, stat, stat_floats, ws, ws_bytes, (hipStream_t)stream);
+    return conv_with_stats("dg_conv_dgrad_bnstats", 1, dy, w, dx, N, H, W, C, K, stat, stat_floats, ws, ws_bytes, stream);
 }
 
 // ---- named wrappers --------------------------------------------------------------
-extern "C" int dg_conv4x4s2_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K,
-                                void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4s2_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_fwd(x, w, y, N, H, W, C, K, 2, 1, ws, wsb, s);
 }
-extern "C" int dg_conv4x4s2_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K,
-                                  void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4s2_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_dgrad(dy, w, dx, N, H, W, C, K, 2, 1, ws, wsb, s);
 }
-extern "C" int dg_conv4x4s2_wgrad(const float* dy, const float* x, float* dw, int N, int H, int W, int C, int K,
-                                  int acc, void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4s2_wgrad(const float* dy, const float* x, float* dw, int N, int H, int W, int C, int K, int acc, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_wgrad(dy, x, dw, N, H, W, C, K, 2, 1, acc, ws, wsb, s);
 }
-extern "C" int dg_conv4x4_valid_fwd(const float* x, const float* w, float* y, int N, int C, int K,
-                                    void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4_valid_fwd(const float* x, const float* w, float* y, int N, int C, int K, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_fwd(x, w, y, N, 4, 4, C, K, 1, 0, ws, wsb, s);
 }
-extern "C" int dg_conv4x4_valid_dgrad(const float* dy, const float* w, float* dx, int N, int C, int K,
-                                      void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4_valid_dgrad(const float* dy, const float* w, float* dx, int N, int C, int K, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_dgrad(dy, w, dx, N, 4, 4, C, K, 1, 0, ws, wsb, s);
 }
-extern "C" int dg_conv4x4_valid_wgrad(const float* dy, const float* x, float* dw, int N, int C, int K,
-                                      int acc, void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_conv4x4_valid_wgrad(const float* dy, const float* x, float* dw, int N, int C, int K, int acc, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_wgrad(dy, x, dw, N, 4, 4, C, K, 1, 0, acc, ws, wsb, s);
 }
 // ConvTranspose2d(Cin,Cout,4,2,1) == dgrad of Conv2d(C=Cout -> K=Cin) on the 2Hin x 2Win grid
-extern "C" int dg_convT4x4s2_fwd(const float* x, const float* w, float* y, int N, int Hin, int Win, int Cin, int Cout,
-                                 void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4s2_fwd(const float* x, const float* w, float* y, int N, int Hin, int Win, int Cin, int Cout, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_dgrad(x, w, y, N, 2 * Hin, 2 * Win, Cout, Cin, 2, 1, ws, wsb, s);
 }
-extern "C" int dg_convT4x4s2_dgrad(const float* dy, const float* w, float* dx, int N, int Hin, int Win, int Cin, int Cout,
-                                   void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4s2_dgrad(const float* dy, const float* w, float* dx, int N, int Hin, int Win, int Cin, int Cout, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_fwd(dy, w, dx, N, 2 * Hin, 2 * Win, Cout, Cin, 2, 1, ws, wsb, s);
 }
-extern "C" int dg_convT4x4s2_wgrad(const float* dy, const float* x, float* dw, int N, int Hin, int Win, int Cin, int Cout,
-                                   int acc, void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4s2_wgrad(const float* dy, const float* x, float* dw, int N, int Hin, int Win, int Cin, int Cout, int acc, void* ws, size_t wsb, dg_stream_t s) {
     // dw[cin][r][s][cout] = sum x[.., cin] * dy[.., cout] : roles (dy := x, x := dy)
     return dg_conv_wgrad(x, dy, dw, N, 2 * Hin, 2 * Win, Cout, Cin, 2, 1, acc, ws, wsb, s);
 }
-extern "C" int dg_convT4x4_1to4_fwd(const float* x, const float* w, float* y, int N, int Cin, int Cout,
-                                    void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4_1to4_fwd(const float* x, const float* w, float* y, int N, int Cin, int Cout, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_dgrad(x, w, y, N, 4, 4, Cout, Cin, 1, 0, ws, wsb, s);
 }
-extern "C" int dg_convT4x4_1to4_dgrad(const float* dy, const float* w, float* dx, int N, int Cin, int Cout,
-                                      void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4_1to4_dgrad(const float* dy, const float* w, float* dx, int N, int Cin, int Cout, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_fwd(dy, w, dx, N, 4, 4, Cout, Cin, 1, 0, ws, wsb, s);
 }
-extern "C" int dg_convT4x4_1to4_wgrad(const float* dy, const float* x, float* dw, int N, int Cin, int Cout,
-                                      int acc, void* ws, size_t wsb, dg_stream_t s) {
+extern "C" int dg_convT4x4_1to4_wgrad(const float* dy, const float* x, float* dw, int N, int Cin, int Cout, int acc, void* ws, size_t wsb, dg_stream_t s) {
     return dg_conv_wgrad(x, dy, dw, N, 4, 4, Cout, Cin, 1, 0, acc, ws, wsb, s);
 }
 

@@ -119,7 +119,7 @@ class DiscoGANTrainer:
         # with fp32 accumulation (BASELINE configs[4]); tensors, BatchNorm, losses, master weights, Adam stay fp32.
         # "f32x3": fp32-accurate products on the bf16 matrix path -- every operand is split into three bf16 planes
         # (24 significand bits), six MFMAs per product block, fp32 accumulation (csrc/igemm.hip PREC 2).
-        # Process-global library option, set for the lifetime of this trainer's calls.
+        # Passed to the library with every call (self.ctx below): no process-global option is set.
         if mfma_dtype not in ("f32", "bf16", "f32x3"):
             raise ValueError("mfma_dtype must be 'f32', 'bf16' or 'f32x3'")
         self.mfma_dtype = mfma_dtype

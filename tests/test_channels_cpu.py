@@ -2,12 +2,14 @@
 makes -- none may fail, whatever the argument tuple --, what the queries answer for shapes the launch entry points refuse, and the
 discrimination of the fp64 error bound at ragged channel counts (channel rotations beside the one-pixel shifts)."""
 import ctypes
+import json
 import math
+import os
 
 import pytest
 import torch
 
-from discogan_modernized_amd import _lib, ops
+from discogan_modernized_amd import _lib, model, ops
 from tests import shape_ref as R
 
 OPS = (0, 1, 2)                                            # forward, input gradient, weight gradient
@@ -117,6 +119,63 @@ def test_refused_input_gradient_is_refused_not_planned():
     assert b"multiple of 32" in L.dg_last_error()
     # a bf16 x of the weight gradient: 8-element granules must not straddle a tap
     assert L.dg_conv_wgrad_mixed(d, 0, d, 1, d, 3, 8, 8, 36, 100, 2, 1, 0, None, 0, None) < 0 and b"C % 8" in L.dg_last_error()
+
+
+PLAN_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan_table.json")
+PLAN_COLUMNS = ("ws", "ws_p", "splits", "splits_p", "rows", "rows_p", "bf16_ok", "x3_ok", "x3_rows", "mixed_rows")
+
+
+def plan_table_shapes():
+    """(N, H, C, K, stride, pad) of the table: every interior conv layer of the generators and discriminators (model.py: the
+    stride-2 stages behind the 3-channel one -- a decoder stage is the input gradient of the same geometry --, the generator's
+    100-channel bottleneck and the discriminator's K = 1 head) at 64 px with N 64 and 256 and at 512 px with N 32, and an off-model
+    grid."""
+    shapes = []
+    for size, N in ((64, 64), (64, 256), (512, 32)):
+        ch = model.stage_channels(size)
+        shapes += [(N, size >> i, ch[i - 1], ch[i], 2, 1) for i in range(1, len(ch))]
+        shapes += [(N, 4, ch[-1], 100, 1, 0), (N, 4, ch[-1], 1, 1, 0)]
+    for C in (32, 96, 128, 192, 320):
+        shapes += [(3, H, C, K, 2, 1) for K in (4, 32, 64, 100, 160, 288) for H in (8, 64)]
+        shapes += [(3, 4, C, K, 1, 0) for K in (1, 32)]
+    return shapes
+
+
+def plan_table_rows(L):
+    """One row of PLAN_COLUMNS per shape x op x arithmetic x plan_groups, in that order, from the library L (option "kt" 0)."""
+    rows = []
+    try:
+        for N, H, C, K, stride, pad in plan_table_shapes():
+            for op in OPS:
+                for prec in (0, 1, 2):
+                    _lib.set_option("bf16", prec)
+                    for pg in (1, 4):
+                        q = all_queries(L, op, N, H, C, K, stride, pad, prec, pg)
+                        rows.append([q[c] for c in PLAN_COLUMNS])
+    finally:
+        _lib.set_option("bf16", 0)
+    return rows
+
+
+def test_plans_match_the_recorded_table():
+    """tests/golden/conv_plan_table.json holds what every plan query answered before the host layer was given one launch path and one
+    query helper (written by tests/golden/make_conv_plan_table.py from the library of the commit before): workspace bytes, K-splits,
+    statistics rows and the bf16 / plane kernel codes of the model's layers and of an off-model grid, per op, arithmetic and
+    plan_groups.  The planner reads no device property, so the table holds on any machine; a change of plan is a change of
+    speed or of summation order and must be made on purpose, with the table regenerated."""
+    with open(PLAN_TABLE) as f:
+        table = json.load(f)
+    assert table["columns"] == list(PLAN_COLUMNS)
+    assert [tuple(s) for s in table["shapes"]] == plan_table_shapes()
+    rows = plan_table_rows(_lib.load())
+    assert len(rows) == len(table["rows"]) == len(plan_table_shapes()) * 3 * 3 * 2
+    it = iter(zip(rows, table["rows"]))
+    for shape in plan_table_shapes():
+        for op in OPS:
+            for prec in (0, 1, 2):
+                for pg in (1, 4):
+                    got, want = next(it)
+                    assert got == want, f"(N, H, C, K, stride, pad) {shape} op {op} arithmetic {prec} plan_groups {pg}: {PLAN_COLUMNS}"
 
 
 OPNAMES = ("fwd", "dgrad", "wgrad")
