@@ -103,6 +103,11 @@ SIGNATURES = {
     "dg_adam_step_flat": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p]),
     "dg_ema_update_flat": (_i, [_p, _p, _z, _f, _p]),
     "dg_swap_flat": (_i, [_p, _p, _z, _p]),
+    "dg_grad_stats_workspace_bytes": (_z, []),
+    "dg_grad_sumsq_partial": (_i, [_p, _z, _p, _z, _i, C.POINTER(_i), _p]),
+    "dg_grad_clip_finalize": (_i, [_p, _i, _d, _d, _i, _p, _p]),
+    "dg_adam_advance_c": (_i, [_p, _d, _d, _d, _p, _p]),
+    "dg_adam_step_flat_c": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _p, _p, _i, _z, _p]),
     "dg_bce_target_fwd": (_i, [_p, _p, _i, _p, _p]),
     "dg_bce_target_bwd": (_i, [_p, _p, _i, _p, _p, _p]),
     "dg_hinge_fwd": (_i, [_p, _p, _z, _f, _p, _p, _z, _p]),

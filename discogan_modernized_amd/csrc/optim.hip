@@ -8,7 +8,9 @@
 //   denom = sqrt(v)/sqrt(1-b2^t) + eps ; p = p - (lr/(1-b1^t)) * m/denom
 #include "dg_common.h"
 
-__global__ void adam_advance_kernel(double* state, double lr, double b1, double b2) {
+// ctl: the step's device control block (dg_grad_clip_finalize), or nullptr; ctl[3] != 0 = this step is skipped, the count stays
+__global__ void adam_advance_kernel(double* state, double lr, double b1, double b2, const double* ctl) {
+    if (ctl != nullptr && ctl[3] != 0.0) return;
     const double t = state[0] + 1.0;
     state[0] = t;
     state[1] = lr / (1.0 - pow(b1, t));
@@ -34,7 +36,14 @@ template <int P16>
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long n,
                                                         const double* __restrict__ state, float b1, float b2, float eps,
-                                                        float wd, float gscale, __bf16* __restrict__ p16, long pstride) {
+                                                        float wd, float gscale, __bf16* __restrict__ p16, long pstride,
+                                                        const double* __restrict__ ctl) {
+    // ctl (or nullptr): the gradient scale and the go / no-go of this step come from device memory (dg_grad_clip_finalize on the same
+    // stream) instead of the host.  A skipped step returns before its first load: p, m, v and every derived form keep their bits.
+    if (ctl != nullptr) {
+        if (ctl[3] != 0.0) return;
+        gscale = (float)ctl[2];
+    }
     const float step_size = (float)state[1];
     const float bc2_sqrt = (float)state[2];
     const float omb1 = 1.f - b1, omb2 = 1.f - b2;
@@ -117,7 +126,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
 
 extern "C" int dg_adam_advance(double* state, double lr, double beta1, double beta2, dg_stream_t stream) {
     DG_CHECK_ARG(state, "dg_adam_advance: null state");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2);
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2, (const double*)nullptr);
     DG_CHECK_LAUNCH("adam_advance");
     return DG_OK;
 }
@@ -129,7 +138,7 @@ extern "C" int dg_adam_step_flat(float* p, const float* g, float* m, float* v, s
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(adam_step_kernel<0>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)nullptr, 0L);
+                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)nullptr, 0L, (const double*)nullptr);
     DG_CHECK_LAUNCH("adam_step");
     return DG_OK;
 }
@@ -141,7 +150,7 @@ extern "C" int dg_adam_step_flat_bf16(float* p, const float* g, float* m, float*
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(adam_step_kernel<1>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p16, 0L);
+                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p16, 0L, (const double*)nullptr);
     DG_CHECK_LAUNCH("adam_step_bf16");
     return DG_OK;
 }
@@ -156,7 +165,7 @@ extern "C" int dg_adam_step_flat_x3(float* p, const float* g, float* m, float* v
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(adam_step_kernel<3>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p3, (long)plane_elems);
+                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p3, (long)plane_elems, (const double*)nullptr);
     DG_CHECK_LAUNCH("adam_step_x3");
     return DG_OK;
 }
@@ -274,5 +283,139 @@ extern "C" int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t stream) {
     DG_CHECK_ARG((hi - lo) / sizeof(float) >= n, "dg_swap_flat: the two ranges of %zu floats overlap", n);
     hipLaunchKernelGGL(swap_flat_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, (unsigned int*)a, (unsigned int*)b, (long)n);
     DG_CHECK_LAUNCH("swap_flat");
+    return DG_OK;
+}
+
+// ---- gradient statistics and step control (optim.Adam.enable_grad_control) --------------------------------------------------------
+// Global gradient norm, clipping by it and a guard against a non-finite gradient, with no host round trip: a read-only pass over the flat
+// gradient leaves one fp64 partial per block, one workgroup folds the partials into the device control block `ctl` (layout:
+// include/discogan_hip.h), and the Adam kernels above take their gradient scale and their go / no-go from ctl.
+// Every element is widened to double before it is squared: the product of two fp32 values is exact in fp64 and at most 2^256, so a finite
+// gradient cannot overflow or underflow the sum, and only inf / NaN elements make it non-finite.  No atomics and a fixed summation order
+// (per thread, per wave, per block, then over the slots in index order): the same gradient gives the same bits on every run.
+#define DG_GRAD_STATS_SLOTS 16384            // workspace capacity in partials: four ranges at the full grid
+static_assert(DG_GRAD_STATS_SLOTS >= 4096, "one full-grid range must fit");
+
+__device__ __forceinline__ void sumsq4(double (&a)[4], const f32x4& x) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] += (double)x[j] * (double)x[j];      // (an exact product: fused or not, the same bits)
+}
+__global__ __launch_bounds__(256) void grad_sumsq_partial_kernel(const float* __restrict__ g, long n, double* __restrict__ ws) {
+    __shared__ double red[4];
+    const long n4 = n >> 2;
+    const long stride = (long)gridDim.x * 256;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    // four trips of the grid-stride loop at a time: four independent 16-byte loads in flight per thread (a read-only stream has no
+    // stores to overlap them with); the additions keep the order of the plain loop below
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 x0 = *(const f32x4*)(g + i * 4);
+        const f32x4 x1 = *(const f32x4*)(g + (i + stride) * 4);
+        const f32x4 x2 = *(const f32x4*)(g + (i + 2 * stride) * 4);
+        const f32x4 x3 = *(const f32x4*)(g + (i + 3 * stride) * 4);
+        sumsq4(a, x0);
+        sumsq4(a, x1);
+        sumsq4(a, x2);
+        sumsq4(a, x3);
+    }
+    for (; i < n4; i += stride) sumsq4(a, *(const f32x4*)(g + i * 4));
+    double s = (a[0] + a[1]) + (a[2] + a[3]);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long e = n4 * 4; e < n; ++e) s += (double)g[e] * (double)g[e];
+    s = dg_wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ ws, int slots, double pre_scale,
+                                                                 double max_norm, int guard, double* __restrict__ ctl) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < slots; i += 256) s += ws[i];
+    s = dg_wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double sumsq = (red[0] + red[1]) + (red[2] + red[3]);
+    const double norm = sqrt(sumsq) * pre_scale;
+    double scale = pre_scale;
+    bool clipped = false;
+    if (max_norm > 0.0) {
+        // torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to at most 1 (a NaN stays a NaN, inf gives 0)
+        const double coef = max_norm / (norm + 1e-6);
+        if (!(coef >= 1.0)) {
+            scale = pre_scale * coef;
+            clipped = coef < 1.0;
+        }
+    }
+    const bool finite = (sumsq - sumsq) == 0.0;      // false for inf and NaN
+    const bool skip = guard != 0 && !finite;
+    ctl[0] = sumsq;
+    ctl[1] = norm;
+    ctl[2] = scale;
+    ctl[3] = skip ? 1.0 : 0.0;
+    ctl[4] += 1.0;
+    if (clipped && !skip) ctl[5] += 1.0;
+    if (skip) ctl[6] += 1.0;
+    if ((norm - norm) == 0.0 && norm > ctl[7]) ctl[7] = norm;
+}
+
+extern "C" size_t dg_grad_stats_workspace_bytes(void) { return (size_t)DG_GRAD_STATS_SLOTS * sizeof(double); }
+extern "C" int dg_grad_sumsq_partial(const float* g, size_t n, double* ws, size_t ws_bytes, int slot0, int* slots_used, dg_stream_t stream) {
+    DG_CHECK_ARG(slots_used, "dg_grad_sumsq_partial: null slots_used");
+    *slots_used = 0;
+    if (n == 0) return DG_OK;
+    DG_CHECK_ARG(g && ws, "dg_grad_sumsq_partial: null pointer");
+    DG_CHECK_ARG(((size_t)g & 15) == 0, "dg_grad_sumsq_partial: the gradient must be 16-byte aligned (%p)", (const void*)g);
+    DG_CHECK_ARG(((size_t)ws & 7) == 0, "dg_grad_sumsq_partial: the workspace must be 8-byte aligned (%p)", (void*)ws);
+    DG_CHECK_ARG(slot0 >= 0, "dg_grad_sumsq_partial: first slot %d", slot0);
+    const int grid = flat_grid(n);
+    DG_CHECK_ARG(((size_t)slot0 + (size_t)grid) * sizeof(double) <= ws_bytes,
+                 "dg_grad_sumsq_partial: workspace of %zu bytes too small for slots %d..%ld (dg_grad_stats_workspace_bytes)", ws_bytes, slot0,
+                 (long)slot0 + grid - 1);
+    hipLaunchKernelGGL(grad_sumsq_partial_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, (long)n, ws + slot0);
+    DG_CHECK_LAUNCH("grad_sumsq_partial");
+    *slots_used = grid;
+    return DG_OK;
+}
+extern "C" int dg_grad_clip_finalize(const double* ws, int slots, double pre_scale, double max_norm, int guard, double* ctl,
+                                     dg_stream_t stream) {
+    DG_CHECK_ARG(ctl, "dg_grad_clip_finalize: null ctl");
+    DG_CHECK_ARG(slots >= 0 && slots <= DG_GRAD_STATS_SLOTS && (slots == 0 || ws), "dg_grad_clip_finalize: %d slots (workspace %p)", slots,
+                 (const void*)ws);
+    DG_CHECK_ARG(pre_scale == pre_scale && max_norm == max_norm, "dg_grad_clip_finalize: NaN pre_scale or max_norm");
+    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, slots, pre_scale, max_norm, guard, ctl);
+    DG_CHECK_LAUNCH("grad_clip_finalize");
+    return DG_OK;
+}
+extern "C" int dg_adam_advance_c(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t stream) {
+    DG_CHECK_ARG(state && ctl, "dg_adam_advance_c: null pointer");
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2, ctl);
+    DG_CHECK_LAUNCH("adam_advance_c");
+    return DG_OK;
+}
+// dg_adam_step_flat / _bf16 / _x3 with the gradient scale (float)ctl[2] and the skip flag ctl[3] read on the device.
+// form 0: out unused; 1: out = the bf16 shadow; 3: out = plane 0 of the range, planes plane_elems elements apart.
+extern "C" int dg_adam_step_flat_c(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1, float beta2,
+                                   float eps, float weight_decay, const double* ctl, void* out, int form, size_t plane_elems,
+                                   dg_stream_t stream) {
+    DG_CHECK_ARG(p && g && m && v && state && ctl, "dg_adam_step_flat_c: null pointer");
+    DG_CHECK_ARG(form == 0 || form == 1 || form == 3, "dg_adam_step_flat_c: form %d (0 plain, 1 bf16 shadow, 3 planes)", form);
+    DG_CHECK_ARG(form == 0 || out, "dg_adam_step_flat_c: form %d without an output", form);
+    DG_CHECK_ARG(form != 3 || (plane_elems >= n && plane_elems % 8 == 0), "dg_adam_step_flat_c: plane distance %zu for %zu parameters",
+                 plane_elems, n);
+    if (n == 0) return DG_OK;
+    const dim3 grid(flat_grid(n)), block(256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (form == 0)
+        hipLaunchKernelGGL(adam_step_kernel<0>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
+                           (__bf16*)nullptr, 0L, ctl);
+    else if (form == 1)
+        hipLaunchKernelGGL(adam_step_kernel<1>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
+                           (__bf16*)out, 0L, ctl);
+    else
+        hipLaunchKernelGGL(adam_step_kernel<3>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
+                           (__bf16*)out, (long)plane_elems, ctl);
+    DG_CHECK_LAUNCH("adam_step_c");
     return DG_OK;
 }

@@ -28,6 +28,9 @@ Weight EMA (optim.EMA): ``--ema_decay D`` (0 = off) keeps ``ema = D * ema + (1 -
 generator step from ``--ema_start_iter`` on; every model save also writes ``gen_A_ema_{tag}.pth`` / ``gen_B_ema_{tag}.pth`` (EMA weights, live
 BatchNorm buffers) for ``inference.py --use_ema`` / ``evaluate.py --use_ema``.  ``--ema_samples`` runs the sample-grid and evaluation passes
 on the EMA weights (``trainer.ema_weights()``); the live weights and running statistics are then left exactly as without those passes.
+Gradient control: ``--grad_clip F`` clips every step's gradient to the global norm F, ``--nonfinite_guard`` skips a step whose gradient holds
+an inf or a NaN, ``--log_grad_norm`` only measures; each of them appends `` GRAD: D <norm> G <norm> clipped c/n skipped s`` to the log line.
+All decided on the device (optim.Adam.enable_grad_control); the counters travel in ``train_state_*.pth``.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -96,6 +99,12 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--ema_start_iter", type=int, default=0, help="the first generator step at or after this iteration starts the EMA with a copy")
     p.add_argument("--ema_samples", action="store_true",
                    help="sample grids and evaluation events run on the EMA weights once the EMA has started (eval lines end in ' [ema]')")
+    p.add_argument("--grad_clip", type=float, default=0.0,
+                   help="clip every optimiser step's gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_'s rule; 0 = off)")
+    p.add_argument("--nonfinite_guard", action="store_true",
+                   help="skip an optimiser step whose gradient holds an inf or a NaN (weights, Adam moments and step count stay as they are)")
+    p.add_argument("--log_grad_norm", action="store_true",
+                   help="append ' GRAD: D <norm> G <norm> clipped c/n skipped s' to every log line (implied by the two flags above)")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")

@@ -1085,11 +1085,23 @@ def loss_mix_bwd(gout, nslots, nfm, rate, arch, which):
 
 
 # ---- Adam -----------------------------------------------------------------------------------------------
-def adam_advance(state, lr, beta1, beta2):
+def adam_advance(state, lr, beta1, beta2, ctl=None):
+    """ctl: the step's control block (grad_clip_finalize); a skipped step (ctl[3] != 0) leaves the state untouched."""
+    if ctl is not None:
+        _check_ctl(ctl, "adam_advance")
+        _lib.check(_lib.load().dg_adam_advance_c(_ptr(state), lr, beta1, beta2, _ptr(ctl), _stream()), "dg_adam_advance_c")
+        return
     _lib.check(_lib.load().dg_adam_advance(_ptr(state), lr, beta1, beta2, _stream()), "dg_adam_advance")
 
 
-def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale=1.0, p16=None, p3=None):
+def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale=1.0, p16=None, p3=None, ctl=None):
+    if ctl is not None:     # the gradient scale (float32(ctl[2])) and the skip flag (ctl[3]) are read on the device; grad_scale is unused
+        _check_ctl(ctl, "adam_step_flat")
+        form, out, dist = (3, p3[0], p3[1]) if p3 is not None else ((1, _ptr(p16), 0) if p16 is not None else (0, None, 0))
+        with _hbm("adam", (28.0 + 2.0 * form) * p.numel()):
+            _lib.check(_lib.load().dg_adam_step_flat_c(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2, eps,
+                                                       weight_decay, _ptr(ctl), out, form, dist, _stream()), "dg_adam_step_flat_c")
+        return
     if p3 is not None:      # (plane-0 address of this range, plane distance in elements): the f32x3 plane triples
         with _hbm("adam", 34.0 * p.numel()):
             _lib.check(_lib.load().dg_adam_step_flat_x3(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2,
@@ -1104,6 +1116,46 @@ def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scal
         _lib.check(_lib.load().dg_adam_step_flat(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1,
                                                  beta2,
                                                  eps, weight_decay, grad_scale, _stream()), "dg_adam_step_flat")
+
+
+# ---- gradient norm / clipping / non-finite guard (include/discogan_hip.h: the control block ctl) ---------
+GRAD_STATS_MAX_GRID = 4096          # blocks of one dg_grad_sumsq_partial launch = partial slots of one range at most
+
+
+def _check_ctl(ctl, who):
+    if not (ctl.is_cuda and ctl.dtype == torch.float64 and ctl.dim() == 1 and ctl.numel() >= 8 and ctl.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who}: ctl must be a contiguous float64 HIP tensor of 8 elements")
+
+
+def grad_stats_workspace(device):
+    """The partial-sum workspace of grad_sumsq_partial / grad_clip_finalize (float64 slots)."""
+    return torch.zeros(_lib.load().dg_grad_stats_workspace_bytes() // 8, device=device, dtype=torch.float64)
+
+
+def grad_sumsq_partial(g, ws, slot0=0):
+    """One fp64 partial sum of squares per block of the flat fp32 range ``g`` into ``ws[slot0:]``; returns the number of slots used."""
+    _check_dev(g)
+    if g.dim() != 1 or not g.is_contiguous():
+        raise _lib.DiscoganHipError(f"grad_sumsq_partial: a contiguous 1-D fp32 tensor required, got {tuple(g.shape)}")
+    if not (ws.is_cuda and ws.dtype == torch.float64 and ws.dim() == 1 and ws.is_contiguous()):
+        raise _lib.DiscoganHipError("grad_sumsq_partial: the workspace must be a contiguous float64 HIP tensor")
+    import ctypes as C
+    used = C.c_int(0)
+    with _hbm("gradnorm", 4.0 * g.numel()):
+        _lib.check(_lib.load().dg_grad_sumsq_partial(_ptr(g), g.numel(), _ptr(ws), ws.numel() * 8, int(slot0), C.byref(used), _stream()),
+                   "dg_grad_sumsq_partial")
+    return used.value
+
+
+def grad_clip_finalize(ws, slots, pre_scale, max_norm, guard, ctl):
+    """Fold ``ws[:slots]`` into the control block: ctl[0] sumsq, [1] norm = sqrt(sumsq) * pre_scale, [2] scale = pre_scale * min(1,
+    max_norm / (norm + 1e-6)) (max_norm <= 0: pre_scale), [3] skip = guard and sumsq not finite, [4..7] steps seen / clipped / skipped,
+    largest finite norm."""
+    _check_ctl(ctl, "grad_clip_finalize")
+    if not (ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()) or slots > ws.numel():
+        raise _lib.DiscoganHipError(f"grad_clip_finalize: {slots} slots of a float64 HIP workspace of {ws.numel()}")
+    _lib.check(_lib.load().dg_grad_clip_finalize(_ptr(ws), int(slots), float(pre_scale), float(max_norm), int(bool(guard)), _ptr(ctl),
+                                                 _stream()), "dg_grad_clip_finalize")
 
 
 def _flat_pair(a, b, who):

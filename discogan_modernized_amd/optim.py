@@ -38,6 +38,7 @@ class Adam:
         self.exp_avg_sq = torch.zeros(total, device=dev)
         self.state = torch.zeros(4, device=dev, dtype=torch.float64)
         self.offsets = offs
+        self.ctl = None                                  # enable_grad_control()
         with torch.no_grad():
             for p, off in zip(self.params, offs):
                 n = p.numel()
@@ -79,6 +80,28 @@ class Adam:
             p._dg_x3_ver = p._version
         if convs:
             ops.x3_transpose_planes(self.flat_p3, self.flat_p3t, self._x3t_table)
+
+    def enable_grad_control(self, max_norm=0.0, guard=False):
+        """Measure the global norm of the stepped gradient in every ``step``, clip by it (``max_norm`` > 0, the rule of
+        ``torch.nn.utils.clip_grad_norm_``) and / or skip a step whose gradient holds an inf or a NaN (``guard``).  Allocates the
+        device control block ``ctl`` (8 x float64, layout in include/discogan_hip.h: sumsq, norm, scale, skip, steps seen / clipped /
+        skipped, largest finite norm) and the workspace of the partial sums.  Nothing waits for the host: the Adam kernels read
+        their scale and their go / no-go from ``ctl``."""
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError(f"max_norm must be >= 0 (0 = no clipping), got {max_norm}")
+        self.max_norm, self.guard = max_norm, bool(guard)
+        if self.ctl is None:
+            self.ctl = torch.zeros(8, device=self.flat_p.device, dtype=torch.float64)
+            self._stats_ws = ops.grad_stats_workspace(self.flat_p.device)
+
+    def grad_stats(self):
+        """The control block on the host (waits for the current stream): dict(sumsq, norm, scale, skip, steps, clipped, skipped, max_norm)."""
+        if self.ctl is None:
+            raise RuntimeError("grad_stats(): gradient control is off (enable_grad_control)")
+        c = self.ctl.cpu().tolist()
+        return dict(sumsq=c[0], norm=c[1], scale=c[2], skip=bool(c[3]), steps=int(c[4]), clipped=int(c[5]), skipped=int(c[6]),
+                    max_norm=c[7])
 
     def refresh_derived(self):
         """Recompute everything derived from ``flat_p`` (bf16 shadow, f32x3 plane triples and their transposed copy) after the
@@ -129,26 +152,43 @@ class Adam:
         decay, no moment update.  None = the whole group."""
         g = self.param_groups[0]
         self._sync_foreign_grads()
-        ops.adam_advance(self.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]))
+        ranges = active if active is not None else [(0, self.numel)]
+        ctl = self.ctl
+        if ctl is not None:
+            # with gradient control (enable_grad_control): the norm over the active ranges (the padding between parameters is zero),
+            # one finalize into ctl, then the guarded advance and the guarded, device-scaled update -- all on this stream.
+            # ``grad_scale`` enters the norm, so that it is the norm of the gradient the update sees (data parallel: the average).
+            slots = 0
+            for b, e in ranges:
+                slots += ops.grad_sumsq_partial(self.flat_g[b:e], self._stats_ws, slots)
+            ops.grad_clip_finalize(self._stats_ws, slots, float(grad_scale), self.max_norm, self.guard, ctl)
+        ops.adam_advance(self.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), ctl=ctl)
         p16 = getattr(self, "flat_p16", None)
         p3 = getattr(self, "flat_p3", None)
-        for b, e in (active if active is not None else [(0, self.numel)]):
+        for b, e in ranges:
             ops.adam_step_flat(self.flat_p[b:e], self.flat_g[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], self.state,
                                float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                                float(grad_scale), p16=None if p16 is None else p16[b:e],
-                               p3=None if p3 is None else (p3.data_ptr() + 2 * b, self.numel))
+                               p3=None if p3 is None else (p3.data_ptr() + 2 * b, self.numel), ctl=ctl)
         if p3 is not None and self.flat_p3t is not None:
             ops.x3_transpose_planes(p3, self.flat_p3t, self._x3t_table)
 
     def state_dict(self):
-        return dict(step=self.state[0:1].clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),
-                    param_groups=[{k: v for k, v in self.param_groups[0].items() if k != "params"}])
+        sd = dict(step=self.state[0:1].clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),
+                  param_groups=[{k: v for k, v in self.param_groups[0].items() if k != "params"}])
+        if self.ctl is not None:                         # steps seen / clipped / skipped, largest finite norm
+            sd["grad_control"] = self.ctl[4:8].clone()
+        return sd
 
     def load_state_dict(self, sd):
         self.state.zero_()
         self.state[0:1].copy_(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.ctl is not None:                         # (a state written without gradient control: the counters start at zero)
+            self.ctl.zero_()
+            if "grad_control" in sd:
+                self.ctl[4:8].copy_(sd["grad_control"])
         for k, v in sd["param_groups"][0].items():
             self.param_groups[0][k] = v
 

@@ -42,7 +42,7 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
 
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
-                ema_decay=0.0, ema_start_iter=0)
+                ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False)
 
 
 def check_ema_decay(decay):
@@ -51,6 +51,21 @@ def check_ema_decay(decay):
     if not 0.0 <= decay < 1.0:
         raise ValueError(f"ema_decay must be 0 (off) or in (0, 1), got {decay}")
     return decay
+
+
+def check_grad_clip(grad_clip):
+    """``grad_clip``: 0 = no clipping, else the bound on the global gradient norm of a step.  Returns it as a float."""
+    grad_clip = float(grad_clip)
+    if not grad_clip >= 0.0:
+        raise ValueError(f"grad_clip must be 0 (off) or a positive norm bound, got {grad_clip}")
+    return grad_clip
+
+
+def format_grad_suffix(dis, gen):
+    """The log suffix of gradient control from the two optimisers' ``grad_stats()``: each side's norm of its last step, then the
+    counters of both sides together."""
+    return (f" GRAD: D {dis['norm']:.4e} G {gen['norm']:.4e} clipped {dis['clipped'] + gen['clipped']}/{dis['steps'] + gen['steps']}"
+            f" skipped {dis['skipped'] + gen['skipped']}")
 
 
 def default_args(**over):
@@ -68,6 +83,8 @@ class DiscoGANTrainer:
             if not hasattr(self.args, k):
                 setattr(self.args, k, v)
         ema_decay = check_ema_decay(self.args.ema_decay)
+        grad_clip = check_grad_clip(getattr(self.args, "grad_clip", 0.0))
+        guard, log_norm = bool(getattr(self.args, "nonfinite_guard", False)), bool(getattr(self.args, "log_grad_norm", False))
         self.device = torch.device(device)
         self.image_size = image_size
         self.pg = process_group
@@ -104,6 +121,18 @@ class DiscoGANTrainer:
         # launch behind every generator Adam step from iteration ema_start_iter on -- eagerly on the main stream, never captured.
         # Sampling, evaluation and the gen_*_ema_*.pth checkpoints read it (ema_weights / ema_state_dicts); training never does.
         self.ema = optim.EMA(self.optim_gen, ema_decay) if ema_decay > 0.0 else None
+        # Gradient control (grad_clip > 0, nonfinite_guard or log_grad_norm; optim.Adam.enable_grad_control): every step of either side
+        # measures the global norm of its gradient on the device, clips by it and / or skips the step when the gradient is not finite,
+        # without a host round trip.  A global norm needs the WHOLE gradient before the first Adam slice, so the schedules that step
+        # the generators slice by slice while the backward still runs (_GradBuckets, the split backward of overlap_comm="graph") are
+        # not used then: a G-step is backward, one all-reduce, statistics, step.  The D-step's hand-over to the communication stream
+        # stays.  The norm is taken behind the all-reduce, so every rank decides alike.  A skipped step leaves weights, moments, step
+        # count and derived operand forms untouched; the forward passes of that iteration have run, so BatchNorm running statistics
+        # have moved, and the EMA update behind a skipped G-step runs on unchanged weights (p == ema stays put, else the usual lerp).
+        self.grad_control = grad_clip > 0.0 or guard or log_norm
+        if self.grad_control:
+            self.optim_gen.enable_grad_control(grad_clip, guard)
+            self.optim_dis.enable_grad_control(grad_clip, guard)
         self._graphs = {}
         self._static = None
         # The A-side chain (G_A, D_A) runs on a second HIP stream next to the B-side chain (G_B, D_B):
@@ -216,6 +245,10 @@ class DiscoGANTrainer:
         # bucket is all-reduced (and its Adam slice applied) on the communication stream as soon as the LAST backward
         # pass through its layers has been issued (functional.FINAL_HOOK), while the rest of the backward runs.
         self._buckets = _GradBuckets(self, bucket_mb) if self.overlap_comm else None
+        if self.grad_control and self.world_size > 1 and (self._buckets is not None or self.graph_overlap) and \
+                torch.distributed.get_rank(process_group) == 0:
+            print("gradient control: the global norm needs the whole gradient, so generator steps exchange it as one message behind "
+                  "the backward pass (no bucketed / split-backward overlap); discriminator steps still overlap", flush=True)
         self._eager_until = self.args.update_interval      # first cycle runs eagerly (warm-up)
 
     # ---------------------------------------------------------------------------------------------
@@ -623,7 +656,7 @@ class DiscoGANTrainer:
         opt = self.optim_dis if dstep else self.optim_gen
         if self.graph_overlap:
             return self._train_iteration_graph_overlap(A, B, iters, do_step, need_losses)
-        bucketed = self._buckets is not None and not dstep and do_step and self.xg is not None
+        bucketed = self._buckets is not None and not dstep and do_step and self.xg is not None and not self.grad_control
         if self.time_comm:
             self.comm_steps["D" if dstep else "G"] += 1
         if bucketed:
@@ -640,8 +673,19 @@ class DiscoGANTrainer:
             self._buckets.finish()
             self._ema_update(iters)                           # (finish() made the main stream wait for every bucket's update)
             return out
-        # gradients of the stepped side only: one flat message, summed; the /W rides in the Adam kernel
-        if self.overlap_comm and dstep and do_step:
+        if do_step:
+            self.apply_step(iters)
+        return out
+
+    def apply_step(self, iters):
+        """Exchange + optimiser step + EMA of the side that iteration ``iters`` steps, on the gradients its backward pass left in the
+        flat buffer: ``train_iteration(A, B, iters, do_step=False)`` followed by ``apply_step(iters)`` is a full iteration (with
+        ``do_step=False`` the gradients stay rank-local: the exchange belongs to the step).  One flat message, summed; the 1/W rides
+        in the Adam kernel.  With gradient control the optimiser measures, clips and guards behind the exchange, on the same stream.
+        A D-step of an overlapped schedule runs on the communication stream and is waited for where the discriminators are read."""
+        dstep = self.is_dis_step(iters)
+        opt = self.optim_dis if dstep else self.optim_gen
+        if dstep and (self.overlap_comm or self.graph_overlap):
             main = torch.cuda.current_stream(self.device)
             ev = torch.cuda.Event()
             ev.record(main)
@@ -651,13 +695,11 @@ class DiscoGANTrainer:
                 opt.step(grad_scale=scale, active=self.active_ranges(dstep))
                 self._ev_dis_ready = torch.cuda.Event()
                 self._ev_dis_ready.record(self.comm_stream)
-            return out
+            return
         scale = self._exchange(opt, "D" if dstep else "G")
-        if do_step:
-            opt.step(grad_scale=scale, active=self.active_ranges(dstep))
-            if not dstep:
-                self._ema_update(iters)
-        return out
+        opt.step(grad_scale=scale, active=self.active_ranges(dstep))
+        if not dstep:
+            self._ema_update(iters)
 
     def _ema_update(self, iters):
         """Behind a generator Adam step that is ordered before this point on the current (main) stream."""
@@ -675,33 +717,25 @@ class DiscoGANTrainer:
         if dstep and self._ev_dis_ready is not None:          # (a D-step right behind a D-step: update_interval 1)
             main.wait_event(self._ev_dis_ready)
             self._ev_dis_ready = None
-        self._split_backward, self._dec_done = bool(do_step), False
+        self._split_backward, self._dec_done = bool(do_step) and not self.grad_control, False
         if self.use_graph and iters >= self._eager_until and do_step:
             out = self._fwd_bwd_graphed(A, B, iters, need_losses)
         else:
             out = self._fwd_bwd(A, B, iters, need_losses)
         if not do_step:
             return out
-        if not dstep and not self._dec_done:
-            # the backward was not cut (two-chain schedule): the generators' update is needed by the very next kernel -- main stream
-            scale = self._exchange(opt, "G")
-            opt.step(grad_scale=scale, active=self.active_ranges(dstep))
-            self._ema_update(iters)
+        if dstep or not self._dec_done:
+            # a D-step leaves on the communication stream; a G-step whose backward was not cut (two-chain schedule, gradient control)
+            # is needed by the very next kernel -- main stream
+            self.apply_step(iters)
             return out
         ev = torch.cuda.Event()
         ev.record(main)
         self.comm_stream.wait_event(ev)
         with torch.cuda.stream(self.comm_stream):
-            if dstep:
-                scale = self._exchange(opt, "D")
-                opt.step(grad_scale=scale, active=self.active_ranges(dstep))
-                self._ev_dis_ready = torch.cuda.Event()
-                self._ev_dis_ready.record(self.comm_stream)
-            else:
-                self._exchange_and_step_ranges(opt, self._gen_ranges()[0], "G")      # the encoders: the exposed part
-        if not dstep:
-            main.wait_stream(self.comm_stream)                # the next iteration's first kernels read the generators' weights
-            self._ema_update(iters)                           # ... and so does the EMA: decoders' and encoders' slices are both in
+            self._exchange_and_step_ranges(opt, self._gen_ranges()[0], "G")      # the encoders: the exposed part
+        main.wait_stream(self.comm_stream)                # the next iteration's first kernels read the generators' weights
+        self._ema_update(iters)                           # ... and so does the EMA: decoders' and encoders' slices are both in
         return out
 
     def comm_ms(self):
@@ -790,7 +824,15 @@ class DiscoGANTrainer:
                 f"GEN: {f['gen_loss_A']:.4f}/{f['gen_loss_B']:.4f}, "
                 f"FM: {f['fm_loss_A']:.4f}/{f['fm_loss_B']:.4f}, "
                 f"RECON: {f['recon_loss_A']:.4f}/{f['recon_loss_B']:.4f}, "
-                f"DIS: {f['dis_loss_A']:.4f}/{f['dis_loss_B']:.4f}")
+                f"DIS: {f['dis_loss_A']:.4f}/{f['dis_loss_B']:.4f}" + self.grad_log_suffix())
+
+    def grad_log_suffix(self):
+        """With gradient control: `` GRAD: D {norm} G {norm} clipped {c}/{n} skipped {s}`` from the two control blocks (read here, where
+        the host waits for the losses anyway); without: the empty string."""
+        if not self.grad_control:
+            return ""
+        self.finish()
+        return format_grad_suffix(self.optim_dis.grad_stats(), self.optim_gen.grad_stats())
 
     def state_dicts(self):
         return {k: v.state_dict() for k, v in self.nets.items()}

@@ -336,6 +336,35 @@ int dg_adam_step_flat(float* p, const float* g, float* m, float* v, size_t n, co
 int dg_ema_update_flat(float* ema, const float* p, size_t n, float w, dg_stream_t s);
 int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t s);
 
+/* ---- Gradient norm, clipping by it and the non-finite guard of an Adam step (optim.Adam.enable_grad_control) --------------------
+ * Everything stays on the device and on one stream: partials of every stepped flat range, one finalize, then the *_c forms of the Adam
+ * entry points, which take their gradient scale and their go / no-go from the control block the finalize wrote.
+ *
+ * dg_grad_sumsq_partial: sum of squares of g[0..n), every element widened to double BEFORE it is squared (an exact product, so a finite
+ *   fp32 gradient can neither overflow nor underflow the sum: only inf / NaN elements make it non-finite).  Grid of at most 4096 blocks
+ *   x 256 threads, 4 elements (16 bytes) per thread and trip, a tail of n % 4 elements by one thread; block b writes ONE fp64 partial
+ *   to ws[slot0 + b].  No atomics, fixed summation order: the same input gives the same bits on every run.  *slots_used = blocks
+ *   launched (n == 0: none, nothing is launched).  g 16-byte aligned; (slot0 + blocks) * 8 <= ws_bytes.  Ranges of one step use
+ *   consecutive slots: slot0 of the next call = slot0 + *slots_used.  dg_grad_stats_workspace_bytes() holds four full-grid ranges.
+ * dg_grad_clip_finalize: one workgroup sums ws[0..slots) in a fixed order and writes ctl (device, 8 x float64):
+ *   [0] sumsq   [1] norm = sqrt(sumsq) * pre_scale   [2] scale = pre_scale * min(1, max_norm / (norm + 1e-6))   [3] skip (0 / 1)
+ *   [4] steps seen   [5] steps clipped   [6] steps skipped   [7] largest finite norm seen        ([4..7] accumulate: zero them once)
+ *   pre_scale is the factor the step would have passed as grad_scale (data parallel: 1 / world size behind a SUM all-reduce, so norm
+ *   is the norm of the averaged gradient).  max_norm <= 0: no clipping, scale = pre_scale.  The coefficient is
+ *   torch.nn.utils.clip_grad_norm_'s; with error_if_nonfinite=False semantics when guard == 0: an infinite norm gives scale 0, a NaN
+ *   norm a NaN scale, and the step is taken.  guard != 0: skip = !isfinite(sumsq).
+ * dg_adam_advance_c: dg_adam_advance, but state is left untouched when ctl[3] != 0.
+ * dg_adam_step_flat_c: dg_adam_step_flat (form 0) / _bf16 (form 1, out = the shadow) / _x3 (form 3, out = plane 0, plane_elems apart)
+ *   with grad_scale = (float)ctl[2]; when ctl[3] != 0 every thread returns before its first load: p, m, v, the shadow and the planes
+ *   keep their bits.  A step that is taken is bitwise the host-scaled entry point called with grad_scale = (float)ctl[2]. */
+size_t dg_grad_stats_workspace_bytes(void);
+int dg_grad_sumsq_partial(const float* g, size_t n, double* ws, size_t ws_bytes, int slot0, int* slots_used, dg_stream_t s);
+int dg_grad_clip_finalize(const double* ws, int slots, double pre_scale, double max_norm, int guard, double* ctl, dg_stream_t s);
+int dg_adam_advance_c(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t s);
+int dg_adam_step_flat_c(float* p, const float* g, float* m, float* v, size_t n, const double* state,
+                        float beta1, float beta2, float eps, float weight_decay, const double* ctl,
+                        void* out, int form, size_t plane_elems, dg_stream_t s);
+
 /* nn.BCELoss against a target TENSOR (image_translation.py:157-166 materialises ones / zeros label tensors);
  * same -100 log clamp and 1e-12 backward guard as dg_bce_fwd/_bwd.  p, target: [n]. */
 int dg_bce_target_fwd(const float* p, const float* target, int n, float* loss, dg_stream_t s);
