@@ -34,17 +34,15 @@ static inline bool dg_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline size_t dg_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int dg_get_option(int idx);
-// Arithmetic of the conv products (DG_PREC_*) for the launchers of the 3-channel edge kernels (edge.hip, and their entry points at the
-// end of igemm.hip): the `prec` argument of a *_g / *_p entry point there, held in a thread-local for the duration of that call
-// (DgPrecScope); without a scope, the process default dg_set_option("bf16", n).  The interior convs (igemm.hip's planner and launch path)
-// do not read it: they take the arithmetic as an argument.
-int dg_cur_prec();
-struct DgPrecScope {
-    int old;
-    explicit DgPrecScope(int prec);
-    ~DgPrecScope();
-};
 enum { DG_OPT_SPLITK = 0, DG_OPT_KT = 1, DG_OPT_TARGET_WGS = 2, DG_OPT_RESERVED = 3, DG_OPT_SPLIT_BELOW = 4, DG_OPT_POINTER_PATH = 5, DG_OPT_BF16 = 6, DG_OPT_DBG_ZERO = 7, DG_OPT_NO_DMA = 8, DG_OPT_DMA_MFMA = 9, DG_OPT_X3_MFMA = 10, DG_OPT_DGW_PERSIST = 11, DG_OPT_UNDERSTORY = 12, DG_OPT_BN_ITEMS = 13, DG_OPT_COUNT = 14 };
+// Arithmetic of the conv products (DG_PREC_*): an argument all the way down.  DG_PREC_DEFAULT -> the process default
+// dg_set_option("bf16", n), resolved once, where a call enters the library (the `prec` of a *_p / *_g entry point; the forms without one
+// pass DG_PREC_DEFAULT).  Nothing below an entry point reads the option, and no per-thread state carries it.
+static inline int dg_resolve_prec(int prec) { return prec >= 0 ? prec : dg_get_option(DG_OPT_BF16); }
+// The tiled 3 -> K forward (igemm.hip, MODE_FWD_C3; wide: the 128-channel tile for K > 64): the form behind edge.hip's streaming kernels.
+// Arguments are validated by the caller, which also collects the launch status.
+__attribute__((visibility("hidden"))) void dg_c3_fwd_tiled(const float* x_nchw, const float* w, float* y_nhwc, int N, int H, int W, int K, int act,
+                                                           float slope, bool wide, hipStream_t st);
 
 // ---- grouped launches (round 4): one tensor per problem, picked by a block index (wave-uniform: scalar loads) ------------------
 struct DgPtrs {

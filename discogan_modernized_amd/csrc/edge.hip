@@ -1,7 +1,9 @@
 // 3-channel edge layers, image side NCHW (the reference hands over / receives NCHW images:
-// image_translation.py:332-333, model.py:8,80,142): the 3 -> K forward for K == 64 (the tiled MODE_FWD_C3 path
-// in igemm.hip is the fallback for other K), the K -> 3 direction and the [K][3][4][4] weight gradient.
+// image_translation.py:332-333, model.py:8,80,142): the 3 -> K forward, the K -> 3 direction and the [K][3][4][4] weight gradient,
+// with every dg_conv4x4s2_c3_* entry point.  The forward kernels here take K == 64; for other K the forward calls the tiled
+// MODE_FWD_C3 kernel of igemm.hip (dg_c3_fwd_tiled), the one thing this file needs from another.
 // All are HBM-bound (AI ~ 20 FLOP/B); the hot kernels feed the matrix cores so the VALU stays free.
+// Host side: "one call record per op" below.
 //
 //   c3_fwd (K == 64): a wave owns groups of 32 consecutive output pixels; MFMA operands gathered straight from
 //       the NCHW image with range-checked buffer loads (no LDS, no barriers after the weights are staged).
@@ -387,112 +389,149 @@ __global__ __launch_bounds__(256, 2) void c3_dgrad_scatter_kernel(const DgPtrs d
 }
 
 extern "C" size_t dg_c3_dgrad_workspace_bytes(int K) { return K == CD_K ? (size_t)CD_NK * 16 * sizeof(float) : 0; }
-// groups > 1 (dg_conv4x4s2_c3_dgrad_g): the scatter form only (K == 64, fp32 dy)
-static int c3_dgrad_run(int groups, const float* const* dy_nhwc, int dy_bf16, const float* const* w, float* const* dx_nchw, int N, int H, int W, int K,
-                        int act, void* ws, size_t ws_bytes, dg_stream_t stream, const void* act_out = nullptr, float slope = 0.f);
+
+// ---- host side: one call record per op ------------------------------------------------------------------------------------------------
+// Every entry point of this file describes its call in a C3Fwd / C3Dgrad / C3Wgrad on its stack and hands it to c3_fwd / c3_dgrad /
+// c3_wgrad.  That function validates once, names the kernel form (a pure function of the record and the named options) and launches it.
+// `prec` in a record is resolved (DG_PREC_F32 | DG_PREC_BF16 | DG_PREC_F32X3, dg_resolve_prec at the entry point): nothing below an
+// entry point reads the process default.  Pointer members hold one pointer per problem (`groups` of them).
+//
+// A template argument chosen at run time: f(std::true_type{} | std::false_type{}), f(std::integral_constant<int, DG_ACT_*>{}).
+using C3Yes = std::true_type;
+using C3No = std::false_type;
+template <typename F> static void c3_with_flag(bool b, F&& f) { if (b) f(C3Yes{}); else f(C3No{}); }
+template <typename F> static void c3_with_fwd_act(int act, F&& f) {
+    if (act == DG_ACT_LEAKY) f(std::integral_constant<int, DG_ACT_LEAKY>{});
+    else if (act == DG_ACT_RELU) f(std::integral_constant<int, DG_ACT_RELU>{});
+    else f(std::integral_constant<int, DG_ACT_NONE>{});
+}
+#define C3_CHECK_PREC(who, prec) DG_CHECK_ARG((prec) >= DG_PREC_DEFAULT && (prec) <= DG_PREC_F32X3, who ": prec=%d", prec)
+
+struct C3Dgrad {
+    const char* who;                        // the entry point's public name, for messages
+    int groups;
+    bool grouped;                           // the *_g entry point: exists for the scatter kernel's K, and not under option "kt" 16
+    const void *const *dy, *const *w;
+    void* const* dx;
+    int dy_bf16, N, H, W, K, act, prec;
+    const void* act_out;                    // fused LeakyReLU backward on dy (one problem): the layer's saved output, nullptr: none,
+    float slope;                            // and its slope
+    void* ws;                               // the gather form's weight image
+    size_t ws_bytes;
+    hipStream_t st;
+};
+// one problem, nothing fused: an entry point overwrites what it differs in
+static C3Dgrad c3_dgrad_call(const char* who, const void* const* dy, int dy_bf16, const float* const* w, float* const* dx, int N, int H, int W, int K,
+                             int act, int prec, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    C3Dgrad c = C3Dgrad();
+    c.who = who; c.groups = 1; c.dy = dy; c.dy_bf16 = dy_bf16; c.w = (const void* const*)w; c.dx = (void* const*)dx;
+    c.N = N; c.H = H; c.W = W; c.K = K; c.act = act; c.prec = dg_resolve_prec(prec);
+    c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    return c;
+}
+static int c3_dgrad(const C3Dgrad& c);
 extern "C" int dg_conv4x4s2_c3_dgrad(const float* dy_nhwc, const float* w, float* dx_nchw, int N, int H, int W, int K,
                                      int act, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return c3_dgrad_run(1, &dy_nhwc, 0, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream);
+    return c3_dgrad(c3_dgrad_call("dg_conv4x4s2_c3_dgrad", (const void* const*)&dy_nhwc, 0, &w, &dx_nchw, N, H, W, K, act, DG_PREC_DEFAULT, ws, ws_bytes,
+                                  stream));
 }
 extern "C" int dg_conv4x4s2_c3_dgrad_t(const void* dy_nhwc, int dy_bf16, const float* w, float* dx_nchw, int N, int H, int W, int K,
                                        int act, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    const float* dyp = (const float*)dy_nhwc;
-    return c3_dgrad_run(1, &dyp, dy_bf16, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream);
+    return c3_dgrad(c3_dgrad_call("dg_conv4x4s2_c3_dgrad_t", &dy_nhwc, dy_bf16, &w, &dx_nchw, N, H, W, K, act, DG_PREC_DEFAULT, ws, ws_bytes, stream));
 }
 extern "C" int dg_conv4x4s2_c3_dgrad_p(const void* dy_nhwc, int dy_bf16, const float* w, float* dx_nchw, int N, int H, int W, int K,
                                        int act, int prec, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_dgrad_p: prec=%d", prec);
-    DgPrecScope scope(prec);
-    const float* dyp = (const float*)dy_nhwc;
-    return c3_dgrad_run(1, &dyp, dy_bf16, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream);
-}
-// The scatter form takes dy up to 2^31 bytes (32-bit offsets into one buffer descriptor), counted in dy's own element size.
-static bool c3_dgrad_scatter_fits(int N, int H, int W, int K, int dy_bf16) {
-    return K == CD_K && N >= 1 && (long)N * (H / 2) * (W / 2) * CD_K * (dy_bf16 ? 2 : 4) < (1L << 31);
-}
-// 1 when the fused form below exists for this problem under the options in force: the scatter kernel (K == 64, dy under 2^31 bytes,
-// option "kt" != 16).  Past that size the input-gradient runs on the VALU kernel, which has no fused activation backward.
-extern "C" int dg_c3_dgrad_act_ok(int N, int H, int W, int K, int dy_bf16) {
-    return c3_dgrad_scatter_fits(N, H, W, K, dy_bf16) && dg_get_option(DG_OPT_KT) != 16 ? 1 : 0;
+    C3_CHECK_PREC("dg_conv4x4s2_c3_dgrad_p", prec);
+    return c3_dgrad(c3_dgrad_call("dg_conv4x4s2_c3_dgrad_p", &dy_nhwc, dy_bf16, &w, &dx_nchw, N, H, W, K, act, prec, ws, ws_bytes, stream));
 }
 // conv1's input-gradient with the backward of the layer's fused LeakyReLU applied to dy in the load path: dx = dgrad(dy * (act_out > 0 ? 1 : slope))
 extern "C" int dg_conv4x4s2_c3_dgrad_act_p(const void* dy_nhwc, int dy_bf16, const void* act_out, int in_act, float slope, const float* w, float* dx_nchw,
                                            int N, int H, int W, int K, int act, int prec, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_dgrad_act_p: prec=%d", prec);
+    C3_CHECK_PREC("dg_conv4x4s2_c3_dgrad_act_p", prec);
     DG_CHECK_ARG(act_out && in_act == DG_ACT_LEAKY, "dg_conv4x4s2_c3_dgrad_act_p: needs the saved output of a fused LeakyReLU (in_act=%d)", in_act);
-    DG_CHECK_ARG(dg_c3_dgrad_act_ok(N, H, W, K, dy_bf16), "dg_conv4x4s2_c3_dgrad_act_p: the fused form is the scatter kernel (K == 64, dy under 2^31 bytes, option kt != 16)");
-    DgPrecScope scope(prec);
-    const float* dyp = (const float*)dy_nhwc;
-    return c3_dgrad_run(1, &dyp, dy_bf16, &w, &dx_nchw, N, H, W, K, act, ws, ws_bytes, stream, act_out, slope);
+    C3Dgrad c = c3_dgrad_call("dg_conv4x4s2_c3_dgrad_act_p", &dy_nhwc, dy_bf16, &w, &dx_nchw, N, H, W, K, act, prec, ws, ws_bytes, stream);
+    c.act_out = act_out; c.slope = slope;
+    return c3_dgrad(c);
 }
 extern "C" int dg_conv4x4s2_c3_dgrad_g(int groups, const float* const* dy_nhwc, const float* const* w, float* const* dx_nchw, int N, int H, int W, int K,
                                        int act, int prec, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && dy_nhwc && w && dx_nchw, "dg_conv4x4s2_c3_dgrad_g: bad group / null table");
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_dgrad_g: prec=%d", prec);
-    DG_CHECK_ARG(K == CD_K && dg_get_option(DG_OPT_KT) != 16, "dg_conv4x4s2_c3_dgrad_g: the grouped form is the scatter kernel (K == 64)");
-    DgPrecScope scope(prec);
-    return c3_dgrad_run(groups, dy_nhwc, 0, w, dx_nchw, N, H, W, K, act, nullptr, 0, stream);
+    C3_CHECK_PREC("dg_conv4x4s2_c3_dgrad_g", prec);
+    C3Dgrad c = c3_dgrad_call("dg_conv4x4s2_c3_dgrad_g", (const void* const*)dy_nhwc, 0, w, dx_nchw, N, H, W, K, act, prec, nullptr, 0, stream);
+    c.groups = groups; c.grouped = true;
+    return c3_dgrad(c);
 }
-static int c3_dgrad_run(int groups, const float* const* dy_tab, int dy_bf16, const float* const* w_tab, float* const* dx_tab, int N, int H, int W, int K,
-                        int act, void* ws, size_t ws_bytes, dg_stream_t stream, const void* act_out, float slope) {
-    DG_CHECK_ARG(act_out == nullptr || groups == 1, "dg_conv4x4s2_c3_dgrad: the fused activation backward takes one problem");
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(dy_tab[i] && w_tab[i] && dx_tab[i], "dg_conv4x4s2_c3_dgrad: null pointer");
-    const float* dy_nhwc = dy_tab[0];
-    const float* w = w_tab[0];
-    float* dx_nchw = dx_tab[0];
-    DG_CHECK_ARG(!dy_bf16 || (K == CD_K && dg_get_option(DG_OPT_KT) != 16), "dg_conv4x4s2_c3_dgrad_t: a bf16 dy needs K == 64 (scatter form)");
-    DG_CHECK_ARG(N >= 1 && K >= 4 && K % 4 == 0, "dg_conv4x4s2_c3_dgrad: bad N/K (%d,%d)", N, K);
-    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "dg_conv4x4s2_c3_dgrad: H,W must be powers of two");
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_SIGMOID, "dg_conv4x4s2_c3_dgrad: bad act %d", act);
-    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "dg_conv4x4s2_c3_dgrad: tensor too large");
-    hipStream_t st = (hipStream_t)stream;
-    const int Ho = H / 2, Wo = W / 2;
-    if (c3_dgrad_scatter_fits(N, H, W, K, dy_bf16)) {
-        if (dg_get_option(DG_OPT_KT) != 16) {       // scatter form (dense GEMM + overlap-add); "kt" 16 keeps the gather form testable
-            const int tiles_r = (Ho + CS_TR - 1) / CS_TR, tiles_c = (Wo + CS_TC - 1) / CS_TC;
-            const long ntiles = (long)N * tiles_r * tiles_c;
-            DG_CHECK_ARG(ntiles < (1L << 30), "dg_conv4x4s2_c3_dgrad: too many tiles");
-            const dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512), groups);
-            const DgPtrs pd = dg_ptrs((const void* const*)dy_tab, groups), pw = dg_ptrs((const void* const*)w_tab, groups),
-                         px = dg_ptrs((const void* const*)dx_tab, groups);
-            const DgPtrs pa = dg_ptrs1(act_out ? act_out : (const void*)dy_tab[0]);
-            const unsigned dyb = (unsigned)((long)N * Ho * Wo * CD_K * (dy_bf16 ? 2 : 4));
-#define C3_SCATTER(...) hipLaunchKernelGGL((c3_dgrad_scatter_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, pd, pw, px, N, H, W, act, tiles_r, tiles_c, (int)ntiles, dyb, pa, slope)
-            if (dy_bf16 && dg_cur_prec() == 1) {      // bf16 matrix path: bf16 MFMA
-                if (act_out) C3_SCATTER(true, true, false, true); else C3_SCATTER(true, true);
-            } else if (dy_bf16) {
-                if (act_out) C3_SCATTER(true, false, false, true); else C3_SCATTER(true, false);
-            } else if (dg_cur_prec() == 2) {          // f32x3 path: fp32-accurate products on the bf16 MFMA
-                if (act_out) C3_SCATTER(false, false, true, true); else C3_SCATTER(false, false, true);
-            } else {
-                if (act_out) C3_SCATTER(false, false, false, true); else C3_SCATTER(false, false);
-            }
-#undef C3_SCATTER
-            DG_CHECK_LAUNCH("c3_dgrad_scatter");
-            return DG_OK;
-        }
-        DG_CHECK_ARG(groups == 1 && !act_out, "dg_conv4x4s2_c3_dgrad: the gather form takes one problem and no fused activation backward");
-        DG_CHECK_ARG(!dy_bf16, "dg_conv4x4s2_c3_dgrad: the gather form reads an fp32 dy (a bf16 dy needs the scatter form)");
+
+// The scatter form takes dy up to 2^31 bytes (32-bit offsets into one buffer descriptor), counted in dy's own element size.
+static bool c3_dgrad_scatter_fits(int N, int H, int W, int K, int dy_bf16) {
+    return K == CD_K && N >= 1 && (long)N * (H / 2) * (W / 2) * CD_K * (dy_bf16 ? 2 : 4) < (1L << 31);
+}
+// 1 when the fused form (dg_conv4x4s2_c3_dgrad_act_p) exists for this problem under the options in force: the scatter kernel (K == 64,
+// dy under 2^31 bytes, option "kt" != 16).  Past that size the input-gradient runs on the VALU kernel, which has no fused activation backward.
+extern "C" int dg_c3_dgrad_act_ok(int N, int H, int W, int K, int dy_bf16) {
+    return c3_dgrad_scatter_fits(N, H, W, K, dy_bf16) && dg_get_option(DG_OPT_KT) != 16 ? 1 : 0;
+}
+// scatter: dense GEMM + overlap-add (its operand variants: dy type x arithmetic x fused activation backward); gather: the form it
+// replaced, kept testable under option "kt" 16; VALU: any K % 4 == 0 and any size
+enum C3DgradForm { C3_DGRAD_SCATTER, C3_DGRAD_GATHER, C3_DGRAD_VALU };
+static C3DgradForm c3_dgrad_form(const C3Dgrad& c) {
+    if (!c3_dgrad_scatter_fits(c.N, c.H, c.W, c.K, c.dy_bf16)) return C3_DGRAD_VALU;
+    return dg_get_option(DG_OPT_KT) != 16 ? C3_DGRAD_SCATTER : C3_DGRAD_GATHER;
+}
+static int c3_dgrad(const C3Dgrad& c) {
+    const int N = c.N, H = c.H, W = c.W, K = c.K, Ho = H / 2, Wo = W / 2;
+    DG_CHECK_ARG(c.groups >= 1 && c.groups <= DG_MAX_GROUPS && c.dy && c.w && c.dx, "%s: bad group / null table", c.who);
+    for (int i = 0; i < c.groups; ++i) DG_CHECK_ARG(c.dy[i] && c.w[i] && c.dx[i], "%s: null pointer", c.who);
+    DG_CHECK_ARG(!c.grouped || (K == CD_K && dg_get_option(DG_OPT_KT) != 16), "%s: the grouped form is the scatter kernel (K == 64, option kt != 16)", c.who);
+    DG_CHECK_ARG(!c.dy_bf16 || (K == CD_K && dg_get_option(DG_OPT_KT) != 16), "%s: a bf16 dy needs K == 64 (scatter form)", c.who);
+    DG_CHECK_ARG(N >= 1 && K >= 4 && K % 4 == 0, "%s: bad N/K (%d,%d)", c.who, N, K);
+    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "%s: H,W must be powers of two", c.who);
+    DG_CHECK_ARG(c.act == DG_ACT_NONE || c.act == DG_ACT_SIGMOID, "%s: bad act %d", c.who, c.act);
+    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "%s: tensor too large", c.who);      // so tile counts stay far below 2^31 as well
+    const C3DgradForm form = c3_dgrad_form(c);
+    if (form != C3_DGRAD_SCATTER) {
+        DG_CHECK_ARG(c.groups == 1 && !c.act_out, "%s: several problems and the fused form are the scatter kernel (K == 64, dy under 2^31 bytes, option kt != 16)",
+                     c.who);
+        DG_CHECK_ARG(!c.dy_bf16, "%s: the VALU form reads an fp32 dy (a bf16 dy of %ld bytes is past the scatter form's 2^31)", c.who, (long)N * Ho * Wo * K * 2);
+    }
+    switch (form) {
+    case C3_DGRAD_SCATTER: {
+        const int tiles_r = (Ho + CS_TR - 1) / CS_TR, tiles_c = (Wo + CS_TC - 1) / CS_TC;
+        const long ntiles = (long)N * tiles_r * tiles_c;
+        const dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512), c.groups);
+        const DgPtrs pd = dg_ptrs(c.dy, c.groups), pw = dg_ptrs(c.w, c.groups), px = dg_ptrs(c.dx, c.groups);
+        const DgPtrs pa = dg_ptrs1(c.act_out ? c.act_out : c.dy[0]);
+        const unsigned dyb = (unsigned)((long)N * Ho * Wo * CD_K * (c.dy_bf16 ? 2 : 4));
+        auto scatter = [&](auto IN16, auto MF16, auto X3) {      // bf16 dy, on the bf16 MFMA, fp32 dy as three bf16 pieces
+            c3_with_flag(c.act_out != nullptr, [&](auto FACT) {
+                hipLaunchKernelGGL((c3_dgrad_scatter_kernel<decltype(IN16)::value, decltype(MF16)::value, decltype(X3)::value, decltype(FACT)::value>), grid,
+                                   dim3(256), 0, c.st, pd, pw, px, N, H, W, c.act, tiles_r, tiles_c, (int)ntiles, dyb, pa, c.slope);
+            });
+        };
+        if (c.dy_bf16 && c.prec == DG_PREC_BF16) scatter(C3Yes{}, C3Yes{}, C3No{});
+        else if (c.dy_bf16) scatter(C3Yes{}, C3No{}, C3No{});
+        else if (c.prec == DG_PREC_F32X3) scatter(C3No{}, C3No{}, C3Yes{});
+        else scatter(C3No{}, C3No{}, C3No{});
+        break;
+    }
+    case C3_DGRAD_GATHER: {
         const int tiles_r = (Ho + CD_TR - 1) / CD_TR, tiles_c = (Wo + CD_TC - 1) / CD_TC;
         const long ntiles = (long)N * tiles_r * tiles_c;
-        DG_CHECK_ARG(ntiles < (1L << 31), "dg_conv4x4s2_c3_dgrad: too many tiles");
-        if (ws == nullptr || ws_bytes < dg_c3_dgrad_workspace_bytes(K))
-            return dg_fail(DG_ERR_WORKSPACE, "dg_conv4x4s2_c3_dgrad: workspace %zu < %zu", ws_bytes, dg_c3_dgrad_workspace_bytes(K));
-        hipLaunchKernelGGL(c3_wq_build_kernel, dim3((CD_NK * 16 + 255) / 256), dim3(256), 0, st, w, (float*)ws);
+        if (c.ws == nullptr || c.ws_bytes < dg_c3_dgrad_workspace_bytes(K))
+            return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < %zu", c.who, c.ws_bytes, dg_c3_dgrad_workspace_bytes(K));
+        hipLaunchKernelGGL(c3_wq_build_kernel, dim3((CD_NK * 16 + 255) / 256), dim3(256), 0, c.st, (const float*)c.w[0], (float*)c.ws);
         DG_CHECK_LAUNCH("c3_wq_build");
-        const int grid = (int)(ntiles < 512 ? ntiles : 512);
-        hipLaunchKernelGGL(c3_dgrad_mfma_kernel, dim3(grid), dim3(256), 0, st, dy_nhwc, (const float*)ws, dx_nchw, N, H, W, act,
-                           tiles_r, tiles_c, (int)ntiles);
-        DG_CHECK_LAUNCH("c3_dgrad_mfma");
-        return DG_OK;
+        hipLaunchKernelGGL(c3_dgrad_mfma_kernel, dim3((unsigned)(ntiles < 512 ? ntiles : 512)), dim3(256), 0, c.st, (const float*)c.dy[0], (const float*)c.ws,
+                           (float*)c.dx[0], N, H, W, c.act, tiles_r, tiles_c, (int)ntiles);
+        break;
     }
-    DG_CHECK_ARG(groups == 1 && !act_out, "dg_conv4x4s2_c3_dgrad: the VALU form takes one problem and no fused activation backward");
-    DG_CHECK_ARG(!dy_bf16, "dg_conv4x4s2_c3_dgrad: the VALU form reads an fp32 dy (a bf16 dy of %ld bytes is past the scatter form's 2^31)",
-                 (long)N * Ho * Wo * K * 2);
-    const long nquad = (long)N * Ho * Wo;
-    hipLaunchKernelGGL(c3_dgrad_valu_kernel, dim3((unsigned)((nquad + 255) / 256)), dim3(256), 0, st, dy_nhwc, w,
-                       dx_nchw, N, H, W, K, dg_ilog2(Ho), dg_ilog2(Wo), act);
-    DG_CHECK_LAUNCH("c3_dgrad_valu");
+    case C3_DGRAD_VALU: {
+        const long nquad = (long)N * Ho * Wo;
+        hipLaunchKernelGGL(c3_dgrad_valu_kernel, dim3((unsigned)((nquad + 255) / 256)), dim3(256), 0, c.st, (const float*)c.dy[0], (const float*)c.w[0],
+                           (float*)c.dx[0], N, H, W, K, dg_ilog2(Ho), dg_ilog2(Wo), c.act);
+        break;
+    }
+    }
+    DG_CHECK_LAUNCH(c.who);
     return DG_OK;
 }
 
@@ -768,98 +807,124 @@ __global__ __launch_bounds__(256, 2) void c3_fwd_bf16mfma_kernel(const DgPtrs xs
     }
 }
 
-// f32x3 path: conv1 forward (+ fused activation) that ALSO writes the plane triple of its output (see PL above).
+// ---- forward: entry points, form, launch ------------------------------------------------------------------------------------------
+struct C3Fwd {
+    const char* who;
+    int groups;
+    bool streaming_only;                    // the grouped and the plane-writing entry points: no tiled form behind them
+    const void *const *x, *const *w;
+    void* const* y;
+    void* planes;                           // the plane-writing form (one problem): the bf16 plane triple of y as well (PL above),
+    size_t plane_elems;                     // elements from one plane to the next
+    int y_bf16, N, H, W, K, act, prec;
+    float slope;
+    hipStream_t st;
+};
+// one problem, fp32 output, tiled form allowed: an entry point overwrites what it differs in
+static C3Fwd c3_fwd_call(const char* who, const float* const* x, const float* const* w, void* const* y, int y_bf16, int N, int H, int W, int K, int act,
+                         float slope, int prec, dg_stream_t stream) {
+    C3Fwd c = C3Fwd();
+    c.who = who; c.groups = 1; c.x = (const void* const*)x; c.w = (const void* const*)w; c.y = y; c.y_bf16 = y_bf16;
+    c.N = N; c.H = H; c.W = W; c.K = K; c.act = act; c.slope = slope; c.prec = dg_resolve_prec(prec); c.st = (hipStream_t)stream;
+    return c;
+}
+static int c3_fwd(const C3Fwd& c);
+extern "C" int dg_conv4x4s2_c3_fwd(const float* x_nchw, const float* w, float* y_nhwc, int N, int H, int W, int K,
+                                   int act, float slope, dg_stream_t stream) {
+    return c3_fwd(c3_fwd_call("dg_conv4x4s2_c3_fwd", &x_nchw, &w, (void* const*)&y_nhwc, 0, N, H, W, K, act, slope, DG_PREC_DEFAULT, stream));
+}
+extern "C" int dg_conv4x4s2_c3_fwd_t(const float* x_nchw, const float* w, void* y_nhwc, int y_bf16, int N, int H, int W, int K,
+                                     int act, float slope, dg_stream_t stream) {
+    return c3_fwd(c3_fwd_call("dg_conv4x4s2_c3_fwd_t", &x_nchw, &w, &y_nhwc, y_bf16, N, H, W, K, act, slope, DG_PREC_DEFAULT, stream));
+}
+extern "C" int dg_conv4x4s2_c3_fwd_p(const float* x_nchw, const float* w, void* y_nhwc, int y_bf16, int N, int H, int W, int K,
+                                     int act, float slope, int prec, dg_stream_t stream) {
+    C3_CHECK_PREC("dg_conv4x4s2_c3_fwd_p", prec);
+    return c3_fwd(c3_fwd_call("dg_conv4x4s2_c3_fwd_p", &x_nchw, &w, &y_nhwc, y_bf16, N, H, W, K, act, slope, prec, stream));
+}
+// grouped form: the K == 64 streaming kernels only (the network's first conv / last transposed conv)
+extern "C" int dg_conv4x4s2_c3_fwd_g(int groups, const float* const* x_nchw, const float* const* w, float* const* y_nhwc, int N, int H, int W, int K,
+                                     int act, float slope, int prec, dg_stream_t stream) {
+    C3_CHECK_PREC("dg_conv4x4s2_c3_fwd_g", prec);
+    C3Fwd c = c3_fwd_call("dg_conv4x4s2_c3_fwd_g", x_nchw, w, (void* const*)y_nhwc, 0, N, H, W, K, act, slope, prec, stream);
+    c.groups = groups; c.streaming_only = true;
+    return c3_fwd(c);
+}
+// f32x3 path: conv1 forward (+ fused activation) that ALSO writes the plane triple of its output
 extern "C" int dg_conv4x4s2_c3_fwd_x3(const float* x_nchw, const float* w, float* y_nhwc, void* y_planes, size_t plane_elems, int N, int H,
                                       int W, int K, int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(x_nchw && w && y_nhwc && y_planes, "dg_conv4x4s2_c3_fwd_x3: null pointer");
-    DG_CHECK_ARG(K == CF_K, "dg_conv4x4s2_c3_fwd_x3: K must be %d", CF_K);
-    DG_CHECK_ARG(N >= 1 && dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "dg_conv4x4s2_c3_fwd_x3: H, W must be powers of two");
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "dg_conv4x4s2_c3_fwd_x3: bad act %d", act);
-    const int Ho = H / 2, Wo = W / 2;
-    const long npix = (long)N * Ho * Wo;
-    DG_CHECK_ARG((long)N * 3 * H * W * 4 < (1L << 30) && npix < (1L << 30), "dg_conv4x4s2_c3_fwd_x3: tensors must be below 1 GiB");
-    DG_CHECK_ARG(plane_elems >= (size_t)npix * CF_K && plane_elems % 8 == 0, "dg_conv4x4s2_c3_fwd_x3: plane distance %zu for %ld elements", plane_elems, npix * CF_K);
-    const long ngroups = (npix + 31) / 32;
-    long wgs = (ngroups + 31) / 32;
-    if (wgs > 4096) wgs = 4096;
-    if (wgs < 1) wgs = 1;
-    hipStream_t st = (hipStream_t)stream;
-#define CFPL_LAUNCH(ACT)                                                                                                          \
-    hipLaunchKernelGGL((c3_fwd_bf16mfma_kernel<ACT, false, true, true>), dim3((unsigned)wgs), dim3(256), 0, st, dg_ptrs1(x_nchw), dg_ptrs1(w), dg_ptrs1(y_nhwc), N, H, W, \
-                       dg_ilog2(Ho), dg_ilog2(Wo), npix, (int)ngroups, slope, (int)((long)N * 3 * H * W * 4), (__bf16*)y_planes, (long)plane_elems)
-    if (act == DG_ACT_LEAKY) { CFPL_LAUNCH(DG_ACT_LEAKY); }
-    else if (act == DG_ACT_RELU) { CFPL_LAUNCH(DG_ACT_RELU); }
-    else { CFPL_LAUNCH(DG_ACT_NONE); }
-#undef CFPL_LAUNCH
-    DG_CHECK_LAUNCH("dg_conv4x4s2_c3_fwd_x3");
-    return DG_OK;
+    DG_CHECK_ARG(y_planes, "dg_conv4x4s2_c3_fwd_x3: null pointer");
+    C3Fwd c = c3_fwd_call("dg_conv4x4s2_c3_fwd_x3", &x_nchw, &w, (void* const*)&y_nhwc, 0, N, H, W, K, act, slope, DG_PREC_F32X3, stream);
+    c.planes = y_planes; c.plane_elems = plane_elems; c.streaming_only = true;
+    return c3_fwd(c);
 }
 
-// the K == 64 streaming kernels, `groups` problems per launch (blockIdx.y); arithmetic = dg_cur_prec()
-extern "C" int dg_c3_fwd_mfma_launch_g(int groups, const float* const* x_tab, const float* const* w_tab, void* const* y_tab, int y_bf16, int N, int H, int W,
-                                       int act, float slope, hipStream_t st) {
-    const DgPtrs x_nchw = dg_ptrs((const void* const*)x_tab, groups), w = dg_ptrs((const void* const*)w_tab, groups),
-                 y_nhwc = dg_ptrs((const void* const*)y_tab, groups);
-    const int Ho = H / 2, Wo = W / 2;
+// The streaming kernels take K == 64 and tensors below 1 GiB (32-bit offsets into one buffer descriptor); the tiled kernel of igemm.hip takes
+// the rest, and everything under option "kt" 16 (which keeps it testable).  The plane-writing form has no tiled counterpart to test, so
+// the option does not reach it.
+enum C3FwdForm { C3_FWD_MFMA_F32, C3_FWD_MFMA_BF16, C3_FWD_X3, C3_FWD_X3_PLANES, C3_FWD_TILED_NARROW, C3_FWD_TILED_WIDE };
+static C3FwdForm c3_fwd_form(const C3Fwd& c) {
+    const bool streams = c.K == CF_K && (long)c.N * 3 * c.H * c.W * 4 < (1L << 30) && (long)c.N * (c.H / 2) * (c.W / 2) < (1L << 30) &&
+                         (dg_get_option(DG_OPT_KT) != 16 || c.planes);
+    if (!streams) return c.K <= 64 ? C3_FWD_TILED_NARROW : C3_FWD_TILED_WIDE;
+    if (c.planes) return C3_FWD_X3_PLANES;
+    if (c.prec == DG_PREC_F32X3 && !c.y_bf16) return C3_FWD_X3;       // fp32-accurate products on the bf16 MFMA
+    return c.prec == DG_PREC_BF16 ? C3_FWD_MFMA_BF16 : C3_FWD_MFMA_F32;
+}
+static int c3_fwd(const C3Fwd& c) {
+    const int N = c.N, H = c.H, W = c.W, K = c.K, Ho = H / 2, Wo = W / 2;
+    DG_CHECK_ARG(c.groups >= 1 && c.groups <= DG_MAX_GROUPS && c.x && c.w && c.y, "%s: bad group / null table", c.who);
+    for (int i = 0; i < c.groups; ++i) DG_CHECK_ARG(c.x[i] && c.w[i] && c.y[i], "%s: null pointer", c.who);
+    DG_CHECK_ARG(N >= 1 && K >= 4 && K % 4 == 0, "%s: bad N/K (%d,%d)", c.who, N, K);
+    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "%s: H,W must be powers of two", c.who);
+    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "%s: tensor too large", c.who);
+    DG_CHECK_ARG(c.act == DG_ACT_NONE || c.act == DG_ACT_LEAKY || c.act == DG_ACT_RELU, "%s: bad act %d", c.who, c.act);
     const long npix = (long)N * Ho * Wo;
+    const C3FwdForm form = c3_fwd_form(c);
+    if (form == C3_FWD_TILED_NARROW || form == C3_FWD_TILED_WIDE) {
+        DG_CHECK_ARG(!c.streaming_only, "%s: only the streaming kernel has this form: it needs K == 64 (K=%d) and tensors below 1 GiB%s", c.who, K,
+                     c.planes ? "" : ", and option kt = 16 asks for the tiled kernel");
+        DG_CHECK_ARG(!c.y_bf16, "%s: a bf16 output needs K == 64 and tensors < 1 GiB (the streaming kernel)", c.who);
+        dg_c3_fwd_tiled((const float*)c.x[0], (const float*)c.w[0], (float*)c.y[0], N, H, W, K, c.act, c.slope, form == C3_FWD_TILED_WIDE, c.st);
+        DG_CHECK_LAUNCH(c.who);
+        return DG_OK;
+    }
+    if (c.planes)
+        DG_CHECK_ARG(c.plane_elems >= (size_t)npix * CF_K && c.plane_elems % 8 == 0, "%s: plane distance %zu for %ld elements", c.who, c.plane_elems, npix * CF_K);
     const long ngroups = (npix + 31) / 32;
-    if (ngroups >= (1L << 30)) return dg_fail(DG_ERR_INVALID, "dg_conv4x4s2_c3_fwd: too many pixels");
     // 8 groups per wave and one workgroup per CU (96 KB of LDS reserved so the dispatcher spreads the grid):
     // measured 26 us vs 34 us at 4 groups / 2 workgroups per CU (256 x 3 x 64 x 64 -> 64 ch); the fixed
     // per-workgroup prologue (weights, first gather) is what the longer waves amortise.  Small launches (64 px / batch 64: 2048 groups
     // per problem = 64 such workgroups) leave most CUs idle: fewer groups per wave until the launch has a workgroup per CU
+    // (the plane-writing form always takes 32 per workgroup)
     long per = 32;
-    while (per > 4 && ((ngroups + per - 1) / per) * groups < 256) per >>= 1;
+    while (form != C3_FWD_X3_PLANES && per > 4 && ((ngroups + per - 1) / per) * c.groups < 256) per >>= 1;
     long wgs = (ngroups + per - 1) / per;
     if (wgs > 4096) wgs = 4096;
-    if (wgs < 1) wgs = 1;
-#define CF_LAUNCH(ACT, O16)                                                                                          \
-    { static const hipError_t once = hipFuncSetAttribute((const void*)c3_fwd_mfma_kernel<ACT, O16>,                    \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);      \
-      (void)once; }                                                                                                     \
-    hipLaunchKernelGGL((c3_fwd_mfma_kernel<ACT, O16>), dim3((unsigned)wgs, groups), dim3(256), 96 * 1024, st, x_nchw, w, y_nhwc, N, H, W, \
-                       dg_ilog2(Ho), dg_ilog2(Wo), npix, (int)ngroups, slope, (int)((long)N * 3 * H * W * 4))
-    if (dg_cur_prec() == 2 && dg_get_option(DG_OPT_KT) != 16 && !y_bf16) {   // f32x3 path: fp32-accurate products on the bf16 MFMA
-#define CFX3_LAUNCH(ACT)                                                                                                    \
-        hipLaunchKernelGGL((c3_fwd_bf16mfma_kernel<ACT, false, true>), dim3((unsigned)wgs, groups), dim3(256), 0, st, x_nchw, w, y_nhwc, N, H, W, \
-                           dg_ilog2(Ho), dg_ilog2(Wo), npix, (int)ngroups, slope, (int)((long)N * 3 * H * W * 4))
-        if (act == DG_ACT_LEAKY) { CFX3_LAUNCH(DG_ACT_LEAKY); }
-        else if (act == DG_ACT_RELU) { CFX3_LAUNCH(DG_ACT_RELU); }
-        else { CFX3_LAUNCH(DG_ACT_NONE); }
-#undef CFX3_LAUNCH
-        return DG_OK;
-    }
-    if (dg_cur_prec() == 1 && dg_get_option(DG_OPT_KT) != 16) {     // bf16 matrix path ("kt" 16 keeps the fp32-MFMA kernel testable there)
-#define CF16_LAUNCH(ACT, O16)                                                                                              \
-        hipLaunchKernelGGL((c3_fwd_bf16mfma_kernel<ACT, O16>), dim3((unsigned)wgs, groups), dim3(256), 0, st, x_nchw, w, y_nhwc, N, H, W,    \
-                           dg_ilog2(Ho), dg_ilog2(Wo), npix, (int)ngroups, slope, (int)((long)N * 3 * H * W * 4))
-        if (y_bf16) {
-            if (act == DG_ACT_LEAKY) { CF16_LAUNCH(DG_ACT_LEAKY, true); }
-            else if (act == DG_ACT_RELU) { CF16_LAUNCH(DG_ACT_RELU, true); }
-            else { CF16_LAUNCH(DG_ACT_NONE, true); }
-        } else {
-            if (act == DG_ACT_LEAKY) { CF16_LAUNCH(DG_ACT_LEAKY, false); }
-            else if (act == DG_ACT_RELU) { CF16_LAUNCH(DG_ACT_RELU, false); }
-            else { CF16_LAUNCH(DG_ACT_NONE, false); }
-        }
-#undef CF16_LAUNCH
-        return DG_OK;
-    }
-    if (y_bf16) {
-        if (act == DG_ACT_LEAKY) { CF_LAUNCH(DG_ACT_LEAKY, true); }
-        else if (act == DG_ACT_RELU) { CF_LAUNCH(DG_ACT_RELU, true); }
-        else { CF_LAUNCH(DG_ACT_NONE, true); }
-    } else {
-        if (act == DG_ACT_LEAKY) { CF_LAUNCH(DG_ACT_LEAKY, false); }
-        else if (act == DG_ACT_RELU) { CF_LAUNCH(DG_ACT_RELU, false); }
-        else { CF_LAUNCH(DG_ACT_NONE, false); }
-    }
-#undef CF_LAUNCH
+    const dim3 grid((unsigned)wgs, c.groups);
+    const DgPtrs px = dg_ptrs(c.x, c.groups), pw = dg_ptrs(c.w, c.groups), py = dg_ptrs(c.y, c.groups);
+    const int lgHo = dg_ilog2(Ho), lgWo = dg_ilog2(Wo), xbytes = (int)((long)N * 3 * H * W * 4);
+    auto mfma_f32 = [&](auto O16) {
+        c3_with_fwd_act(c.act, [&](auto ACT) {
+            static const hipError_t once = hipFuncSetAttribute((const void*)c3_fwd_mfma_kernel<decltype(ACT)::value, decltype(O16)::value>,
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            (void)once;
+            hipLaunchKernelGGL((c3_fwd_mfma_kernel<decltype(ACT)::value, decltype(O16)::value>), grid, dim3(256), 96 * 1024, c.st, px, pw, py, N, H, W,
+                               lgHo, lgWo, npix, (int)ngroups, c.slope, xbytes);
+        });
+    };
+    auto mfma_bf16 = [&](auto O16, auto X3, auto PL) {        // bf16 output, fp32 operands as three bf16 pieces, plane triple of the output
+        c3_with_fwd_act(c.act, [&](auto ACT) {
+            hipLaunchKernelGGL((c3_fwd_bf16mfma_kernel<decltype(ACT)::value, decltype(O16)::value, decltype(X3)::value, decltype(PL)::value>), grid, dim3(256), 0,
+                               c.st, px, pw, py, N, H, W, lgHo, lgWo, npix, (int)ngroups, c.slope, xbytes, (__bf16*)c.planes, (long)c.plane_elems);
+        });
+    };
+    if (form == C3_FWD_X3_PLANES) mfma_bf16(C3No{}, C3Yes{}, C3Yes{});
+    else if (form == C3_FWD_X3) mfma_bf16(C3No{}, C3Yes{}, C3No{});
+    else if (form == C3_FWD_MFMA_BF16) { if (c.y_bf16) mfma_bf16(C3Yes{}, C3No{}, C3No{}); else mfma_bf16(C3No{}, C3No{}, C3No{}); }
+    else { if (c.y_bf16) mfma_f32(C3Yes{}); else mfma_f32(C3No{}); }
+    DG_CHECK_LAUNCH(c.who);
     return DG_OK;
-}
-extern "C" int dg_c3_fwd_mfma_launch(const float* x_nchw, const float* w, void* y_nhwc_v, int y_bf16, int N, int H, int W, int act,
-                                     float slope, hipStream_t st) {
-    return dg_c3_fwd_mfma_launch_g(1, &x_nchw, &w, &y_nhwc_v, y_bf16, N, H, W, act, slope, st);
 }
 
 // ---- weight gradient -------------------------------------------------------------------------------------
@@ -1466,52 +1531,61 @@ extern "C" size_t dg_c3_wgrad_workspace_bytes(int N, int H, int W, int K) {
 }
 // groups problems per launch; share > 1: `share` consecutive problems accumulate into the same dw (one main launch over all problems,
 // then one reduction launch per member in problem order, each adding to what the previous one left)
-static int c3_wgrad_run(const char* who, int groups, int share, const float* const* dy_tab, const float* const* ao_tab, int act, float slope,
-                        const float* const* x_tab, float* const* dw_tab, int N, int H, int W, int K, int accumulate, void* const* ws_tab, size_t ws_bytes,
-                        dg_stream_t stream, int io_bf16 = 0);
-extern "C" int dg_conv4x4s2_c3_wgrad_t(const void* dy_nhwc, const void* act_out_nhwc, int io_bf16, int act, float slope,
-                                       const float* x_nchw, float* dw, int N, int H, int W, int K, int accumulate,
-                                       void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(act == DG_ACT_NONE || ((act == DG_ACT_LEAKY || act == DG_ACT_RELU) && act_out_nhwc),
-                 "dg_conv4x4s2_c3_wgrad_t: act %d needs the saved activation output (LeakyReLU / ReLU only)", act);
-    const float* dyp = (const float*)dy_nhwc;
-    const float* aop = act == DG_ACT_NONE ? nullptr : (const float*)act_out_nhwc;
-    return c3_wgrad_run("dg_conv4x4s2_c3_wgrad_t", 1, 1, &dyp, &aop, act, act == DG_ACT_RELU ? 0.f : slope, &x_nchw, &dw, N, H, W, K, accumulate, &ws,
-                        ws_bytes, stream, io_bf16);
+struct C3Wgrad {
+    const char* who;
+    int groups, share;
+    const void *const *dy, *const *x;
+    const void* const* act_out;             // fused LeakyReLU / ReLU backward on dy: the layer's saved outputs (read when act != DG_ACT_NONE),
+    int act;                                // the activation,
+    float slope;                            // and LeakyReLU's slope
+    float* const* dw;
+    int io_bf16, N, H, W, K, prec, accumulate;    // io_bf16: dy and act_out are bf16
+    void* const* ws;                        // per problem: the per-workgroup partial slabs
+    size_t ws_bytes;
+    hipStream_t st;
+};
+// one problem: the grouped entry point overwrites groups and share
+static C3Wgrad c3_wgrad_call(const char* who, const void* const* dy, const void* const* act_out, int io_bf16, int act, float slope, const float* const* x,
+                             float* const* dw, int N, int H, int W, int K, int prec, int accumulate, void* const* ws, size_t ws_bytes, dg_stream_t stream) {
+    C3Wgrad c = C3Wgrad();
+    c.who = who; c.groups = c.share = 1; c.dy = dy; c.x = (const void* const*)x; c.act_out = act_out; c.act = act; c.slope = slope; c.io_bf16 = io_bf16;
+    c.dw = dw; c.N = N; c.H = H; c.W = W; c.K = K; c.prec = dg_resolve_prec(prec); c.accumulate = accumulate;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    return c;
 }
+static int c3_wgrad(const C3Wgrad& c);
 extern "C" int dg_conv4x4s2_c3_wgrad(const float* dy_nhwc, const float* x_nchw, float* dw, int N, int H, int W, int K,
                                      int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    const float* aop = nullptr;
-    return c3_wgrad_run("dg_conv4x4s2_c3_wgrad", 1, 1, &dy_nhwc, &aop, DG_ACT_NONE, 0.f, &x_nchw, &dw, N, H, W, K, accumulate, &ws, ws_bytes, stream);
+    return c3_wgrad(c3_wgrad_call("dg_conv4x4s2_c3_wgrad", (const void* const*)&dy_nhwc, nullptr, 0, DG_ACT_NONE, 0.f, &x_nchw, &dw, N, H, W, K,
+                                  DG_PREC_DEFAULT, accumulate, &ws, ws_bytes, stream));
 }
 extern "C" int dg_conv4x4s2_c3_wgrad_act(const float* dy_nhwc, const float* act_out_nhwc, int act, float slope,
                                          const float* x_nchw, float* dw, int N, int H, int W, int K, int accumulate,
                                          void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(act == DG_ACT_NONE || ((act == DG_ACT_LEAKY || act == DG_ACT_RELU) && act_out_nhwc),
-                 "dg_conv4x4s2_c3_wgrad_act: act %d needs the saved activation output (LeakyReLU / ReLU only)", act);
-    const float* aop = act == DG_ACT_NONE ? nullptr : act_out_nhwc;
-    return c3_wgrad_run("dg_conv4x4s2_c3_wgrad_act", 1, 1, &dy_nhwc, &aop, act, act == DG_ACT_RELU ? 0.f : slope, &x_nchw, &dw, N, H, W, K, accumulate, &ws,
-                        ws_bytes, stream);
+    return c3_wgrad(c3_wgrad_call("dg_conv4x4s2_c3_wgrad_act", (const void* const*)&dy_nhwc, (const void* const*)&act_out_nhwc, 0, act, slope, &x_nchw, &dw,
+                                  N, H, W, K, DG_PREC_DEFAULT, accumulate, &ws, ws_bytes, stream));
+}
+extern "C" int dg_conv4x4s2_c3_wgrad_t(const void* dy_nhwc, const void* act_out_nhwc, int io_bf16, int act, float slope,
+                                       const float* x_nchw, float* dw, int N, int H, int W, int K, int accumulate,
+                                       void* ws, size_t ws_bytes, dg_stream_t stream) {
+    return c3_wgrad(c3_wgrad_call("dg_conv4x4s2_c3_wgrad_t", &dy_nhwc, &act_out_nhwc, io_bf16, act, slope, &x_nchw, &dw, N, H, W, K, DG_PREC_DEFAULT,
+                                  accumulate, &ws, ws_bytes, stream));
 }
 extern "C" int dg_conv4x4s2_c3_wgrad_p(const void* dy_nhwc, const void* act_out_nhwc, int io_bf16, int act, float slope,
                                        const float* x_nchw, float* dw, int N, int H, int W, int K, int prec, int accumulate,
                                        void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_wgrad_p: prec=%d", prec);
-    DgPrecScope scope(prec);
-    return dg_conv4x4s2_c3_wgrad_t(dy_nhwc, act_out_nhwc, io_bf16, act, slope, x_nchw, dw, N, H, W, K, accumulate, ws, ws_bytes, stream);
+    C3_CHECK_PREC("dg_conv4x4s2_c3_wgrad_p", prec);
+    return c3_wgrad(c3_wgrad_call("dg_conv4x4s2_c3_wgrad_p", &dy_nhwc, &act_out_nhwc, io_bf16, act, slope, &x_nchw, &dw, N, H, W, K, prec, accumulate, &ws,
+                                  ws_bytes, stream));
 }
 extern "C" int dg_conv4x4s2_c3_wgrad_g(int groups, int share, const float* const* dy_nhwc, const float* const* act_out_nhwc, int act, float slope,
                                        const float* const* x_nchw, float* const* dw, int N, int H, int W, int K, int prec, int accumulate,
                                        void* const* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && dy_nhwc && x_nchw && dw && ws, "dg_conv4x4s2_c3_wgrad_g: bad group / null table");
-    DG_CHECK_ARG(share >= 1 && groups % share == 0, "dg_conv4x4s2_c3_wgrad_g: share=%d", share);
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_wgrad_g: prec=%d", prec);
-    DG_CHECK_ARG(act == DG_ACT_NONE || ((act == DG_ACT_LEAKY || act == DG_ACT_RELU) && act_out_nhwc),
-                 "dg_conv4x4s2_c3_wgrad_g: act %d needs the saved activation outputs (LeakyReLU / ReLU only)", act);
-    const float* none[DG_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
-    DgPrecScope scope(prec);
-    return c3_wgrad_run("dg_conv4x4s2_c3_wgrad_g", groups, share, dy_nhwc, act == DG_ACT_NONE ? none : act_out_nhwc, act, act == DG_ACT_RELU ? 0.f : slope,
-                        x_nchw, dw, N, H, W, K, accumulate, ws, ws_bytes, stream);
+    C3_CHECK_PREC("dg_conv4x4s2_c3_wgrad_g", prec);
+    C3Wgrad c = c3_wgrad_call("dg_conv4x4s2_c3_wgrad_g", (const void* const*)dy_nhwc, (const void* const*)act_out_nhwc, 0, act, slope, x_nchw, dw, N, H, W, K,
+                              prec, accumulate, ws, ws_bytes, stream);
+    c.groups = groups; c.share = share;
+    return c3_wgrad(c);
 }
 static int c3_wgrad_reduce_g(int groups, int share, void* const* ws_tab, float* const* dw_tab, int nb, int total, int accumulate, hipStream_t st) {
     const int nout = groups / share;
@@ -1525,76 +1599,79 @@ static int c3_wgrad_reduce_g(int groups, int share, void* const* ws_tab, float* 
     }
     return DG_OK;
 }
-static int c3_wgrad_run(const char* who, int groups, int share, const float* const* dy_tab, const float* const* ao_tab, int act, float slope,
-                        const float* const* x_tab, float* const* dw_tab, int N, int H, int W, int K, int accumulate, void* const* ws_tab, size_t ws_bytes,
-                        dg_stream_t stream, int io_bf16) {
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(dy_tab[i] && x_tab[i] && dw_tab[i], "%s: null pointer", who);
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(dw_tab[i] == dw_tab[i / share * share], "%s: problems of one share set must name the same dw", who);
-    const float* dy_nhwc = dy_tab[0];
-    const float* x_nchw = x_tab[0];
-    const float* act_out = ao_tab[0];
-    void* ws = ws_tab[0];
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG((ao_tab[i] != nullptr) == (act_out != nullptr), "%s: activation outputs for all problems or none", who);
-    DG_CHECK_ARG(N >= 1 && K >= 64 && K % 64 == 0, "%s: K=%d must be a multiple of 64", who, K);
-    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "%s: H,W must be powers of two", who);
-    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "%s: tensor too large", who);
+// lds_x3: fp32-accurate plane products on the bf16 MFMA, image rows staged through LDS (fp32) -- from 256-pixel rows on.  On shorter rows its
+//   one workgroup of four waves per CU is latency-bound and the exact-fp32 MFMA kernel (at least as accurate) is faster: same-box, ms per
+//   call f32 MFMA / this kernel: 64 px batch 64 0.026 / 0.039, batch 256 0.047 / 0.078, 128 px batch 64 0.047 / 0.056, 256 px batch 32
+//   0.076 / 0.075, 512 px batch 32 0.296 / 0.254 (tools/bench_ops.py, round 4)
+// lds_bf16: bf16 operands on the bf16 MFMA, image rows staged through LDS: the same slabs, a contiguous range of output rows per workgroup
+// lane_bf16: the same arithmetic with per-lane gathers (rows past the LDS kernel's, or option "kt" 16); one problem
+// mfma: exact fp32 MFMA, in its variants buffer / 64-bit addressing (BUF), fused activation backward (FACT), bf16 dy (IN16, BUF only)
+enum C3WgradForm { C3_WGRAD_LDS_X3, C3_WGRAD_LDS_BF16, C3_WGRAD_LANE_BF16, C3_WGRAD_MFMA };
+// buf: both tensors < 1 GiB and option "pointer_path" off -> raw buffer loads with 32-bit offsets
+static bool c3_wgrad_buf(const C3Wgrad& c) {
+    return (long)c.N * (c.H / 2) * (c.W / 2) * c.K * 4 < (1L << 30) && (long)c.N * 3 * c.H * c.W * 4 < (1L << 30) && dg_get_option(DG_OPT_POINTER_PATH) == 0;
+}
+static C3WgradForm c3_wgrad_form(const C3Wgrad& c) {
+    const bool lds = c.W / 2 <= CWL_WOMAX && dg_get_option(DG_OPT_KT) != 16;
+    if (!c.io_bf16 && c.prec == DG_PREC_F32X3 && c3_wgrad_buf(c) && c.W >= 256 && lds) return C3_WGRAD_LDS_X3;
+    if (c.io_bf16 && c.prec == DG_PREC_BF16) return c.W >= 32 && lds ? C3_WGRAD_LDS_BF16 : C3_WGRAD_LANE_BF16;
+    return C3_WGRAD_MFMA;
+}
+static int c3_wgrad(const C3Wgrad& c) {
+    const int N = c.N, H = c.H, W = c.W, K = c.K, groups = c.groups;
+    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && c.dy && c.x && c.dw && c.ws, "%s: bad group / null table", c.who);
+    DG_CHECK_ARG(c.share >= 1 && groups % c.share == 0, "%s: share=%d", c.who, c.share);
+    DG_CHECK_ARG(c.act == DG_ACT_NONE || ((c.act == DG_ACT_LEAKY || c.act == DG_ACT_RELU) && c.act_out),
+                 "%s: act %d needs the saved activation output (LeakyReLU / ReLU only)", c.who, c.act);
+    // no activation: no operand; ReLU is LeakyReLU with slope 0
+    const bool fact = c.act != DG_ACT_NONE;
+    const float slope = c.act == DG_ACT_RELU ? 0.f : c.slope;
+    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(c.dy[i] && c.x[i] && c.dw[i] && (!fact || c.act_out[i]), "%s: null pointer", c.who);
+    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(c.dw[i] == c.dw[i / c.share * c.share], "%s: problems of one share set must name the same dw", c.who);
+    DG_CHECK_ARG(N >= 1 && K >= 64 && K % 64 == 0, "%s: K=%d must be a multiple of 64", c.who, K);
+    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "%s: H,W must be powers of two", c.who);
+    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "%s: tensor too large", c.who);
     const long npix = (long)N * (H / 2) * (W / 2);
     int nb, ppw;
     c3_wgrad_plan(npix, &nb, &ppw);
     const size_t need = (size_t)nb * K * 48 * sizeof(float);
     for (int i = 0; i < groups; ++i)
-        if (ws_tab[i] == nullptr || ws_bytes < need) return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const bool buf = npix * K * 4 < (1L << 30) && (long)N * 3 * H * W * 4 < (1L << 30) && dg_get_option(DG_OPT_POINTER_PATH) == 0;
-    const bool fact = act_out != nullptr;
-    const DgPtrs pdy = dg_ptrs((const void* const*)dy_tab, groups), px = dg_ptrs((const void* const*)x_tab, groups),
-                 pws = dg_ptrs((const void* const*)ws_tab, groups), pao = dg_ptrs((const void* const*)ao_tab, groups);
+        if (c.ws[i] == nullptr || c.ws_bytes < need) return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < %zu", c.who, c.ws_bytes, need);
+    const bool buf = c3_wgrad_buf(c);
+    DG_CHECK_ARG(!c.io_bf16 || buf, "%s: bf16 operands need tensors < 1 GiB", c.who);
+    const C3WgradForm form = c3_wgrad_form(c);
+    DG_CHECK_ARG(form != C3_WGRAD_LANE_BF16 || groups == 1, "%s: this kernel takes one problem", c.who);
+    const DgPtrs pdy = dg_ptrs(c.dy, groups), px = dg_ptrs(c.x, groups), pws = dg_ptrs(c.ws, groups), pao = dg_ptrs(fact ? c.act_out : nullptr, groups);
     const dim3 grid(nb, K / 64, groups);
-#define CW_LAUNCH(B, F)                                                                                                  \
-    hipLaunchKernelGGL((c3_wgrad_mfma_kernel<B, F>), grid, dim3(256), 0, st, pdy, px, pws, N, H, W, \
-                       K, dg_ilog2(H / 2), dg_ilog2(W / 2), npix, ppw, pao, slope)
-    if (io_bf16 && !buf) return dg_fail(DG_ERR_INVALID, "%s: bf16 operands need tensors < 1 GiB", who);
-    // f32x3 path: fp32-accurate plane products on the bf16 MFMA, image rows staged through LDS (fp32) -- from 256-pixel rows on.  On
-    // shorter rows its one workgroup of four waves per CU is latency-bound and the exact-fp32 MFMA kernel below (at least as accurate)
-    // is faster: same-box, ms per call f32 MFMA / this kernel: 64 px batch 64 0.026 / 0.039, batch 256 0.047 / 0.078, 128 px batch 64
-    // 0.047 / 0.056, 256 px batch 32 0.076 / 0.075, 512 px batch 32 0.296 / 0.254 (tools/bench_ops.py, round 4)
-    if (!io_bf16 && buf && dg_cur_prec() == 2 && W >= 256 && W / 2 <= CWL_WOMAX && dg_get_option(DG_OPT_KT) != 16) {
-        const int nrows = N * (H / 2);
-        const int rpw = (nrows + nb - 1) / nb;
-        if (fact)
-            hipLaunchKernelGGL((c3_wgrad_lds_kernel<true, true>), grid, dim3(256), 0, st, pdy, px, pws, N, H, W, K, npix, rpw, pao, slope);
-        else
-            hipLaunchKernelGGL((c3_wgrad_lds_kernel<false, true>), grid, dim3(256), 0, st, pdy, px, pws, N, H, W, K, npix, rpw, pao, slope);
-        DG_CHECK_LAUNCH("c3_wgrad_lds_x3");
-        return c3_wgrad_reduce_g(groups, share, ws_tab, dw_tab, nb, K * 48, accumulate, st);
+    const int lgHo = dg_ilog2(H / 2), lgWo = dg_ilog2(W / 2);
+    const int rpw = (N * (H / 2) + nb - 1) / nb;           // the LDS kernels: output rows per workgroup
+    auto lds = [&](auto X3) {
+        c3_with_flag(fact, [&](auto FACT) {
+            hipLaunchKernelGGL((c3_wgrad_lds_kernel<decltype(FACT)::value, decltype(X3)::value>), grid, dim3(256), 0, c.st, pdy, px, pws, N, H, W, K, npix, rpw,
+                               pao, slope);
+        });
+    };
+    auto mfma = [&](auto BUF, auto IN16) {
+        c3_with_flag(fact, [&](auto FACT) {
+            hipLaunchKernelGGL((c3_wgrad_mfma_kernel<decltype(BUF)::value, decltype(FACT)::value, decltype(IN16)::value>), grid, dim3(256), 0, c.st, pdy, px, pws,
+                               N, H, W, K, lgHo, lgWo, npix, ppw, pao, slope);
+        });
+    };
+    switch (form) {
+    case C3_WGRAD_LDS_X3: lds(C3Yes{}); break;
+    case C3_WGRAD_LDS_BF16: lds(C3No{}); break;
+    case C3_WGRAD_LANE_BF16:
+        c3_with_flag(fact, [&](auto FACT) {
+            hipLaunchKernelGGL(c3_wgrad_bf16mfma_kernel<decltype(FACT)::value>, dim3(nb, K / 64), dim3(256), 0, c.st, (const float*)c.dy[0], (const float*)c.x[0],
+                               (float*)c.ws[0], N, H, W, K, lgHo, lgWo, npix, ppw, (const float*)(fact ? c.act_out[0] : nullptr), slope);
+        });
+        break;
+    case C3_WGRAD_MFMA:
+        if (c.io_bf16) mfma(C3Yes{}, C3Yes{});
+        else if (buf) mfma(C3Yes{}, C3No{});
+        else mfma(C3No{}, C3No{});
+        break;
     }
-    if (io_bf16 && dg_cur_prec() == 1 && W >= 32 && W / 2 <= CWL_WOMAX && dg_get_option(DG_OPT_KT) != 16) {
-        // bf16 matrix path, image rows staged through LDS: the same nb slabs, a contiguous range of output rows per workgroup
-        const int nrows = N * (H / 2);
-        const int rpw = (nrows + nb - 1) / nb;
-        if (fact)
-            hipLaunchKernelGGL(c3_wgrad_lds_kernel<true>, grid, dim3(256), 0, st, pdy, px, pws, N, H, W, K, npix, rpw, pao, slope);
-        else
-            hipLaunchKernelGGL(c3_wgrad_lds_kernel<false>, grid, dim3(256), 0, st, pdy, px, pws, N, H, W, K, npix, rpw, pao, slope);
-    } else if (io_bf16 && dg_cur_prec() == 1) {        // bf16 matrix path: bf16 MFMA, per-lane gathers
-        DG_CHECK_ARG(groups == 1, "%s: this kernel takes one problem", who);
-        if (fact)
-            hipLaunchKernelGGL(c3_wgrad_bf16mfma_kernel<true>, dim3(nb, K / 64), dim3(256), 0, st, dy_nhwc, x_nchw, (float*)ws, N, H, W,
-                               K, dg_ilog2(H / 2), dg_ilog2(W / 2), npix, ppw, act_out, slope);
-        else
-            hipLaunchKernelGGL(c3_wgrad_bf16mfma_kernel<false>, dim3(nb, K / 64), dim3(256), 0, st, dy_nhwc, x_nchw, (float*)ws, N, H, W,
-                               K, dg_ilog2(H / 2), dg_ilog2(W / 2), npix, ppw, act_out, slope);
-    } else if (io_bf16 && fact) {
-        hipLaunchKernelGGL((c3_wgrad_mfma_kernel<true, true, true>), grid, dim3(256), 0, st, pdy, px, pws, N, H, W,
-                           K, dg_ilog2(H / 2), dg_ilog2(W / 2), npix, ppw, pao, slope);
-    } else if (io_bf16) {
-        hipLaunchKernelGGL((c3_wgrad_mfma_kernel<true, false, true>), grid, dim3(256), 0, st, pdy, px, pws, N, H, W,
-                           K, dg_ilog2(H / 2), dg_ilog2(W / 2), npix, ppw, pao, slope);
-    } else if (buf && fact) CW_LAUNCH(true, true);
-    else if (buf) CW_LAUNCH(true, false);
-    else if (fact) CW_LAUNCH(false, true);
-    else CW_LAUNCH(false, false);
-#undef CW_LAUNCH
-    DG_CHECK_LAUNCH("c3_wgrad_mfma");
-    return c3_wgrad_reduce_g(groups, share, ws_tab, dw_tab, nb, K * 48, accumulate, st);
+    DG_CHECK_LAUNCH(c.who);
+    return c3_wgrad_reduce_g(groups, c.share, c.ws, c.dw, nb, K * 48, c.accumulate, c.st);
 }

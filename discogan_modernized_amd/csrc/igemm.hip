@@ -1186,9 +1186,6 @@ static int check_channels(const char* who, int op, const ConvGeom& g) {
     if (op == 1 && g.stride == 2) DG_CHECK_ARG(g.K % 32 == 0, "%s: K=%d must be a multiple of 32", who, g.K);
     return DG_OK;
 }
-// DG_PREC_DEFAULT -> the process default (option "bf16").  Resolved once, where a call enters the library: below that the arithmetic is
-// an argument.
-static int resolve_prec(int prec) { return prec >= 0 ? prec : dg_get_option(DG_OPT_BF16); }
 
 // Everything a plan depends on, the named tuning options that make_plan reads (dg_get_option) aside.
 struct PlanReq {
@@ -1506,7 +1503,7 @@ static int run_plan(const char* who, Plan& pl, hipStream_t st) {
 static bool query_plan(const char* who, int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups, int a16, int b16,
                        Plan* pl, PlanReq* keep = nullptr) {
     if (op < 0 || op > 2) { dg_fail(DG_ERR_INVALID, "%s: op=%d (0 forward, 1 input gradient, 2 weight gradient)", who, op); return false; }
-    PlanReq rq = {op, ConvGeom(), resolve_prec(prec), plan_groups >= 1 ? plan_groups : 1, a16, b16, 1};
+    PlanReq rq = {op, ConvGeom(), dg_resolve_prec(prec), plan_groups >= 1 ? plan_groups : 1, a16, b16, 1};
     if (check_geom(who, N, H, W, C, K, stride, pad, &rq.g) != DG_OK || K == 1 || check_channels(who, op, rq.g) != DG_OK) return false;
     make_plan(rq, pl);
     if (keep) *keep = rq;
@@ -1618,7 +1615,7 @@ static ConvCall conv_call(const char* who, int op, const void* const* a, const v
     ConvCall c = ConvCall();
     c.who = who; c.op = op; c.a = a; c.b = b; c.out = out;
     c.N = N; c.H = H; c.W = W; c.C = C; c.K = K; c.stride = stride; c.pad = pad;
-    c.groups = c.share = c.plan_groups = 1; c.prec = resolve_prec(DG_PREC_DEFAULT); c.has_head = true;
+    c.groups = c.share = c.plan_groups = 1; c.prec = dg_resolve_prec(DG_PREC_DEFAULT); c.has_head = true;
     c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
     return c;
 }
@@ -1741,7 +1738,7 @@ static int conv_g(const char* who, int op, int groups, int share, const float* c
     DG_CHECK_ARG(share <= 1 || (op == 2 && groups % share == 0), "%s: share=%d needs the weight gradient and groups %% share == 0", who, share);
     ConvCall c = conv_call(who, op, (const void* const*)a_in, (const void* const*)b_in, (void* const*)out, N, H, W, C, K, stride, pad, ws, ws_bytes,
                            stream);
-    c.groups = groups; c.share = share; c.prec = resolve_prec(prec); c.plan_groups = plan_groups;
+    c.groups = groups; c.share = share; c.prec = dg_resolve_prec(prec); c.plan_groups = plan_groups;
     c.accumulate = accumulate; c.stat = stat; c.stat_floats = stat_floats;
     return conv_launch(c);
 }
@@ -1761,15 +1758,15 @@ extern "C" int dg_conv_wgrad_g(int groups, int share, const float* const* dy, co
 }
 extern "C" int dg_conv_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K,
                            int stride, int pad, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g("dg_conv_fwd", 0, 1, 1, &x, &w, &y, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
+    return conv_g("dg_conv_fwd", 0, 1, 1, &x, &w, &y, N, H, W, C, K, stride, pad, dg_resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K,
                              int stride, int pad, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g("dg_conv_dgrad", 1, 1, 1, &dy, &w, &dx, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
+    return conv_g("dg_conv_dgrad", 1, 1, 1, &dy, &w, &dx, N, H, W, C, K, stride, pad, dg_resolve_prec(DG_PREC_DEFAULT), 1, 0, nullptr, 0, &ws, ws_bytes, stream);
 }
 extern "C" int dg_conv_wgrad(const float* dy, const float* x, float* dw, int N, int H, int W, int C, int K,
                              int stride, int pad, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return conv_g("dg_conv_wgrad", 2, 1, 1, &dy, &x, &dw, N, H, W, C, K, stride, pad, resolve_prec(DG_PREC_DEFAULT), 1, accumulate, nullptr, 0, &ws, ws_bytes, stream);
+    return conv_g("dg_conv_wgrad", 2, 1, 1, &dy, &x, &dw, N, H, W, C, K, stride, pad, dg_resolve_prec(DG_PREC_DEFAULT), 1, accumulate, nullptr, 0, &ws, ws_bytes, stream);
 }
 
 // ---- bf16 shadow operands (option "bf16" = 1 only) -------------------------------------------------------------------
@@ -1945,59 +1942,8 @@ extern "C" int dg_convT4x4_1to4_wgrad(const float* dy, const float* x, float* dw
     return dg_conv_wgrad(x, dy, dw, N, 4, 4, Cout, Cin, 1, 0, acc, ws, wsb, s);
 }
 
-extern "C" int dg_c3_fwd_mfma_launch(const float* x_nchw, const float* w, void* y_nhwc, int y_bf16, int N, int H, int W, int act,
-                                     float slope, hipStream_t st);   // edge.hip
-extern "C" int dg_c3_fwd_mfma_launch_g(int groups, const float* const* x_tab, const float* const* w_tab, void* const* y_tab, int y_bf16, int N, int H, int W,
-                                       int act, float slope, hipStream_t st);   // edge.hip
-static int c3_fwd_run(const float* x_nchw, const float* w, float* y_nhwc, int y_bf16, int N, int H, int W, int K,
-                      int act, float slope, dg_stream_t stream);
-// ---- 3-channel image side, forward direction (conv1 forward / last-convT input-grad) ----------------
-// grouped form: the K == 64 streaming kernels only (the network's first conv / last transposed conv), arithmetic as an argument
-extern "C" int dg_conv4x4s2_c3_fwd_g(int groups, const float* const* x_nchw, const float* const* w, float* const* y_nhwc, int N, int H, int W, int K,
-                                     int act, float slope, int prec, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && x_nchw && w && y_nhwc, "dg_conv4x4s2_c3_fwd_g: bad group / null table");
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(x_nchw[i] && w[i] && y_nhwc[i], "dg_conv4x4s2_c3_fwd_g: null pointer");
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_fwd_g: prec=%d", prec);
-    DG_CHECK_ARG(N >= 1 && K == 64, "dg_conv4x4s2_c3_fwd_g: the grouped form is the K == 64 streaming kernel (K=%d)", K);
-    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "dg_conv4x4s2_c3_fwd_g: H,W must be powers of two");
-    DG_CHECK_ARG((long)N * 3 * H * W * 4 < (1L << 30) && (long)N * (H / 2) * (W / 2) < (1L << 30) && dg_get_option(DG_OPT_KT) != 16,
-                 "dg_conv4x4s2_c3_fwd_g: tensors must be below 1 GiB");
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "dg_conv4x4s2_c3_fwd_g: bad act %d", act);
-    DgPrecScope scope(prec);
-    int rc = dg_c3_fwd_mfma_launch_g(groups, x_nchw, w, (void* const*)y_nhwc, 0, N, H, W, act, slope, (hipStream_t)stream);
-    if (rc != DG_OK) return rc;
-    DG_CHECK_LAUNCH("dg_conv4x4s2_c3_fwd_g");
-    return DG_OK;
-}
-extern "C" int dg_conv4x4s2_c3_fwd(const float* x_nchw, const float* w, float* y_nhwc, int N, int H, int W, int K,
-                                   int act, float slope, dg_stream_t stream) {
-    return c3_fwd_run(x_nchw, w, y_nhwc, 0, N, H, W, K, act, slope, stream);
-}
-extern "C" int dg_conv4x4s2_c3_fwd_t(const float* x_nchw, const float* w, void* y_nhwc, int y_bf16, int N, int H, int W, int K,
-                                     int act, float slope, dg_stream_t stream) {
-    return c3_fwd_run(x_nchw, w, (float*)y_nhwc, y_bf16, N, H, W, K, act, slope, stream);
-}
-extern "C" int dg_conv4x4s2_c3_fwd_p(const float* x_nchw, const float* w, void* y_nhwc, int y_bf16, int N, int H, int W, int K,
-                                     int act, float slope, int prec, dg_stream_t stream) {
-    DG_CHECK_ARG(prec >= DG_PREC_DEFAULT && prec <= DG_PREC_F32X3, "dg_conv4x4s2_c3_fwd_p: prec=%d", prec);
-    DgPrecScope scope(prec);
-    return c3_fwd_run(x_nchw, w, (float*)y_nhwc, y_bf16, N, H, W, K, act, slope, stream);
-}
-static int c3_fwd_run(const float* x_nchw, const float* w, float* y_nhwc, int y_bf16, int N, int H, int W, int K,
-                      int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(x_nchw && w && y_nhwc, "dg_conv4x4s2_c3_fwd: null pointer");
-    DG_CHECK_ARG(N >= 1 && K >= 4 && K % 4 == 0, "dg_conv4x4s2_c3_fwd: bad N/K (%d,%d)", N, K);
-    DG_CHECK_ARG(dg_is_pow2(H) && dg_is_pow2(W) && H >= 2 && W >= 2, "dg_conv4x4s2_c3_fwd: H,W must be powers of two");
-    DG_CHECK_ARG((long)N * 3 * H * W < (1L << 31), "dg_conv4x4s2_c3_fwd: tensor too large");
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "dg_conv4x4s2_c3_fwd: bad act %d", act);
-    hipStream_t st = (hipStream_t)stream;
-    if (K == 64 && dg_get_option(DG_OPT_KT) != 16 && (long)N * 3 * H * W * 4 < (1L << 30) && (long)N * (H / 2) * (W / 2) < (1L << 30)) {       // streaming per-wave kernel (edge.hip); kt=16 forces the tiled path
-        int rc = dg_c3_fwd_mfma_launch(x_nchw, w, y_nhwc, y_bf16, N, H, W, act, slope, st);
-        if (rc != DG_OK) return rc;
-        DG_CHECK_LAUNCH("dg_conv4x4s2_c3_fwd");
-        return DG_OK;
-    }
-    DG_CHECK_ARG(!y_bf16, "dg_conv4x4s2_c3_fwd_t: a bf16 output needs K == 64 and tensors < 1 GiB (the streaming kernel)");
+// ---- 3-channel image side, forward direction: the tiled form behind edge.hip's streaming kernels (any K % 4 == 0, any size) --------
+void dg_c3_fwd_tiled(const float* x_nchw, const float* w, float* y_nhwc, int N, int H, int W, int K, int act, float slope, bool wide, hipStream_t st) {
     IgemmArgs a = IgemmArgs();
     a.A = x_nchw; a.B = w; a.C = y_nhwc;
     a.N = N; a.H = H; a.W = W; a.Cc = 3; a.K = K;
@@ -2006,13 +1952,11 @@ static int c3_fwd_run(const float* x_nchw, const float* w, float* y_nhwc, int y_
     a.M = N * a.Ho * a.Wo; a.Ng = K; a.R = 48;
     a.nIt = 3; a.itPerSplit = 3; a.splits = 1;
     a.act = act; a.slope = slope;
-    if (K <= 64) {
+    if (!wide) {
         a.tilesM = (a.M + 255) / 256; a.tilesN = 1;
         launch_igemm<MODE_FWD_C3, 4, 1, 16>(a, 1, st);
     } else {
         a.tilesM = (a.M + 127) / 128; a.tilesN = (K + 127) / 128;
         launch_igemm<MODE_FWD_C3, 2, 2, 16>(a, 1, st);
     }
-    DG_CHECK_LAUNCH("dg_conv4x4s2_c3_fwd");
-    return DG_OK;
 }

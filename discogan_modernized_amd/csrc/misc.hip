@@ -14,10 +14,6 @@ int dg_fail(int code, const char* fmt, ...) {
     return code;
 }
 int dg_get_option(int idx) { return (idx >= 0 && idx < DG_OPT_COUNT) ? g_options[idx] : 0; }
-static thread_local int tl_call_prec = -1;
-int dg_cur_prec() { return tl_call_prec >= 0 ? tl_call_prec : g_options[DG_OPT_BF16]; }
-DgPrecScope::DgPrecScope(int prec) : old(tl_call_prec) { if (prec >= 0) tl_call_prec = prec; }     // DG_PREC_DEFAULT (-1): keep what is in force
-DgPrecScope::~DgPrecScope() { tl_call_prec = old; }
 
 extern "C" int dg_version(void) { return 100; }
 // bit 0: the experiments build (kernels that lost their A/B: window forward kernel, register-staged plane reader, persistent window

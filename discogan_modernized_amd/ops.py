@@ -795,19 +795,9 @@ def c3_wgrad(dy, x_nchw, out=None, accumulate=False, act_out=None, act=ACT_NONE,
     if fuse:
         ao = as_nhwc(act_out)
         assert ao.shape == dy.shape and ao.dtype == dy.dtype
-    if _is16(dy):
-        with _hbm("edge_c3_wgrad", 2.0 * ((2 if fuse else 1) * dy.numel()) + 4.0 * x.numel()):
-            _lib.check(L.dg_conv4x4s2_c3_wgrad_p(_ptr(dy), _ptr(ao), 1, act if fuse else ACT_NONE, float(slope), _ptr(x), _ptr(dw),
-                                                 n, h, wd, k, _CUR.cprec, int(accumulate), _ptr(ws), wsb, _stream()), "dg_conv4x4s2_c3_wgrad_p")
-        return dw
-    if fuse:
-        with _hbm("edge_c3_wgrad", 4.0 * (2 * dy.numel() + x.numel())):
-            _lib.check(L.dg_conv4x4s2_c3_wgrad_p(_ptr(dy), _ptr(ao), 0, act, float(slope), _ptr(x), _ptr(dw), n, h, wd, k, _CUR.cprec,
-                                                 int(accumulate), _ptr(ws), wsb, _stream()), "dg_conv4x4s2_c3_wgrad_p")
-        return dw
-    with _hbm("edge_c3_wgrad", 4.0 * (dy.numel() + x.numel())):
-        _lib.check(L.dg_conv4x4s2_c3_wgrad_p(_ptr(dy), None, 0, ACT_NONE, 0.0, _ptr(x), _ptr(dw), n, h, wd, k, _CUR.cprec, int(accumulate), _ptr(ws), wsb,
-                                             _stream()), "dg_conv4x4s2_c3_wgrad_p")
+    with _hbm("edge_c3_wgrad", float(dy.element_size()) * ((2 if fuse else 1) * dy.numel()) + 4.0 * x.numel()):
+        _lib.check(L.dg_conv4x4s2_c3_wgrad_p(_ptr(dy), _ptr(ao), int(_is16(dy)), act if fuse else ACT_NONE, float(slope), _ptr(x), _ptr(dw),
+                                             n, h, wd, k, _CUR.cprec, int(accumulate), _ptr(ws), wsb, _stream()), "dg_conv4x4s2_c3_wgrad_p")
     return dw
 
 

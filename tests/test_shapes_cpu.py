@@ -1,6 +1,9 @@
 """Host-side halves of tests/test_shapes_gpu.py (no GPU needed): the plan queries on both sides of the 2 GiB limits, the
-c3 input gradient's argument checks past the scatter kernel's limit, and the discrimination of the fp64 error bound."""
+c3 input gradient's argument checks past the scatter kernel's limit, the recorded refusals of every 3-channel edge entry point, and
+the discrimination of the fp64 error bound."""
 import ctypes
+import json
+import os
 
 import pytest
 import torch
@@ -37,6 +40,157 @@ def test_c3_dgrad_refuses_a_bf16_dy_on_the_fp32_kernels():
     assert b"scatter kernel" in L.dg_last_error()
     assert L.dg_conv4x4s2_c3_dgrad_act_p(d, 0, d, ops.ACT_LEAKY, 0.2, d, d, 128, 512, 512, 64, ops.ACT_NONE, 0, None, 0, None) < 0
     assert b"scatter kernel" in L.dg_last_error()
+
+
+# ---- every 3-channel edge entry point: what it refuses before any launch -------------------------------------------------------------
+EDGE_REFUSALS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edge_refusals.json")
+_E = "dg_conv4x4s2_c3_"
+# parameter names of the entry points, in ABI order
+EDGE_PARAMS = {
+    "fwd": "x w y N H W K act slope stream",
+    "fwd_t": "x w y bf16 N H W K act slope stream",
+    "fwd_p": "x w y bf16 N H W K act slope prec stream",
+    "fwd_g": "groups x w y N H W K act slope prec stream",
+    "fwd_x3": "x w y planes plane_elems N H W K act slope stream",
+    "dgrad": "dy w dx N H W K act ws ws_bytes stream",
+    "dgrad_t": "dy bf16 w dx N H W K act ws ws_bytes stream",
+    "dgrad_p": "dy bf16 w dx N H W K act prec ws ws_bytes stream",
+    "dgrad_act_p": "dy bf16 act_out in_act slope w dx N H W K act prec ws ws_bytes stream",
+    "dgrad_g": "groups dy w dx N H W K act prec stream",
+    "wgrad": "dy x dw N H W K accumulate ws ws_bytes stream",
+    "wgrad_act": "dy act_out fact slope x dw N H W K accumulate ws ws_bytes stream",
+    "wgrad_t": "dy act_out bf16 fact slope x dw N H W K accumulate ws ws_bytes stream",
+    "wgrad_p": "dy act_out bf16 fact slope x dw N H W K prec accumulate ws ws_bytes stream",
+    "wgrad_g": "groups share dy act_out fact slope x dw N H W K prec accumulate ws ws_bytes stream",
+}
+EDGE_POINTERS = ("x", "w", "y", "planes", "dy", "dx", "dw", "act_out", "ws")
+BIG = (4096, 512, 512)          # N * 3 * H * W = 3 * 2^30 elements: past every edge kernel's 2^31
+GIB = (1024, 512, 512)          # an image tensor of 3 GiB: past the streaming forward's 1 GiB
+
+
+def edge_refusal_cases():
+    """(label, entry point, {parameter: value} over the accepted base call, {option: value}) for argument tuples that every edge
+    entry point must refuse before it launches anything.  The base call is (N, H, W, K) = (2, 8, 8, 64), fp32 tensors, no activation,
+    arithmetic 0, two problems for the grouped forms, a large enough workspace.  Pointer values: "ptr" a non-null dummy (never
+    dereferenced: validation fails first), "ptr2" another one, None null; for a grouped form a table of four of them, "hole" a table
+    whose second entry is null, "mixed" a table of two different addresses."""
+    cases = []
+
+    def add(what, entry, over, **options):
+        if all(k in EDGE_PARAMS[entry].split() for k in over):
+            opt = "".join(f" [{k} {v}]" for k, v in sorted(options.items()))
+            cases.append((f"{entry}: {what}{opt}", entry, dict(over), dict(options)))
+
+    for entry, params in EDGE_PARAMS.items():
+        names = params.split()
+        op = entry.split("_")[0]
+        grouped = entry.endswith("_g")
+        for ptr in EDGE_POINTERS:
+            if ptr in names and not (op == "dgrad" and ptr == "ws") and not (op == "wgrad" and ptr in ("act_out", "ws")):
+                add(f"null {ptr}", entry, {ptr: None})
+                if grouped:
+                    add(f"null entry in {ptr}", entry, {ptr: "hole"})
+        for g in (0, 5):
+            add(f"groups {g}", entry, dict(groups=g))
+        add("share 3 of 2 problems", entry, dict(share=3))
+        add("share 0", entry, dict(share=0))
+        add("mismatched dw in a share set", entry, dict(share=2, dw="mixed"))
+        for prec in (-2, 3):
+            add(f"prec {prec}", entry, dict(prec=prec))
+        for K in ((32, 96) if op == "wgrad" else (0, 2, 6)):
+            add(f"K {K}", entry, dict(K=K))
+        for dim in ("H", "W"):
+            for v in (1, 6, 12):
+                add(f"{dim} {v}", entry, {dim: v})
+        add("N 0", entry, dict(N=0))
+        add("image tensor past 2^31 elements", entry, dict(zip("NHW", BIG)))
+        for act in ((1, 7) if op == "dgrad" else (3, 7)):
+            add(f"bad act {act}", entry, dict(act=act))
+            add(f"bad fused act {act}", entry, dict(fact=act, act_out="ptr"))
+        for act in (1, 2):
+            add(f"fused act {act} without act_out", entry, dict(fact=act, act_out=None))
+        if op != "wgrad":
+            for K in (32, 128):
+                add(f"bf16 tensor at K {K}", entry, dict(bf16=1, K=K))
+                if grouped or entry in ("fwd_x3", "dgrad_act_p"):
+                    add(f"K {K}", entry, dict(K=K))
+            add("bf16 tensor", entry, dict(bf16=1), kt=16)
+            if grouped or entry == "dgrad_act_p":
+                add("base call", entry, {}, kt=16)
+        if op == "wgrad":
+            add("null ws", entry, dict(ws=None))
+            add("short ws", entry, dict(ws_bytes="short"))
+            add("bf16 tensors on the 64-bit addressing kernels", entry, dict(bf16=1), pointer_path=1)
+            if grouped:
+                add("null entry in ws", entry, dict(ws="hole"))
+        if op == "dgrad" and "ws" in names and entry != "dgrad_act_p":
+            add("null ws", entry, dict(ws=None), kt=16)
+            add("short ws", entry, dict(ws_bytes="short"), kt=16)
+    add("image tensor of 3 GiB", "fwd_g", dict(zip("NHW", GIB)))
+    add("image tensor of 3 GiB", "fwd_x3", dict(zip("NHW", GIB), plane_elems=1 << 40))
+    add("bf16 output with an image tensor of 3 GiB", "fwd_t", dict(zip("NHW", GIB), bf16=1))
+    add("plane distance too small", "fwd_x3", dict(plane_elems=2 * 4 * 4 * 64 - 8))
+    add("plane distance no multiple of 8", "fwd_x3", dict(plane_elems=2 * 4 * 4 * 64 + 4))
+    for a in (0, 2, 3):
+        add(f"in_act {a}", "dgrad_act_p", dict(in_act=a))
+    add("bf16 dy past 2^31 bytes", "dgrad_t", dict(N=256, H=512, W=512, bf16=1))
+    add("bf16 dy past 2^31 bytes", "dgrad_act_p", dict(N=256, H=512, W=512, bf16=1))
+    add("fp32 dy past 2^31 bytes", "dgrad_act_p", dict(N=128, H=512, W=512))
+    add("fp32 dy past 2^31 bytes", "dgrad_g", dict(N=128, H=512, W=512))
+    return cases
+
+
+def edge_refusal_codes(L):
+    """The return code of every case of edge_refusal_cases(), under each process-default arithmetic: {"0": [...], "1": ..., "2": ...}."""
+    P = ctypes.c_void_p
+    tables = dict(ptr=(P * 4)(8, 8, 8, 8), hole=(P * 4)(8, None, 8, 8), mixed=(P * 4)(8, 16, 8, 8))
+    codes = {}
+    try:
+        for default in (0, 1, 2):
+            _lib.set_option("bf16", default)
+            row = codes[str(default)] = []
+            for label, entry, over, options in edge_refusal_cases():
+                grouped = entry.endswith("_g")
+                v = dict(N=2, H=8, W=8, K=64, act=0, fact=0, in_act=ops.ACT_LEAKY, slope=0.2, prec=0, bf16=0, groups=2, share=1, accumulate=0,
+                         plane_elems=2 * 4 * 4 * 64, ws_bytes=1 << 20, stream=None, **{p: "ptr" for p in EDGE_POINTERS})
+                if entry.startswith("wgrad") and "act_out" not in over:
+                    v["act_out"] = None
+                v.update(over)
+                if v["ws_bytes"] == "short":
+                    need = L.dg_c3_wgrad_workspace_bytes(v["N"], v["H"], v["W"], v["K"]) if entry.startswith("wgrad") else L.dg_c3_dgrad_workspace_bytes(v["K"])
+                    assert need > 0
+                    v["ws_bytes"] = need - 1
+                for p in EDGE_POINTERS:
+                    if v[p] is not None:
+                        v[p] = tables[v[p]] if grouped else P(dict(ptr=8, ptr2=16)[v[p]])
+                for k, val in options.items():
+                    _lib.set_option(k, val)
+                try:
+                    row.append(getattr(L, _E + entry)(*[v[n] for n in EDGE_PARAMS[entry].split()]))
+                finally:
+                    for k in options:
+                        _lib.set_option(k, 0)
+    finally:
+        for k in ("kt", "bf16", "pointer_path"):
+            _lib.set_option(k, 0)
+    return codes
+
+
+def test_edge_entry_points_refuse_what_the_recorded_table_says():
+    """tests/golden/edge_refusals.json holds the return code of every 3-channel edge entry point for argument tuples that are refused
+    before any launch, written from the library of the commit BEFORE the edge host code was rewritten around one call record per op
+    (tests/golden/make_edge_refusals.py).  The library must still give exactly these codes: DG_ERR_INVALID (-1) or DG_ERR_WORKSPACE (-2),
+    whatever the process-default arithmetic."""
+    with open(EDGE_REFUSALS) as f:
+        table = json.load(f)
+    cases = edge_refusal_cases()
+    assert table["cases"] == [c[0] for c in cases] and len(set(table["cases"])) == len(cases)
+    codes = edge_refusal_codes(_lib.load())
+    assert sorted(codes) == sorted(table["codes"]) == ["0", "1", "2"]
+    for default, want in table["codes"].items():
+        assert len(want) == len(cases) and all(c in (-1, -2) for c in want)
+        for label, got, w in zip(table["cases"], codes[default], want):
+            assert got == w, f"{label} (process default arithmetic {default}): {got}, recorded {w}"
 
 
 @pytest.mark.parametrize("N,fits", [(65535, True), (65536, False)])
