@@ -10,6 +10,7 @@
 //             dbeta = sum g, dgamma = sum g*xhat, dy = gamma*invstd*(g - dbeta/M - xhat*dgamma/M)
 #include "dg_common.h"
 #include <string.h>
+#include <initializer_list>
 
 #define BN_U 8     // independent row loads in flight per thread (same-box A/B of the whole iteration: U=2 13.46 ms, 4 13.17, 8 13.13)
 
@@ -898,12 +899,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const BnGroup G,
     }
 }
 // geometry of the two kernels above: TX channel lanes (16 for quad-chunk planes: a wave = 4 pixels x 64 channels), row chunks of a multiple of
-// 8 rows.  Shapes they do not take (C not a multiple of 64, M not of 8) stay on the item kernels.
-struct BnRows { int ok, tx, cchunks, rchunks, rows_per; };
+// 8 rows.  Geometry only: bn_form() decides which shapes take these kernels (C a multiple of 64, M of 8).
+struct BnRows { int tx, cchunks, rchunks, rows_per; };
 static BnRows bn_rows(int M, int C, int cm, int V) {
-    BnRows g = {0, 0, 0, 0, 0};
-    if (C % 64 != 0 || M % 8 != 0 || dg_get_option(DG_OPT_BN_ITEMS)) return g;
-    g.ok = 1;
+    BnRows g;
     g.tx = 64 / V;                                  // quad-chunk planes: a wave = 4 (8) pixels x 64 channels
     if (!cm) while (g.tx < C / V && g.tx < 64) g.tx <<= 1;
     g.cchunks = (C / V + g.tx - 1) / g.tx;         // ragged last chunk (C = 192, 320, ...): the kernels return on c >= C
@@ -987,60 +986,292 @@ extern "C" size_t dg_bn_workspace_bytes(int M, int C) {
     return ((size_t)2 * g.rchunks * C + 2 * (size_t)C) * sizeof(double);   // fp64 partials in the backward
 }
 
-// io_bf16: every activation tensor of the call (y / z / dz / dy) is bf16; statistics, parameters and their gradients stay fp32
-// groups problems per launch (BnGroup), share: consecutive problems through the same module (see bn_stats_finalize_kernel)
-template <typename T>
-static int bn_train_stats_impl(int groups, int share, const BnGroup& G, int M, int C, float eps, float momentum, size_t ws_bytes, dg_stream_t stream) {
-    constexpr int V = BnV<T>::V;
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && share >= 1 && groups % share == 0, "dg_bn_train_stats: groups=%d share=%d", groups, share);
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(G.p[i].y && G.p[i].saved, "dg_bn_train_stats: null pointer (problem %d)", i);
-    DG_CHECK_ARG(M >= 2, "dg_bn_train_stats: Expected more than 1 value per channel when training (M=%d)", M);
-    DG_CHECK_ARG(C >= V && C % V == 0, "dg_bn_train_stats: C=%d must be a multiple of %d", C, V);
-    for (int i = 0; i < groups; ++i)
-        if (G.p[i].ws == nullptr || ws_bytes < dg_bn_workspace_bytes(M, C))
-            return dg_fail(DG_ERR_WORKSPACE, "dg_bn_train_stats: workspace %zu < %zu", ws_bytes, dg_bn_workspace_bytes(M, C));
-    const BnGrid g = bn_grid(M, C, V);
-    const int cc = g.cchunks, rc = g.rchunks;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_partial_kernel<T>, dim3(cc, rc, groups), dim3(256), 0, st, G, M, C, rc, g.tx);
+// ---- BatchNorm host layer: one call record, three passes ------------------------------------------------------------------------
+// Every dg_bn_* entry point fills one BnCall on its stack and calls its pass (bn_stats, bn_fwd, bn_bwd); a pass validates the record once,
+// names the apply form (bn_form) and launches.  Nothing below an entry point reads a process-wide option.
+enum BnExtra { BN_EXTRA_NONE = 0, BN_EXTRA_SHADOW = 1, BN_EXTRA_PLANES = 2 };
+struct BnCall {
+    const char* who;                        // the entry point's public name, for messages
+    int groups;                             // problems of this launch (1 .. DG_MAX_GROUPS)
+    int share;                              // consecutive problems through the same module: one finalize block sums them (1: none)
+    bool null_table;                        // a *_g entry point was handed a null pointer table (its problems are then not read)
+    BnGroup G;                              // the problems' pointers: the kernel argument as it stands
+    int M, C;                               // rows (N * H * W) and channels of every problem
+    bool bf16;                              // activation storage: y / z / dz / dy are bf16 (io_bf16), else fp32; everything else stays fp32
+    BnExtra extra;                          // second output beside p[0].out, at p[0].out16 (one problem): none | bf16 shadow | bf16 plane triple
+    size_t plane_elems;                     // planes: elements from one plane to the next (>= M * C, % 8 == 0)
+    int plane_layout;                       // planes: 0 pixel-major, 1 quad-chunk (C % 64 == 0, M % 4 == 0)
+    bool write_out;                         // p[i].out is written; false (planes only): the plane triple is the only output
+    int act;                                // apply passes: DG_ACT_NONE | _LEAKY | _RELU,
+    float slope;                            // and LeakyReLU's slope
+    float eps, momentum;                    // statistics pass
+    int accumulate;                         // backward: add to dgamma / dbeta instead of overwriting them
+    size_t ws_bytes;                        // bytes behind every p[i].ws (dg_bn_workspace_bytes)
+    int items;                              // apply passes: option "bn_items", read where the call entered the library (item kernels everywhere)
+    hipStream_t st;
+};
+// one fp32 problem, no second output: an entry point overwrites what it differs in
+static BnCall bn_call(const char* who, int M, int C, dg_stream_t stream) {
+    BnCall c = BnCall();
+    c.who = who; c.groups = c.share = 1; c.M = M; c.C = C; c.write_out = true; c.st = (hipStream_t)stream;
+    return c;
+}
+static BnCall bn_apply_call(const char* who, int M, int C, int act, float slope, dg_stream_t stream) {
+    BnCall c = bn_call(who, M, C, stream);
+    c.act = act; c.slope = slope; c.items = dg_get_option(DG_OPT_BN_ITEMS);
+    return c;
+}
+// a *_g entry point: groups, share (< 1 -> 1) and how many problems to read from its tables (none when a table is missing)
+static int bn_grouped(BnCall& c, int groups, int share, bool tables) {
+    c.groups = groups; c.share = share < 1 ? 1 : share; c.null_table = !tables;
+    return tables && groups >= 1 && groups <= DG_MAX_GROUPS ? groups : 0;
+}
+
+// What a pass needs of a call: per-problem pointers beyond y and saved, and the checks that not every pass makes.
+enum { BN_NEED_DZ = 1, BN_NEED_OUT = 2, BN_NEED_AFFINE = 4, BN_NEED_WS = 8, BN_NEED_ROWS2 = 16, BN_NEED_ACT = 32 };
+// The one validation.  Every refusal is DG_ERR_INVALID, except the workspace's (DG_ERR_WORKSPACE), which comes last.
+static int bn_validate(const BnCall& c, int need) {
+    const int M = c.M, C = c.C, V = c.bf16 ? 8 : 4;
+    DG_CHECK_ARG(c.groups >= 1 && c.groups <= DG_MAX_GROUPS && !c.null_table, "%s: groups=%d (1..%d) or a null table", c.who, c.groups, DG_MAX_GROUPS);
+    DG_CHECK_ARG(c.share >= 1 && c.groups % c.share == 0, "%s: groups=%d share=%d", c.who, c.groups, c.share);
+    DG_CHECK_ARG(c.groups == 1 || c.extra == BN_EXTRA_NONE, "%s: shadow / plane outputs exist in the one-problem forms only", c.who);
+    for (int i = 0; i < c.groups; ++i) {
+        const BnProb &P = c.G.p[i], &S = c.G.p[i / c.share * c.share];
+        DG_CHECK_ARG(P.rmean == S.rmean && P.dgamma == S.dgamma && P.dbeta == S.dbeta,
+                     "%s: problems of one share set must name the same module buffers (running_mean, dgamma, dbeta)", c.who);
+        DG_CHECK_ARG(P.y && P.saved && (!(need & BN_NEED_DZ) || P.dz) && (!(need & BN_NEED_OUT) || !c.write_out || P.out) &&
+                         (!(need & BN_NEED_AFFINE) || (P.gamma && P.beta)),
+                     "%s: null pointer (problem %d)", c.who, i);
+    }
+    if (c.extra != BN_EXTRA_NONE)
+        DG_CHECK_ARG(c.G.p[0].out16, "%s: null %s pointer", c.who, c.extra == BN_EXTRA_PLANES ? "plane" : "shadow");
+    if (c.extra == BN_EXTRA_PLANES) {
+        DG_CHECK_ARG(c.plane_layout == 0 || c.plane_layout == 1, "%s: plane_layout 0 (pixel-major) or 1 (quad-chunk)", c.who);
+        DG_CHECK_ARG(c.plane_elems >= (size_t)M * C && c.plane_elems % 8 == 0, "%s: plane distance %zu for %ld elements", c.who, c.plane_elems, (long)M * C);
+        DG_CHECK_ARG(!c.plane_layout || (C % 64 == 0 && M % 4 == 0), "%s: quad-chunk planes need C %% 64 == 0 and M %% 4 == 0 (C=%d, M=%d)", c.who, C, M);
+    }
+    if (need & BN_NEED_ROWS2) DG_CHECK_ARG(M >= 2, "%s: Expected more than 1 value per channel when training (M=%d)", c.who, M);
+    DG_CHECK_ARG(C >= V && C % V == 0, "%s: C=%d must be a multiple of %d", c.who, C, V);
+    if (need & BN_NEED_ACT) DG_CHECK_ARG(c.act == DG_ACT_NONE || c.act == DG_ACT_LEAKY || c.act == DG_ACT_RELU, "%s: bad act %d", c.who, c.act);
+    if (need & BN_NEED_WS) {
+        const size_t want = dg_bn_workspace_bytes(M, C);
+        for (int i = 0; i < c.groups; ++i)
+            if (c.G.p[i].ws == nullptr || c.ws_bytes < want) return dg_fail(DG_ERR_WORKSPACE, "%s: workspace %zu < %zu", c.who, c.ws_bytes, want);
+    }
+    return DG_OK;
+}
+
+// The apply form of a forward / backward pass: the kernel that moves the activations, and what it writes beside `out`.
+enum BnApply {
+    BN_APPLY_BF16,                                                              // bf16 storage
+    BN_APPLY_ROWS, BN_APPLY_ROWS_SHADOW, BN_APPLY_ROWS_PLANES,                  // rows kernels + BnExtra
+    BN_APPLY_ITEMS, BN_APPLY_ITEMS_SHADOW, BN_APPLY_ITEMS_PLANES                // item kernels + BnExtra
+};
+struct BnForm { BnApply apply; BnRows rows; };                                  // rows: the rows kernels' geometry (BN_APPLY_ROWS* only)
+// Pure: no option, no global.  In priority order:
+//   1. bf16 storage has one kernel per pass (8 channels per lane on the reduction passes' grid) and no second output;
+//   2. the rows kernels take C % 64 == 0 && M % 8 == 0, unless `items` asks for the item kernels; planes move V = 8 channels per lane, and
+//      quad-chunk planes (layout 1) keep tx = 64 / V (bn_rows);
+//   3. every other shape goes to the item kernels.
+// Within 2 and 3 the second output picks the instantiation.
+static BnForm bn_form(bool bf16, BnExtra extra, int layout, int M, int C, int items) {
+    BnForm f = BnForm();
+    const bool rows = !bf16 && C % 64 == 0 && M % 8 == 0 && !items;
+    f.apply = bf16 ? BN_APPLY_BF16 : (BnApply)((rows ? BN_APPLY_ROWS : BN_APPLY_ITEMS) + extra);
+    if (rows) f.rows = bn_rows(M, C, layout, extra == BN_EXTRA_PLANES ? 8 : 4);
+    return f;
+}
+
+#define BN_LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, c.G, __VA_ARGS__)
+
+static int bn_stats(const BnCall& c) {
+    if (const int rc = bn_validate(c, BN_NEED_WS | BN_NEED_ROWS2)) return rc;
+    const BnGrid g = bn_grid(c.M, c.C, c.bf16 ? 8 : 4);
+    const dim3 pgrid(g.cchunks, g.rchunks, c.groups), fgrid((c.C + BN_FIN_CH - 1) / BN_FIN_CH, c.groups / c.share);
+    if (c.bf16) BN_LAUNCH(bn_stats_partial_kernel<__bf16>, pgrid, c.M, c.C, g.rchunks, g.tx);
+    else BN_LAUNCH(bn_stats_partial_kernel<float>, pgrid, c.M, c.C, g.rchunks, g.tx);
     DG_CHECK_LAUNCH("bn_stats_partial");
-    hipLaunchKernelGGL(bn_stats_finalize_kernel<T>, dim3((C + BN_FIN_CH - 1) / BN_FIN_CH, groups / share), dim3(256), 0, st, G, share, M, C, rc, eps, momentum);
+    if (c.bf16) BN_LAUNCH(bn_stats_finalize_kernel<__bf16>, fgrid, c.share, c.M, c.C, g.rchunks, c.eps, c.momentum);
+    else BN_LAUNCH(bn_stats_finalize_kernel<float>, fgrid, c.share, c.M, c.C, g.rchunks, c.eps, c.momentum);
     DG_CHECK_LAUNCH("bn_stats_finalize");
     return DG_OK;
 }
-static BnGroup bn_group_zero() {
-    BnGroup G;
-    memset(&G, 0, sizeof(G));
-    return G;
+
+static int bn_fwd(const BnCall& c) {
+    if (const int rc = bn_validate(c, BN_NEED_OUT | BN_NEED_AFFINE | BN_NEED_ACT)) return rc;
+    const BnForm f = bn_form(c.bf16, c.extra, c.plane_layout, c.M, c.C, c.items);
+    const BnRows& r = f.rows;
+    const int M = c.M, C = c.C, act = c.act, cm = c.plane_layout;
+    const float slope = c.slope;
+    const long total4 = (long)M * C / 4, ps = (long)c.plane_elems;
+    const dim3 rgrid(r.cchunks, r.rchunks, c.groups), igrid(stream_grid(total4), c.groups);
+    switch (f.apply) {
+    case BN_APPLY_BF16: {
+        const BnGrid g = bn_grid(M, C, 8);
+        BN_LAUNCH(bn_act_fwd16_kernel, dim3(g.cchunks, g.rchunks, c.groups), M, C, g.rchunks, g.tx, act, slope);
+        break;
+    }
+    case BN_APPLY_ROWS:         BN_LAUNCH((bn_act_fwd_rows_kernel<0, 4>), rgrid, M, C, r.rows_per, r.tx, act, slope, 0L, 0); break;
+    case BN_APPLY_ROWS_SHADOW:  BN_LAUNCH((bn_act_fwd_rows_kernel<1, 4>), rgrid, M, C, r.rows_per, r.tx, act, slope, 0L, 0); break;
+    case BN_APPLY_ROWS_PLANES:  BN_LAUNCH((bn_act_fwd_rows_kernel<3, 8>), rgrid, M, C, r.rows_per, r.tx, act, slope, ps, cm); break;
+    case BN_APPLY_ITEMS:        BN_LAUNCH((bn_act_fwd_kernel<float, float, 0>), igrid, total4, C, act, slope, 0L, 0); break;
+    case BN_APPLY_ITEMS_SHADOW: BN_LAUNCH((bn_act_fwd_kernel<float, float, 1>), igrid, total4, C, act, slope, 0L, 0); break;
+    case BN_APPLY_ITEMS_PLANES: BN_LAUNCH((bn_act_fwd_kernel<float, float, 3>), igrid, total4, C, act, slope, ps, cm); break;
+    }
+    DG_CHECK_LAUNCH("bn_act_fwd");
+    return DG_OK;
+}
+
+static int bn_bwd(const BnCall& c) {
+    if (const int rc = bn_validate(c, BN_NEED_DZ | BN_NEED_OUT | BN_NEED_AFFINE | BN_NEED_ACT | BN_NEED_WS)) return rc;
+    const BnForm f = bn_form(c.bf16, c.extra, c.plane_layout, c.M, c.C, c.items);
+    const BnRows& r = f.rows;
+    const int M = c.M, C = c.C, act = c.act, cm = c.plane_layout;
+    const float slope = c.slope;
+    const BnGrid g = bn_grid(M, C, c.bf16 ? 8 : 4);
+    const int rc = g.rchunks;                                                   // partials per channel: also what the apply kernels' coefficients came from
+    const long total4 = (long)M * C / 4, ps = (long)c.plane_elems;
+    const dim3 pgrid(g.cchunks, rc, c.groups), rgrid(r.cchunks, r.rchunks, c.groups), igrid(stream_grid(total4), c.groups);
+    if (c.bf16) BN_LAUNCH(bn_bwd_partial_kernel<__bf16>, pgrid, M, C, rc, g.tx, act, slope);
+    else BN_LAUNCH(bn_bwd_partial_kernel<float>, pgrid, M, C, rc, g.tx, act, slope);
+    DG_CHECK_LAUNCH("bn_bwd_partial");
+    BN_LAUNCH(bn_bwd_finalize_kernel, dim3((C + BN_FIN_CH - 1) / BN_FIN_CH, c.groups / c.share), c.share, M, C, rc, c.accumulate);
+    DG_CHECK_LAUNCH("bn_bwd_finalize");
+    switch (f.apply) {
+    case BN_APPLY_BF16:         BN_LAUNCH(bn_bwd_apply16_kernel, pgrid, M, C, rc, g.tx, rc, act, slope); break;
+    case BN_APPLY_ROWS:         BN_LAUNCH((bn_bwd_apply_rows_kernel<0, 4>), rgrid, M, C, r.rows_per, r.tx, rc, act, slope, 0L, 0); break;
+    case BN_APPLY_ROWS_SHADOW:  BN_LAUNCH((bn_bwd_apply_rows_kernel<1, 4>), rgrid, M, C, r.rows_per, r.tx, rc, act, slope, 0L, 0); break;
+    case BN_APPLY_ROWS_PLANES:  BN_LAUNCH((bn_bwd_apply_rows_kernel<3, 8>), rgrid, M, C, r.rows_per, r.tx, rc, act, slope, ps, cm); break;
+    case BN_APPLY_ITEMS:        BN_LAUNCH((bn_bwd_apply_kernel<float, 0>), igrid, total4, C, rc, act, slope, 0L, 0); break;
+    case BN_APPLY_ITEMS_SHADOW: BN_LAUNCH((bn_bwd_apply_kernel<float, 1>), igrid, total4, C, rc, act, slope, 0L, 0); break;
+    case BN_APPLY_ITEMS_PLANES: BN_LAUNCH((bn_bwd_apply_kernel<float, 3>), igrid, total4, C, rc, act, slope, ps, cm); break;
+    }
+    DG_CHECK_LAUNCH("bn_bwd_apply");
+    return DG_OK;
+}
+#undef BN_LAUNCH
+
+// ---- entry points: fill the record, call the pass ---------------------------------------------------------------------------------
+static int bn_stats_one(const char* who, const void* y, int io_bf16, int M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                        int64_t* nbt, float* saved, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    BnCall c = bn_call(who, M, C, stream);
+    c.bf16 = io_bf16 != 0; c.eps = eps; c.momentum = momentum; c.ws_bytes = ws_bytes;
+    BnProb& P = c.G.p[0];
+    P.y = y; P.rmean = running_mean; P.rvar = running_var; P.nbt = nbt; P.saved = saved; P.ws = ws;
+    return bn_stats(c);
 }
 extern "C" int dg_bn_train_stats_t(const void* y, int io_bf16, int M, int C, float eps, float momentum, float* running_mean,
                                    float* running_var, int64_t* nbt, float* saved, void* ws, size_t ws_bytes,
                                    dg_stream_t stream) {
-    BnGroup G = bn_group_zero();
-    G.p[0].y = y; G.p[0].rmean = running_mean; G.p[0].rvar = running_var; G.p[0].nbt = nbt; G.p[0].saved = saved; G.p[0].ws = ws;
-    if (io_bf16) return bn_train_stats_impl<__bf16>(1, 1, G, M, C, eps, momentum, ws_bytes, stream);
-    return bn_train_stats_impl<float>(1, 1, G, M, C, eps, momentum, ws_bytes, stream);
+    return bn_stats_one("dg_bn_train_stats_t", y, io_bf16, M, C, eps, momentum, running_mean, running_var, nbt, saved, ws, ws_bytes, stream);
 }
 extern "C" int dg_bn_train_stats(const float* y, int M, int C, float eps, float momentum, float* running_mean,
                                  float* running_var, int64_t* nbt, float* saved, void* ws, size_t ws_bytes,
                                  dg_stream_t stream) {
-    return dg_bn_train_stats_t(y, 0, M, C, eps, momentum, running_mean, running_var, nbt, saved, ws, ws_bytes, stream);
+    return bn_stats_one("dg_bn_train_stats", y, 0, M, C, eps, momentum, running_mean, running_var, nbt, saved, ws, ws_bytes, stream);
 }
 extern "C" int dg_bn_train_stats_g(int groups, int share, const float* const* y, int M, int C, float eps, float momentum, float* const* running_mean,
                                    float* const* running_var, int64_t* const* nbt, float* const* saved, void* const* ws, size_t ws_bytes,
                                    dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && y && saved && ws, "dg_bn_train_stats_g: bad group / null table");
-    BnGroup G = bn_group_zero();
-    for (int i = 0; i < groups; ++i) {
-        G.p[i].y = y[i]; G.p[i].saved = saved[i]; G.p[i].ws = ws[i];
-        G.p[i].rmean = running_mean ? running_mean[i] : nullptr;
-        G.p[i].rvar = running_var ? running_var[i] : nullptr;
-        G.p[i].nbt = nbt ? nbt[i] : nullptr;
+    BnCall c = bn_call("dg_bn_train_stats_g", M, C, stream);
+    c.eps = eps; c.momentum = momentum; c.ws_bytes = ws_bytes;
+    for (int i = 0, n = bn_grouped(c, groups, share, y && saved && ws); i < n; ++i) {
+        BnProb& P = c.G.p[i];
+        P.y = y[i]; P.saved = saved[i]; P.ws = ws[i];
+        P.rmean = running_mean ? running_mean[i] : nullptr;
+        P.rvar = running_var ? running_var[i] : nullptr;
+        P.nbt = nbt ? nbt[i] : nullptr;
     }
-    if (share > 1)
-        for (int i = 0; i < groups; ++i)
-            DG_CHECK_ARG(G.p[i].rmean == G.p[i / share * share].rmean, "dg_bn_train_stats_g: problems of one share set must name the same module buffers");
-    return bn_train_stats_impl<float>(groups, share < 1 ? 1 : share, G, M, C, eps, momentum, ws_bytes, stream);
+    return bn_stats(c);
+}
+
+static BnCall bn_fwd_call(const char* who, const void* y, void* z, int M, int C, const float* saved, const float* gamma, const float* beta, int act,
+                          float slope, dg_stream_t stream) {
+    BnCall c = bn_apply_call(who, M, C, act, slope, stream);
+    BnProb& P = c.G.p[0];
+    P.y = y; P.out = z; P.saved = (float*)saved; P.gamma = gamma; P.beta = beta;
+    return c;
+}
+extern "C" int dg_bn_act_fwd(const float* y, float* z, int M, int C, const float* saved, const float* gamma,
+                             const float* beta, int act, float slope, dg_stream_t stream) {
+    return bn_fwd(bn_fwd_call("dg_bn_act_fwd", y, z, M, C, saved, gamma, beta, act, slope, stream));
+}
+extern "C" int dg_bn_act_fwd_g(int groups, const float* const* y, float* const* z, int M, int C, const float* const* saved, const float* const* gamma,
+                               const float* const* beta, int act, float slope, dg_stream_t stream) {
+    BnCall c = bn_apply_call("dg_bn_act_fwd_g", M, C, act, slope, stream);
+    for (int i = 0, n = bn_grouped(c, groups, 1, y && z && saved && gamma && beta); i < n; ++i) {
+        BnProb& P = c.G.p[i];
+        P.y = y[i]; P.out = z[i]; P.saved = (float*)saved[i]; P.gamma = gamma[i]; P.beta = beta[i];
+    }
+    return bn_fwd(c);
+}
+extern "C" int dg_bn_act_fwd_bf16(const float* y, float* z, void* z_bf16, int M, int C, const float* saved, const float* gamma,
+                                  const float* beta, int act, float slope, dg_stream_t stream) {
+    BnCall c = bn_fwd_call("dg_bn_act_fwd_bf16", y, z, M, C, saved, gamma, beta, act, slope, stream);
+    c.extra = BN_EXTRA_SHADOW; c.G.p[0].out16 = z_bf16;
+    return bn_fwd(c);
+}
+// the same pass, also writing the three bf16 planes of z (plane_elems elements apart, >= M * C, % 8 == 0) for the f32x3 matrix path;
+// z == nullptr: the planes only
+extern "C" int dg_bn_act_fwd_x3(const float* y, float* z, void* z_planes, size_t plane_elems, int plane_layout, int M, int C, const float* saved,
+                                const float* gamma, const float* beta, int act, float slope, dg_stream_t stream) {
+    BnCall c = bn_fwd_call("dg_bn_act_fwd_x3", y, z, M, C, saved, gamma, beta, act, slope, stream);
+    c.extra = BN_EXTRA_PLANES; c.G.p[0].out16 = z_planes; c.plane_elems = plane_elems; c.plane_layout = plane_layout; c.write_out = z != nullptr;
+    return bn_fwd(c);
+}
+extern "C" int dg_bn_act_fwd_t(const void* y, void* z, int io_bf16, int M, int C, const float* saved, const float* gamma,
+                               const float* beta, int act, float slope, dg_stream_t stream) {
+    BnCall c = bn_fwd_call("dg_bn_act_fwd_t", y, z, M, C, saved, gamma, beta, act, slope, stream);
+    c.bf16 = io_bf16 != 0;
+    return bn_fwd(c);
+}
+
+static void bn_bwd_prob(BnProb& P, const void* dz, const void* y, void* dy, const float* saved, const float* gamma, const float* beta, float* dgamma,
+                        float* dbeta, void* ws) {
+    P.dz = dz; P.y = y; P.out = dy; P.saved = (float*)saved; P.gamma = gamma; P.beta = beta; P.dgamma = dgamma; P.dbeta = dbeta; P.ws = ws;
+}
+static BnCall bn_bwd_call(const char* who, const void* dz, const void* y, void* dy, int M, int C, const float* saved, const float* gamma,
+                          const float* beta, int act, float slope, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes,
+                          dg_stream_t stream) {
+    BnCall c = bn_apply_call(who, M, C, act, slope, stream);
+    c.accumulate = accumulate; c.ws_bytes = ws_bytes;
+    bn_bwd_prob(c.G.p[0], dz, y, dy, saved, gamma, beta, dgamma, dbeta, ws);
+    return c;
+}
+extern "C" int dg_bn_act_bwd(const float* dz, const float* y, float* dy, int M, int C, const float* saved,
+                             const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
+                             int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    return bn_bwd(bn_bwd_call("dg_bn_act_bwd", dz, y, dy, M, C, saved, gamma, beta, act, slope, dgamma, dbeta, accumulate, ws, ws_bytes, stream));
+}
+extern "C" int dg_bn_act_bwd_g(int groups, int share, const float* const* dz, const float* const* y, float* const* dy, int M, int C,
+                               const float* const* saved, const float* const* gamma, const float* const* beta, int act, float slope,
+                               float* const* dgamma, float* const* dbeta, int accumulate, void* const* ws, size_t ws_bytes, dg_stream_t stream) {
+    BnCall c = bn_apply_call("dg_bn_act_bwd_g", M, C, act, slope, stream);
+    c.accumulate = accumulate; c.ws_bytes = ws_bytes;
+    for (int i = 0, n = bn_grouped(c, groups, share, dz && y && dy && saved && gamma && beta && ws); i < n; ++i)
+        bn_bwd_prob(c.G.p[i], dz[i], y[i], dy[i], saved[i], gamma[i], beta[i], dgamma ? dgamma[i] : nullptr, dbeta ? dbeta[i] : nullptr, ws[i]);
+    return bn_bwd(c);
+}
+extern "C" int dg_bn_act_bwd_bf16(const float* dz, const float* y, float* dy, void* dy_bf16, int M, int C, const float* saved,
+                                  const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
+                                  int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    BnCall c = bn_bwd_call("dg_bn_act_bwd_bf16", dz, y, dy, M, C, saved, gamma, beta, act, slope, dgamma, dbeta, accumulate, ws, ws_bytes, stream);
+    c.extra = BN_EXTRA_SHADOW; c.G.p[0].out16 = dy_bf16;
+    return bn_bwd(c);
+}
+extern "C" int dg_bn_act_bwd_x3(const float* dz, const float* y, float* dy, void* dy_planes, size_t plane_elems, int plane_layout, int M, int C,
+                                const float* saved, const float* gamma, const float* beta, int act, float slope, float* dgamma,
+                                float* dbeta, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    BnCall c = bn_bwd_call("dg_bn_act_bwd_x3", dz, y, dy, M, C, saved, gamma, beta, act, slope, dgamma, dbeta, accumulate, ws, ws_bytes, stream);
+    c.extra = BN_EXTRA_PLANES; c.G.p[0].out16 = dy_planes; c.plane_elems = plane_elems; c.plane_layout = plane_layout; c.write_out = dy != nullptr;
+    return bn_bwd(c);
+}
+extern "C" int dg_bn_act_bwd_t(const void* dz, const void* y, void* dy, int io_bf16, int M, int C, const float* saved,
+                               const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
+                               int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    BnCall c = bn_bwd_call("dg_bn_act_bwd_t", dz, y, dy, M, C, saved, gamma, beta, act, slope, dgamma, dbeta, accumulate, ws, ws_bytes, stream);
+    c.bf16 = io_bf16 != 0;
+    return bn_bwd(c);
 }
 
 static int bn_partials_row_blocks(int P) {
@@ -1074,202 +1305,6 @@ extern "C" int dg_bn_stats_from_partials(const float* stat, int P, int M, int C,
                        M, C, eps, momentum, running_mean, running_var, nbt, saved);
     DG_CHECK_LAUNCH("bn_partials_finalize");
     return DG_OK;
-}
-
-template <typename T>
-static int bn_act_fwd_impl(int groups, const BnGroup& G, int M, int C, int act, float slope, dg_stream_t stream, long pstride = 0, int plane_cm = 0) {
-    constexpr int V = BnV<T>::V;
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS, "dg_bn_act_fwd: groups=%d", groups);
-    const void* z16 = G.p[0].out16;
-    DG_CHECK_ARG(groups == 1 || z16 == nullptr, "dg_bn_act_fwd: shadow / plane outputs exist in the one-problem forms only");
-    for (int i = 0; i < groups; ++i)
-        DG_CHECK_ARG(G.p[i].y && (G.p[i].out || (G.p[i].out16 && pstride > 0)) && G.p[i].saved && G.p[i].gamma && G.p[i].beta, "dg_bn_act_fwd: null pointer");
-    DG_CHECK_ARG(!plane_cm || (pstride > 0 && C % 64 == 0 && M % 4 == 0), "dg_bn_act_fwd: quad-chunk planes need plane operands, C %% 64 == 0 and M %% 4 == 0 (C=%d, M=%d)", C, M);
-    DG_CHECK_ARG(C >= V && C % V == 0, "dg_bn_act_fwd: C=%d must be a multiple of %d", C, V);
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "dg_bn_act_fwd: bad act %d", act);
-    const long totalv = (long)M * C / V;
-    if constexpr (V == 8) {
-        const BnGrid g = bn_grid(M, C, V);
-        hipLaunchKernelGGL(bn_act_fwd16_kernel, dim3(g.cchunks, g.rchunks, groups), dim3(256), 0, (hipStream_t)stream, G, M, C, g.rchunks, g.tx, act, slope);
-        DG_CHECK_LAUNCH("bn_act_fwd16");
-        return DG_OK;
-    }
-    if constexpr (V == 4) {
-        const bool planes = z16 && pstride > 0;
-        if (const BnRows rg = bn_rows(M, C, plane_cm, planes ? 8 : 4); rg.ok) {
-            const dim3 rgrid(rg.cchunks, rg.rchunks, groups);
-            if (planes)
-                hipLaunchKernelGGL((bn_act_fwd_rows_kernel<3, 8>), rgrid, dim3(256), 0, (hipStream_t)stream, G, M, C, rg.rows_per, rg.tx, act, slope, pstride, plane_cm);
-            else if (z16)
-                hipLaunchKernelGGL((bn_act_fwd_rows_kernel<1, 4>), rgrid, dim3(256), 0, (hipStream_t)stream, G, M, C, rg.rows_per, rg.tx, act, slope, 0L, 0);
-            else
-                hipLaunchKernelGGL((bn_act_fwd_rows_kernel<0, 4>), rgrid, dim3(256), 0, (hipStream_t)stream, G, M, C, rg.rows_per, rg.tx, act, slope, 0L, 0);
-            DG_CHECK_LAUNCH("bn_act_fwd_rows");
-            return DG_OK;
-        }
-    }
-    const dim3 grid(stream_grid(totalv), groups);
-    if constexpr (V == 4) {
-        if (z16 && pstride > 0) {
-            hipLaunchKernelGGL((bn_act_fwd_kernel<T, T, 3>), grid, dim3(256), 0, (hipStream_t)stream, G, totalv, C, act, slope, pstride, plane_cm);
-            DG_CHECK_LAUNCH("bn_act_fwd");
-            return DG_OK;
-        }
-        if (z16) {
-            hipLaunchKernelGGL((bn_act_fwd_kernel<T, T, 1>), grid, dim3(256), 0, (hipStream_t)stream, G, totalv, C, act, slope, 0L, 0);
-            DG_CHECK_LAUNCH("bn_act_fwd");
-            return DG_OK;
-        }
-    }
-    hipLaunchKernelGGL((bn_act_fwd_kernel<T, T, 0>), grid, dim3(256), 0, (hipStream_t)stream, G, totalv, C, act, slope, 0L, 0);
-    DG_CHECK_LAUNCH("bn_act_fwd");
-    return DG_OK;
-}
-static BnGroup bn_fwd_one(const void* y, void* z, void* z16, const float* saved, const float* gamma, const float* beta) {
-    BnGroup G = bn_group_zero();
-    G.p[0].y = y; G.p[0].out = z; G.p[0].out16 = z16; G.p[0].saved = (float*)saved; G.p[0].gamma = gamma; G.p[0].beta = beta;
-    return G;
-}
-extern "C" int dg_bn_act_fwd(const float* y, float* z, int M, int C, const float* saved, const float* gamma,
-                             const float* beta, int act, float slope, dg_stream_t stream) {
-    return bn_act_fwd_impl<float>(1, bn_fwd_one(y, z, nullptr, saved, gamma, beta), M, C, act, slope, stream);
-}
-extern "C" int dg_bn_act_fwd_g(int groups, const float* const* y, float* const* z, int M, int C, const float* const* saved, const float* const* gamma,
-                               const float* const* beta, int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && y && z && saved && gamma && beta, "dg_bn_act_fwd_g: bad group / null table");
-    BnGroup G = bn_group_zero();
-    for (int i = 0; i < groups; ++i) {
-        G.p[i].y = y[i]; G.p[i].out = z[i]; G.p[i].saved = (float*)saved[i]; G.p[i].gamma = gamma[i]; G.p[i].beta = beta[i];
-    }
-    return bn_act_fwd_impl<float>(groups, G, M, C, act, slope, stream);
-}
-extern "C" int dg_bn_act_fwd_bf16(const float* y, float* z, void* z_bf16, int M, int C, const float* saved, const float* gamma,
-                                  const float* beta, int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(z_bf16, "dg_bn_act_fwd_bf16: null shadow pointer");
-    return bn_act_fwd_impl<float>(1, bn_fwd_one(y, z, z_bf16, saved, gamma, beta), M, C, act, slope, stream);
-}
-// the same pass, also writing the three bf16 planes of z (plane_elems elements apart, >= M * C, % 8 == 0) for the f32x3 matrix path
-extern "C" int dg_bn_act_fwd_x3(const float* y, float* z, void* z_planes, size_t plane_elems, int plane_layout, int M, int C, const float* saved,
-                                const float* gamma, const float* beta, int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(plane_layout == 0 || plane_layout == 1, "dg_bn_act_fwd_x3: plane_layout 0 (pixel-major) or 1 (quad-chunk)");
-    DG_CHECK_ARG(z_planes, "dg_bn_act_fwd_x3: null plane pointer");
-    DG_CHECK_ARG(plane_elems >= (size_t)M * C && plane_elems % 8 == 0, "dg_bn_act_fwd_x3: plane distance %zu for %ld elements", plane_elems, (long)M * C);
-    return bn_act_fwd_impl<float>(1, bn_fwd_one(y, z, z_planes, saved, gamma, beta), M, C, act, slope, stream, (long)plane_elems, plane_layout);
-}
-extern "C" int dg_bn_act_fwd_t(const void* y, void* z, int io_bf16, int M, int C, const float* saved, const float* gamma,
-                               const float* beta, int act, float slope, dg_stream_t stream) {
-    if (io_bf16) return bn_act_fwd_impl<__bf16>(1, bn_fwd_one(y, z, nullptr, saved, gamma, beta), M, C, act, slope, stream);
-    return bn_act_fwd_impl<float>(1, bn_fwd_one(y, z, nullptr, saved, gamma, beta), M, C, act, slope, stream);
-}
-
-template <typename T>
-static int bn_act_bwd_impl(int groups, int share, const BnGroup& G, int M, int C, int act, float slope, int accumulate, size_t ws_bytes,
-                           dg_stream_t stream, long pstride = 0, int plane_cm = 0) {
-    constexpr int V = BnV<T>::V;
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && share >= 1 && groups % share == 0, "dg_bn_act_bwd: groups=%d share=%d", groups, share);
-    const void* dy16 = G.p[0].out16;
-    DG_CHECK_ARG(groups == 1 || dy16 == nullptr, "dg_bn_act_bwd: shadow / plane outputs exist in the one-problem forms only");
-    for (int i = 0; i < groups; ++i)
-        DG_CHECK_ARG(G.p[i].dz && G.p[i].y && (G.p[i].out || (G.p[i].out16 && pstride > 0)) && G.p[i].saved && G.p[i].gamma && G.p[i].beta, "dg_bn_act_bwd: null pointer");
-    DG_CHECK_ARG(!plane_cm || (pstride > 0 && C % 64 == 0 && M % 4 == 0), "dg_bn_act_bwd: quad-chunk planes need plane operands, C %% 64 == 0 and M %% 4 == 0 (C=%d, M=%d)", C, M);
-    DG_CHECK_ARG(C >= V && C % V == 0, "dg_bn_act_bwd: C=%d must be a multiple of %d", C, V);
-    DG_CHECK_ARG(act == DG_ACT_NONE || act == DG_ACT_LEAKY || act == DG_ACT_RELU, "dg_bn_act_bwd: bad act %d", act);
-    for (int i = 0; i < groups; ++i)
-        if (G.p[i].ws == nullptr || ws_bytes < dg_bn_workspace_bytes(M, C))
-            return dg_fail(DG_ERR_WORKSPACE, "dg_bn_act_bwd: workspace %zu < %zu", ws_bytes, dg_bn_workspace_bytes(M, C));
-    const BnGrid g = bn_grid(M, C, V);
-    const int cc = g.cchunks, rc = g.rchunks;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(cc, rc, groups), dim3(256), 0, st, G, M, C, rc, g.tx, act, slope);
-    DG_CHECK_LAUNCH("bn_bwd_partial");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + BN_FIN_CH - 1) / BN_FIN_CH, groups / share), dim3(256), 0, st, G, share, M, C, rc, accumulate);
-    DG_CHECK_LAUNCH("bn_bwd_finalize");
-    const long totalv = (long)M * C / V;
-    if constexpr (V == 4) {
-        const bool planes = dy16 && pstride > 0;
-        if (const BnRows rg = bn_rows(M, C, plane_cm, planes ? 8 : 4); rg.ok) {
-            const dim3 rgrid(rg.cchunks, rg.rchunks, groups);
-            if (planes)
-                hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<3, 8>), rgrid, dim3(256), 0, st, G, M, C, rg.rows_per, rg.tx, rc, act, slope, pstride, plane_cm);
-            else if (dy16)
-                hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<1, 4>), rgrid, dim3(256), 0, st, G, M, C, rg.rows_per, rg.tx, rc, act, slope, 0L, 0);
-            else
-                hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<0, 4>), rgrid, dim3(256), 0, st, G, M, C, rg.rows_per, rg.tx, rc, act, slope, 0L, 0);
-            DG_CHECK_LAUNCH("bn_bwd_apply_rows");
-            return DG_OK;
-        }
-    }
-    const dim3 grid(stream_grid(totalv), groups);
-    if constexpr (V == 4) {
-        if (dy16 && pstride > 0) {
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 3>), grid, dim3(256), 0, st, G, totalv, C, rc, act, slope, pstride, plane_cm);
-            DG_CHECK_LAUNCH("bn_bwd_apply");
-            return DG_OK;
-        }
-        if (dy16) {
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 1>), grid, dim3(256), 0, st, G, totalv, C, rc, act, slope, 0L, 0);
-            DG_CHECK_LAUNCH("bn_bwd_apply");
-            return DG_OK;
-        }
-    } else {
-        hipLaunchKernelGGL(bn_bwd_apply16_kernel, dim3(cc, rc, groups), dim3(256), 0, st, G, M, C, rc, g.tx, rc, act, slope);
-        DG_CHECK_LAUNCH("bn_bwd_apply16");
-        return DG_OK;
-    }
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 0>), grid, dim3(256), 0, st, G, totalv, C, rc, act, slope, 0L, 0);
-    DG_CHECK_LAUNCH("bn_bwd_apply");
-    return DG_OK;
-}
-static BnGroup bn_bwd_one(const void* dz, const void* y, void* dy, void* dy16, const float* saved, const float* gamma, const float* beta,
-                          float* dgamma, float* dbeta, void* ws) {
-    BnGroup G = bn_group_zero();
-    BnProb& P = G.p[0];
-    P.dz = dz; P.y = y; P.out = dy; P.out16 = dy16; P.saved = (float*)saved; P.gamma = gamma; P.beta = beta; P.dgamma = dgamma; P.dbeta = dbeta; P.ws = ws;
-    return G;
-}
-extern "C" int dg_bn_act_bwd(const float* dz, const float* y, float* dy, int M, int C, const float* saved,
-                             const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
-                             int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    return bn_act_bwd_impl<float>(1, 1, bn_bwd_one(dz, y, dy, nullptr, saved, gamma, beta, dgamma, dbeta, ws), M, C, act, slope, accumulate, ws_bytes, stream);
-}
-extern "C" int dg_bn_act_bwd_g(int groups, int share, const float* const* dz, const float* const* y, float* const* dy, int M, int C,
-                               const float* const* saved, const float* const* gamma, const float* const* beta, int act, float slope,
-                               float* const* dgamma, float* const* dbeta, int accumulate, void* const* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && dz && y && dy && saved && gamma && beta && ws, "dg_bn_act_bwd_g: bad group / null table");
-    BnGroup G = bn_group_zero();
-    for (int i = 0; i < groups; ++i) {
-        BnProb& P = G.p[i];
-        P.dz = dz[i]; P.y = y[i]; P.out = dy[i]; P.saved = (float*)saved[i]; P.gamma = gamma[i]; P.beta = beta[i]; P.ws = ws[i];
-        P.dgamma = dgamma ? dgamma[i] : nullptr;
-        P.dbeta = dbeta ? dbeta[i] : nullptr;
-    }
-    if (share > 1)
-        for (int i = 0; i < groups; ++i)
-            DG_CHECK_ARG(G.p[i].dgamma == G.p[i / share * share].dgamma && G.p[i].dbeta == G.p[i / share * share].dbeta,
-                         "dg_bn_act_bwd_g: problems of one share set must name the same dgamma / dbeta");
-    return bn_act_bwd_impl<float>(groups, share < 1 ? 1 : share, G, M, C, act, slope, accumulate, ws_bytes, stream);
-}
-extern "C" int dg_bn_act_bwd_bf16(const float* dz, const float* y, float* dy, void* dy_bf16, int M, int C, const float* saved,
-                                  const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
-                                  int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(dy_bf16, "dg_bn_act_bwd_bf16: null shadow pointer");
-    return bn_act_bwd_impl<float>(1, 1, bn_bwd_one(dz, y, dy, dy_bf16, saved, gamma, beta, dgamma, dbeta, ws), M, C, act, slope, accumulate, ws_bytes, stream);
-}
-extern "C" int dg_bn_act_bwd_x3(const float* dz, const float* y, float* dy, void* dy_planes, size_t plane_elems, int plane_layout, int M, int C,
-                                const float* saved, const float* gamma, const float* beta, int act, float slope, float* dgamma,
-                                float* dbeta, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    DG_CHECK_ARG(plane_layout == 0 || plane_layout == 1, "dg_bn_act_bwd_x3: plane_layout 0 (pixel-major) or 1 (quad-chunk)");
-    DG_CHECK_ARG(dy_planes, "dg_bn_act_bwd_x3: null plane pointer");
-    DG_CHECK_ARG(plane_elems >= (size_t)M * C && plane_elems % 8 == 0, "dg_bn_act_bwd_x3: plane distance %zu for %ld elements", plane_elems, (long)M * C);
-    return bn_act_bwd_impl<float>(1, 1, bn_bwd_one(dz, y, dy, dy_planes, saved, gamma, beta, dgamma, dbeta, ws), M, C, act, slope, accumulate, ws_bytes,
-                                  stream, (long)plane_elems, plane_layout);
-}
-extern "C" int dg_bn_act_bwd_t(const void* dz, const void* y, void* dy, int io_bf16, int M, int C, const float* saved,
-                               const float* gamma, const float* beta, int act, float slope, float* dgamma, float* dbeta,
-                               int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
-    const BnGroup G = bn_bwd_one(dz, y, dy, nullptr, saved, gamma, beta, dgamma, dbeta, ws);
-    if (io_bf16) return bn_act_bwd_impl<__bf16>(1, 1, G, M, C, act, slope, accumulate, ws_bytes, stream);
-    return bn_act_bwd_impl<float>(1, 1, G, M, C, act, slope, accumulate, ws_bytes, stream);
 }
 
 #ifdef DG_EXPERIMENTS
@@ -1345,10 +1380,19 @@ static int act_fwd_understory(const float* x, float* y, size_t n, int act, float
 }
 #endif
 
-extern "C" int dg_act_fwd_g(int groups, const float* const* x, float* const* y, size_t n, int act, float slope, dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && x && y, "dg_act_fwd: bad group / null table");
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(x[i] && y[i], "dg_act_fwd: null pointer");
-    DG_CHECK_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "dg_act_fwd: bad act %d", act);
+// ---- stand-alone activations: one validation, one launch site per kernel ---------------------------------------------------------
+// tabs: the call's pointer tables, `groups` pointers each (a one-problem form passes the addresses of its arguments)
+static int act_validate(const char* who, int groups, std::initializer_list<const void* const*> tabs, int act) {
+    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS, "%s: groups=%d (1..%d)", who, groups, DG_MAX_GROUPS);
+    for (const void* const* t : tabs) {
+        DG_CHECK_ARG(t, "%s: null table", who);
+        for (int i = 0; i < groups; ++i) DG_CHECK_ARG(t[i], "%s: null pointer", who);
+    }
+    DG_CHECK_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "%s: bad act %d", who, act);
+    return DG_OK;
+}
+static int act_fwd(const char* who, int groups, const float* const* x, float* const* y, size_t n, int act, float slope, dg_stream_t stream) {
+    if (const int rc = act_validate(who, groups, {(const void* const*)x, (const void* const*)y}, act)) return rc;
     if (n == 0) return DG_OK;
 #ifdef DG_EXPERIMENTS
     if (const int np = dg_get_option(DG_OPT_UNDERSTORY); np && groups == 1 && n % 4 == 0) {
@@ -1364,33 +1408,35 @@ extern "C" int dg_act_fwd_g(int groups, const float* const* x, float* const* y, 
     DG_CHECK_LAUNCH("act_fwd");
     return DG_OK;
 }
-extern "C" int dg_act_fwd(const float* x, float* y, size_t n, int act, float slope, dg_stream_t stream) {
-    return dg_act_fwd_g(1, &x, &y, n, act, slope, stream);
+extern "C" int dg_act_fwd_g(int groups, const float* const* x, float* const* y, size_t n, int act, float slope, dg_stream_t stream) {
+    return act_fwd("dg_act_fwd_g", groups, x, y, n, act, slope, stream);
 }
-extern "C" int dg_act_bwd_g(int groups, const float* const* dy, const float* const* out, float* const* dx, size_t n, int act, float slope,
-                            dg_stream_t stream) {
-    DG_CHECK_ARG(groups >= 1 && groups <= DG_MAX_GROUPS && dy && out && dx, "dg_act_bwd: bad group / null table");
-    for (int i = 0; i < groups; ++i) DG_CHECK_ARG(dy[i] && out[i] && dx[i], "dg_act_bwd: null pointer");
-    DG_CHECK_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "dg_act_bwd: bad act %d", act);
+extern "C" int dg_act_fwd(const float* x, float* y, size_t n, int act, float slope, dg_stream_t stream) {
+    return act_fwd("dg_act_fwd", 1, &x, &y, n, act, slope, stream);
+}
+// io_bf16 (one problem): bf16 in, bf16 out, n % 8 == 0
+static int act_bwd(const char* who, int groups, const void* const* dy, const void* const* out, void* const* dx, int io_bf16, size_t n, int act,
+                   float slope, dg_stream_t stream) {
+    if (const int rc = act_validate(who, groups, {dy, out, (const void* const*)dx}, act)) return rc;
+    DG_CHECK_ARG(!io_bf16 || n % 8 == 0, "%s: bf16 tensors need n %% 8 == 0 (n=%zu)", who, n);
     if (n == 0) return DG_OK;
-    const long total4 = (long)((n + 3) / 4);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(stream_grid(total4), groups), dim3(256), 0, (hipStream_t)stream, dg_ptrs((const void* const*)dy, groups),
-                       dg_ptrs((const void* const*)out, groups), dg_ptrs((const void* const*)dx, groups), total4, (long)n, act, slope);
+    const long total = (long)(io_bf16 ? n / 8 : (n + 3) / 4);
+    if (io_bf16)
+        hipLaunchKernelGGL(act_bwd16_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy[0], (const __bf16*)out[0],
+                           (__bf16*)dx[0], total, act, slope);
+    else
+        hipLaunchKernelGGL(act_bwd_kernel, dim3(stream_grid(total), groups), dim3(256), 0, (hipStream_t)stream, dg_ptrs(dy, groups), dg_ptrs(out, groups),
+                           dg_ptrs((const void* const*)dx, groups), total, (long)n, act, slope);
     DG_CHECK_LAUNCH("act_bwd");
     return DG_OK;
 }
+extern "C" int dg_act_bwd_g(int groups, const float* const* dy, const float* const* out, float* const* dx, size_t n, int act, float slope,
+                            dg_stream_t stream) {
+    return act_bwd("dg_act_bwd_g", groups, (const void* const*)dy, (const void* const*)out, (void* const*)dx, 0, n, act, slope, stream);
+}
 extern "C" int dg_act_bwd(const float* dy, const float* out, float* dx, size_t n, int act, float slope, dg_stream_t stream) {
-    return dg_act_bwd_g(1, &dy, &out, &dx, n, act, slope, stream);
+    return act_bwd("dg_act_bwd", 1, (const void* const*)&dy, (const void* const*)&out, (void* const*)&dx, 0, n, act, slope, stream);
 }
 extern "C" int dg_act_bwd_t(const void* dy, const void* out, void* dx, int io_bf16, size_t n, int act, float slope, dg_stream_t stream) {
-    if (!io_bf16) return dg_act_bwd((const float*)dy, (const float*)out, (float*)dx, n, act, slope, stream);
-    DG_CHECK_ARG(dy && out && dx, "dg_act_bwd_t: null pointer");
-    DG_CHECK_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "dg_act_bwd_t: bad act %d", act);
-    DG_CHECK_ARG(n % 8 == 0, "dg_act_bwd_t: bf16 tensors need n %% 8 == 0 (n=%zu)", n);
-    if (n == 0) return DG_OK;
-    const long total8 = (long)(n / 8);
-    hipLaunchKernelGGL(act_bwd16_kernel, dim3(stream_grid(total8)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy, (const __bf16*)out,
-                       (__bf16*)dx, total8, act, slope);
-    DG_CHECK_LAUNCH("act_bwd16");
-    return DG_OK;
+    return act_bwd("dg_act_bwd_t", 1, &dy, &out, &dx, io_bf16, n, act, slope, stream);
 }

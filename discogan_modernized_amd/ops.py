@@ -832,43 +832,65 @@ def bn_stats_from_partials(stat, y, running_mean, running_var, nbt, eps, momentu
     return saved
 
 
+def _bn_out(y, planes_cm, planes_only):
+    """The output form of a BatchNorm apply pass (forward or backward) over ``y`` under the current context, with its empty tensors:
+    (form, out, extra, cm, plane_only).
+      "bf16"    bf16 activation storage: bf16 in, bf16 out, nothing else is written
+      "planes"  f32x3 path: the convs after this pass read ``out`` as the plane triple ``extra`` (quad-chunk if cm: its reader is a window
+                input-grad kernel); plane_only: every reader is a plane kernel, the fp32 copy is not written (X3_PLANES_ONLY)
+      "shadow"  bf16 path: ``extra`` is the bf16 shadow of ``out``
+      "plain"   fp32 only"""
+    n, c, h, w = y.shape
+    if _is16(y):
+        return "bf16", empty_nhwc(n, c, h, w, y.device, torch.bfloat16), None, 0, False
+    out = empty_nhwc(n, c, h, w, y.device)
+    if _CUR.x3 and c % 8 == 0:
+        extra = torch.empty((3, out.numel()), device=y.device, dtype=torch.bfloat16)
+        cm = int(bool(planes_cm) and c % 64 == 0 and (n * h * w) % 4 == 0)
+        return "planes", out, extra, cm, bool(planes_only) and X3_PLANES_ONLY
+    if _CUR.shadow and c % 8 == 0:
+        return "shadow", out, empty_nhwc_bf16(n, c, h, w, y.device), 0, False
+    return "plain", out, None, 0, False
+
+
+def _bn_publish(form, out, extra, cm, plane_only):
+    """Make what a BatchNorm pass wrote beside ``out`` known to the convs that read it; returns ``out``."""
+    if form == "planes":
+        planes_put(out, extra, cm)
+        if plane_only:
+            out._dg_planes_only = True
+            if POISON_PLANES_ONLY:
+                out.fill_(float("nan"))
+    elif form == "shadow":
+        shadow_put(out, extra)
+    return out
+
+
+# algorithmic bytes per element of (M, C), by output form (planes_only: "planes" without the fp32 copy)
+_BN_FWD_BYTES = {"bf16": 4.0, "planes": 14.0, "planes_only": 10.0, "shadow": 10.0, "plain": 8.0}
+_BN_BWD_BYTES = {"bf16": 10.0, "planes": 26.0, "planes_only": 22.0, "shadow": 22.0, "plain": 20.0}
+
+
 def bn_act_fwd(y, saved, gamma, beta, act, slope=0.2, planes_cm=False, planes_only=False):
     """planes_cm (f32x3 plane path): write z's plane triple in the quad-chunk layout (its reader is a window input-grad kernel);
     planes_only: every reader of z is a plane kernel -> the fp32 copy is not written (X3_PLANES_ONLY)."""
     _check_dev(y, allow16=True)
     y = as_nhwc(y)
     n, c, h, w = y.shape
-    if _is16(y):                      # bf16 activation storage: bf16 in, bf16 out, nothing else is written
-        z = empty_nhwc(n, c, h, w, y.device, torch.bfloat16)
-        with _hbm("bn_apply", 4.0 * n * h * w * c):
-            _lib.check(_lib.load().dg_bn_act_fwd_t(_ptr(y), _ptr(z), 1, n * h * w, c, _ptr(saved), _ptr(gamma), _ptr(beta),
-                                                   act, slope, _stream()), "dg_bn_act_fwd_t")
-        return z
-    z = empty_nhwc(n, c, h, w, y.device)
-    if _CUR.x3 and c % 8 == 0:             # f32x3 path: the next conv (forward and weight gradient) reads z as a plane triple
-        z3 = torch.empty((3, z.numel()), device=y.device, dtype=torch.bfloat16)
-        with _hbm("bn_apply", (10.0 if (planes_only and X3_PLANES_ONLY) else 14.0) * n * h * w * c):
-            cm = int(bool(planes_cm) and c % 64 == 0 and (n * h * w) % 4 == 0)
-            po = bool(planes_only) and X3_PLANES_ONLY
-            _lib.check(_lib.load().dg_bn_act_fwd_x3(_ptr(y), None if po else _ptr(z), _ptr(z3), z3.stride(0), cm, n * h * w, c, _ptr(saved),
-                                                    _ptr(gamma), _ptr(beta), act, slope, _stream()), "dg_bn_act_fwd_x3")
-        planes_put(z, z3, cm)
-        if po:
-            z._dg_planes_only = True
-            if POISON_PLANES_ONLY:
-                z.fill_(float("nan"))
-        return z
-    if _CUR.shadow and c % 8 == 0:
-        z16 = empty_nhwc_bf16(n, c, h, w, y.device)
-        with _hbm("bn_apply", 10.0 * n * h * w * c):
-            _lib.check(_lib.load().dg_bn_act_fwd_bf16(_ptr(y), _ptr(z), _ptr(z16), n * h * w, c, _ptr(saved), _ptr(gamma), _ptr(beta),
-                                                      act, slope, _stream()), "dg_bn_act_fwd_bf16")
-        shadow_put(z, z16)
-        return z
-    with _hbm("bn_apply", 8.0 * n * h * w * c):
-        _lib.check(_lib.load().dg_bn_act_fwd(_ptr(y), _ptr(z), n * h * w, c, _ptr(saved), _ptr(gamma), _ptr(beta),
-                                             act, slope, _stream()), "dg_bn_act_fwd")
-    return z
+    m = n * h * w
+    form, z, extra, cm, po = _bn_out(y, planes_cm, planes_only)
+    L = _lib.load()
+    rest = (m, c, _ptr(saved), _ptr(gamma), _ptr(beta), act, slope, _stream())
+    with _hbm("bn_apply", _BN_FWD_BYTES["planes_only" if po else form] * m * c):
+        if form == "bf16":
+            _lib.check(L.dg_bn_act_fwd_t(_ptr(y), _ptr(z), 1, *rest), "dg_bn_act_fwd_t")
+        elif form == "planes":
+            _lib.check(L.dg_bn_act_fwd_x3(_ptr(y), None if po else _ptr(z), _ptr(extra), extra.stride(0), cm, *rest), "dg_bn_act_fwd_x3")
+        elif form == "shadow":
+            _lib.check(L.dg_bn_act_fwd_bf16(_ptr(y), _ptr(z), _ptr(extra), *rest), "dg_bn_act_fwd_bf16")
+        else:
+            _lib.check(L.dg_bn_act_fwd(_ptr(y), _ptr(z), *rest), "dg_bn_act_fwd")
+    return _bn_publish(form, z, extra, cm, po)
 
 
 def bn_act_bwd(dz, y, saved, gamma, beta, act, slope=0.2, need_param_grads=True, out_grads=None, planes_cm=False, planes_only=False):
@@ -888,39 +910,20 @@ def bn_act_bwd(dz, y, saved, gamma, beta, act, slope=0.2, need_param_grads=True,
         dbeta = torch.empty(c, device=y.device, dtype=torch.float32) if need_param_grads else None
     L = _lib.load()
     ws, wsb = _ws(L.dg_bn_workspace_bytes(m, c), y.device)
-    if _is16(y):
-        if not _is16(dz):
-            raise _lib.DiscoganHipError("bn_act_bwd: bf16 y needs a bf16 dz")
-        dy = empty_nhwc(n, c, h, w, y.device, torch.bfloat16)
-        with _hbm("bn_backward", 10.0 * m * c):
-            _lib.check(L.dg_bn_act_bwd_t(_ptr(dz), _ptr(y), _ptr(dy), 1, m, c, _ptr(saved), _ptr(gamma), _ptr(beta), act,
-                                         slope, _ptr(dgamma), _ptr(dbeta), acc, _ptr(ws), wsb, _stream()), "dg_bn_act_bwd_t")
-        return dy, dgamma, dbeta
-    dy = empty_nhwc(n, c, h, w, y.device)
-    if _CUR.x3 and c % 8 == 0:             # f32x3 path: dy goes to the layer's input-gradient and weight-gradient convs as a plane triple
-        dy3 = torch.empty((3, dy.numel()), device=y.device, dtype=torch.bfloat16)
-        po = bool(planes_only) and X3_PLANES_ONLY
-        with _hbm("bn_backward", (22.0 if po else 26.0) * m * c):
-            cm = int(bool(planes_cm) and c % 64 == 0 and m % 4 == 0)
-            _lib.check(L.dg_bn_act_bwd_x3(_ptr(dz), _ptr(y), None if po else _ptr(dy), _ptr(dy3), dy3.stride(0), cm, m, c, _ptr(saved), _ptr(gamma),
-                                          _ptr(beta), act, slope, _ptr(dgamma), _ptr(dbeta), acc, _ptr(ws), wsb, _stream()), "dg_bn_act_bwd_x3")
-        planes_put(dy, dy3, cm)
-        if po:
-            dy._dg_planes_only = True
-            if POISON_PLANES_ONLY:
-                dy.fill_(float("nan"))
-        return dy, dgamma, dbeta
-    if _CUR.shadow and c % 8 == 0:
-        dy16 = empty_nhwc_bf16(n, c, h, w, y.device)
-        with _hbm("bn_backward", 22.0 * m * c):
-            _lib.check(L.dg_bn_act_bwd_bf16(_ptr(dz), _ptr(y), _ptr(dy), _ptr(dy16), m, c, _ptr(saved), _ptr(gamma), _ptr(beta), act,
-                                            slope, _ptr(dgamma), _ptr(dbeta), acc, _ptr(ws), wsb, _stream()), "dg_bn_act_bwd_bf16")
-        shadow_put(dy, dy16)
-        return dy, dgamma, dbeta
-    with _hbm("bn_backward", 20.0 * m * c):
-        _lib.check(L.dg_bn_act_bwd(_ptr(dz), _ptr(y), _ptr(dy), m, c, _ptr(saved), _ptr(gamma), _ptr(beta), act, slope,
-                                   _ptr(dgamma), _ptr(dbeta), acc, _ptr(ws), wsb, _stream()), "dg_bn_act_bwd")
-    return dy, dgamma, dbeta
+    if _is16(y) and not _is16(dz):
+        raise _lib.DiscoganHipError("bn_act_bwd: bf16 y needs a bf16 dz")
+    form, dy, extra, cm, po = _bn_out(y, planes_cm, planes_only)
+    rest = (m, c, _ptr(saved), _ptr(gamma), _ptr(beta), act, slope, _ptr(dgamma), _ptr(dbeta), acc, _ptr(ws), wsb, _stream())
+    with _hbm("bn_backward", _BN_BWD_BYTES["planes_only" if po else form] * m * c):
+        if form == "bf16":
+            _lib.check(L.dg_bn_act_bwd_t(_ptr(dz), _ptr(y), _ptr(dy), 1, *rest), "dg_bn_act_bwd_t")
+        elif form == "planes":
+            _lib.check(L.dg_bn_act_bwd_x3(_ptr(dz), _ptr(y), None if po else _ptr(dy), _ptr(extra), extra.stride(0), cm, *rest), "dg_bn_act_bwd_x3")
+        elif form == "shadow":
+            _lib.check(L.dg_bn_act_bwd_bf16(_ptr(dz), _ptr(y), _ptr(dy), _ptr(extra), *rest), "dg_bn_act_bwd_bf16")
+        else:
+            _lib.check(L.dg_bn_act_bwd(_ptr(dz), _ptr(y), _ptr(dy), *rest), "dg_bn_act_bwd")
+    return _bn_publish(form, dy, extra, cm, po), dgamma, dbeta
 
 
 def _dense_like(x):

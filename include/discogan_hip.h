@@ -84,7 +84,7 @@ const char* dg_last_error(void);
  * "bf16" 2: fp32-accurate products from three bf16 planes per operand (f32x3);
  * "no_dma" 1: convolutions with two bf16 operands stay on the register-staged tiles instead of the LDS-DMA kernel;
  * "bn_items" 1: the fp32 BatchNorm apply passes (forward and backward) on the per-item kernels instead of the row-geometry ones
- *   (same results bit for bit; same-box A/B and the test that says so);
+ *   (same results bit for bit; same-box A/B and the test that says so); read once per call, where a dg_bn_act_* call enters the library;
  * "dma_mfma" 32: the LDS-DMA kernel's 32x32x16 body instead of the default 16x16x32 one; 1: keep the input-grads with <= 128
  *   output channels on the register-staged tiles instead of the window kernels (same-box A/B);
  * (experiments library only, csrc/Makefile EXPERIMENTS=1: "x3_mfma" 16 = the paired-plane 16x16x32 body of the f32x3 plane kernel,

@@ -193,6 +193,139 @@ def test_edge_entry_points_refuse_what_the_recorded_table_says():
             assert got == w, f"{label} (process default arithmetic {default}): {got}, recorded {w}"
 
 
+# ---- every BatchNorm / activation entry point: what it refuses before any launch ----------------------------------------------------
+BN_REFUSALS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bn_refusals.json")
+_BN_FWD = "M C saved gamma beta act slope stream"
+_BN_BWD = "M C saved gamma beta act slope dgamma dbeta accumulate ws ws_bytes stream"
+_BN_STATS = "M C eps momentum rmean rvar nbt saved ws ws_bytes stream"
+# parameter names of the entry points, in ABI order
+BN_PARAMS = {
+    "dg_bn_train_stats": "y " + _BN_STATS,
+    "dg_bn_train_stats_t": "y bf16 " + _BN_STATS,
+    "dg_bn_train_stats_g": "groups share y " + _BN_STATS,
+    "dg_bn_act_fwd": "y z " + _BN_FWD,
+    "dg_bn_act_fwd_g": "groups y z " + _BN_FWD,
+    "dg_bn_act_fwd_bf16": "y z shadow " + _BN_FWD,
+    "dg_bn_act_fwd_x3": "y z planes plane_elems plane_layout " + _BN_FWD,
+    "dg_bn_act_fwd_t": "y z bf16 " + _BN_FWD,
+    "dg_bn_act_bwd": "dz y dy " + _BN_BWD,
+    "dg_bn_act_bwd_g": "groups share dz y dy " + _BN_BWD,
+    "dg_bn_act_bwd_bf16": "dz y dy shadow " + _BN_BWD,
+    "dg_bn_act_bwd_x3": "dz y dy planes plane_elems plane_layout " + _BN_BWD,
+    "dg_bn_act_bwd_t": "dz y dy bf16 " + _BN_BWD,
+    "dg_act_fwd": "x out n act slope stream",
+    "dg_act_fwd_g": "groups x out n act slope stream",
+    "dg_act_bwd": "dy out dx n act slope stream",
+    "dg_act_bwd_g": "groups dy out dx n act slope stream",
+    "dg_act_bwd_t": "dy out dx bf16 n act slope stream",
+}
+BN_POINTERS = ("x", "y", "z", "dz", "dy", "dx", "out", "shadow", "planes", "saved", "gamma", "beta", "rmean", "rvar", "nbt", "dgamma", "dbeta", "ws")
+BN_OPTIONAL = ("rmean", "rvar", "nbt", "dgamma", "dbeta")          # null is allowed: such a call would launch
+
+
+def bn_refusal_cases():
+    """(label, entry point, {parameter: value} over the accepted base call) for argument tuples that the BatchNorm and activation
+    entry points must refuse before they launch anything.  The base call is (M, C) = (16, 64) fp32 with LeakyReLU, n = 64 for the
+    stand-alone activations, two problems for the grouped forms, pixel-major planes M * C elements apart, a large enough workspace.
+    Pointer values as in edge_refusal_cases(); "short" is one byte less than dg_bn_workspace_bytes of the BASE shape."""
+    cases = []
+
+    def add(what, entry, over):
+        if all(k in BN_PARAMS[entry].split() for k in over):
+            cases.append((f"{entry}: {what}", entry, dict(over)))
+
+    for entry, params in BN_PARAMS.items():
+        names = params.split()
+        bn, grouped = entry.startswith("dg_bn_"), entry.endswith("_g")
+        stats = "train_stats" in entry
+        for g in (0, 5):
+            add(f"groups {g}", entry, dict(groups=g))
+        add("share 3 of 4 problems", entry, dict(groups=4, share=3))
+        for ptr in ("rmean", "dgamma", "dbeta"):
+            add(f"mismatched {ptr} in a share set", entry, {"share": 2, ptr: "mixed"})
+        for ptr in BN_POINTERS:
+            plane_only = ptr in ("z", "dy") and entry.endswith("_x3")                # accepted: the plane triple is then the only output
+            if ptr in names and ptr not in BN_OPTIONAL and not plane_only:
+                add(f"null {ptr}", entry, {ptr: None})
+                if grouped:
+                    add(f"null entry in {ptr}", entry, {ptr: "hole"})
+        if stats:
+            add("M 1", entry, dict(M=1))
+        for C in (0, 2, 6):
+            add(f"C {C}", entry, dict(C=C))
+        for C in (4, 12):
+            add(f"bf16 storage at C {C}", entry, dict(bf16=1, C=C))
+        if not stats:
+            for act in ((-1, 3, 4) if bn else (-1, 4)):
+                add(f"bad act {act}", entry, dict(act=act))
+        add("short ws", entry, dict(ws_bytes="short"))
+        add("short ws at bf16 storage", entry, dict(ws_bytes="short", bf16=1))
+        for what, over in (("C 6", dict(C=6)), ("bad act 3", dict(act=3)), ("null y", dict(y=None))):
+            if bn and not (stats and "act" in over):
+                add(f"null ws and {what}", entry, dict(ws=None, **over))
+                add(f"short ws and {what}", entry, dict(ws_bytes="short", **over))
+        add("plane_layout 2", entry, dict(plane_layout=2))
+        add("plane distance too small", entry, dict(plane_elems=16 * 64 - 8))
+        add("plane distance no multiple of 8", entry, dict(plane_elems=16 * 64 + 4))
+        add("quad-chunk planes at C 32", entry, dict(plane_layout=1, C=32))
+        add("quad-chunk planes at M 18", entry, dict(plane_layout=1, M=18, plane_elems=18 * 64))
+        add("null planes and no fp32 output", entry, dict(planes=None, z=None))
+        add("null planes and no fp32 output", entry, dict(planes=None, dy=None))
+    add("bf16 tensors, n 68", "dg_act_bwd_t", dict(bf16=1, n=68))
+    add("bf16 tensors, null dx", "dg_act_bwd_t", dict(bf16=1, dx=None))
+    add("bf16 tensors, bad act 4", "dg_act_bwd_t", dict(bf16=1, act=4))
+    return cases
+
+
+def _bn_call(L, entry, over):
+    P = ctypes.c_void_p
+    tables = dict(ptr=(P * 4)(8, 8, 8, 8), hole=(P * 4)(8, None, 8, 8), mixed=(P * 4)(8, 16, 8, 8))
+    v = dict(M=16, C=64, n=64, act=ops.ACT_LEAKY, slope=0.2, eps=1e-5, momentum=0.1, bf16=0, groups=2, share=1, accumulate=0,
+             plane_elems=16 * 64, plane_layout=0, ws_bytes=1 << 20, stream=None, **{p: "ptr" for p in BN_POINTERS})
+    v.update(over)
+    if v["ws_bytes"] == "short":
+        v["ws_bytes"] = L.dg_bn_workspace_bytes(16, 64) - 1
+    for p in BN_POINTERS:
+        if v[p] is not None:
+            v[p] = tables[v[p]] if entry.endswith("_g") else P(dict(ptr=8, ptr2=16)[v[p]])
+    return getattr(L, entry)(*[v[n] for n in BN_PARAMS[entry].split()])
+
+
+def bn_refusal_codes(L):
+    """The return code of every case of bn_refusal_cases(), under option "bn_items" 0 and 1: {"0": [...], "1": [...]}."""
+    codes = {}
+    try:
+        for items in (0, 1):
+            _lib.set_option("bn_items", items)
+            codes[str(items)] = [_bn_call(L, entry, over) for label, entry, over in bn_refusal_cases()]
+    finally:
+        _lib.set_option("bn_items", 0)
+    return codes
+
+
+def test_bn_entry_points_refuse_what_the_recorded_table_says():
+    """tests/golden/bn_refusals.json holds the return code of every dg_bn_* / dg_act_* entry point for argument tuples that are
+    refused before any launch, written from the library of the commit BEFORE the BatchNorm host code was rewritten around one call
+    record per pass (tests/golden/make_bn_refusals.py).  The library must still give exactly these codes: DG_ERR_INVALID (-1) or
+    DG_ERR_WORKSPACE (-2), whatever option "bn_items" says.  A stand-alone activation over no elements succeeds without a launch."""
+    with open(BN_REFUSALS) as f:
+        table = json.load(f)
+    cases = bn_refusal_cases()
+    assert table["cases"] == [c[0] for c in cases] and len(set(table["cases"])) == len(cases)
+    assert {c[1] for c in cases} == set(BN_PARAMS)
+    L = _lib.load()
+    codes = bn_refusal_codes(L)
+    assert sorted(codes) == sorted(table["codes"]) == ["0", "1"]
+    for items, want in table["codes"].items():
+        assert len(want) == len(cases) and all(c in (-1, -2) for c in want)
+        for label, got, w in zip(table["cases"], codes[items], want):
+            assert got == w, f"{label} (bn_items {items}): {got}, recorded {w}"
+    for entry in BN_PARAMS:
+        if entry.startswith("dg_act_"):
+            for bf16 in (0, 1):
+                assert _bn_call(L, entry, dict(n=0, bf16=bf16)) == 0, (entry, bf16)
+
+
 @pytest.mark.parametrize("N,fits", [(65535, True), (65536, False)])
 def test_plans_drop_bf16_and_plane_kernels_at_2gib_per_plane(N, fits):
     """16 x 16 x 64 fp32 images with K = 256: a bf16 shadow / plane of x and dy reaches 2^31 bytes at N = 65536, and the plan then
