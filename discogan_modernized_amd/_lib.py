@@ -33,6 +33,7 @@ SIGNATURES = {
     "dg_conv_workspace_bytes_p": (_z, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "dg_conv_bnstats_rows_p": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "dg_conv_plan_splits_p": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "dg_conv_plan_describe": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _i]),
     "dg_conv_fwd_g": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _z, _p]),
     "dg_conv_dgrad_g": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _z, _p]),
     "dg_conv_wgrad_g": (_i, [_i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),

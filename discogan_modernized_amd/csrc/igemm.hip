@@ -1022,10 +1022,27 @@ __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const IgemmArg
     }
 }
 
+// the sum of one output vector's slabs: in slab order, or (lanes) in splitk_reduce_small_kernel's order -- lane u sums slabs u, u + 16,
+// ..., then the lane sums are added in lane order
+__device__ __forceinline__ f32x4 dg_sum_slabs(const float* src, long slab, int splits, bool lanes) {
+    if (!lanes) {
+        f32x4 v = *(const f32x4*)src;
+        for (int k = 1; k < splits; ++k) v += *(const f32x4*)(src + k * slab);
+        return v;
+    }
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < 16 && u < splits; ++u) {
+        f32x4 t = {0.f, 0.f, 0.f, 0.f};
+        for (int k = u; k < splits; k += 16) t += *(const f32x4*)(src + k * slab);
+        v = u == 0 ? t : v + t;
+    }
+    return v;
+}
+
 // Split-K reduction that also emits the BatchNorm partial rows: block = 32 float4 columns x 8 row lanes,
-// grid = (column chunks of 128, row chunks); one partial row per row chunk.
+// grid = (column chunks of 128, row chunks); one partial row per row chunk.  lanes: sum the slabs in the lane kernel's order (run_plan).
 template <int MODE>
-__global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const IgemmArgs p, int rchunks) {
+__global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const IgemmArgs p, int rchunks, int lanes) {
     __shared__ f32x4 red[2][8][32];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int grp = blockIdx.z;                         // grouped launch: problem index
@@ -1040,13 +1057,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const IgemmArg
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
     const bool cok = c < p.Ng;
     if (cok && r0 < r1) {
-        const float* src = pPart + r0 * p.Ng + c;
-        sh = *(const f32x4*)src;
-        for (int k = 1; k < p.splits; ++k) sh += *(const f32x4*)(src + k * slab);
+        sh = dg_sum_slabs(pPart + r0 * p.Ng + c, slab, p.splits, lanes != 0);
         for (long row = r0 + ty; row < r1; row += 8) {
-            const float* sp = pPart + row * p.Ng + c;
-            f32x4 v = *(const f32x4*)sp;
-            for (int k = 1; k < p.splits; ++k) v += *(const f32x4*)(sp + k * slab);
+            const f32x4 v = dg_sum_slabs(pPart + row * p.Ng + c, slab, p.splits, lanes != 0);
             long eoff;
             if (MODE == MODE_DGRAD_S2) {
                 const int parity = (int)(row / p.M);
@@ -1208,7 +1221,8 @@ struct Plan {
                      // 3: igemm_dma_x3_dgw.hip (plane operands, input-grad with few output channels: `ncls` parity classes per
                      //    workgroup, gradient window in LDS)
                      // 4: igemm_dma_dgw.hip (bf16 operands, the same input-grad scheme with a 32-deep K-step)
-    int ncls;
+    int ncls;        // parity classes per workgroup of the two window input-grad kernels (dma 3 / 4; 0 elsewhere)
+    int bm, bn, zmul;   // the tile's rows and columns, workgroups per (row tile, column tile, split): 4 parity classes or 1
 };
 
 int dg_igemm_dma_launch(int mode, const IgemmArgs& a, int zmul, hipStream_t st);      // igemm_dma.hip
@@ -1311,6 +1325,7 @@ static void make_plan(const PlanReq& rq, Plan* pl) {
     // LDS-DMA kernel (igemm_dma.hip): both operands are bf16 tensors, the 256-wide tile is at least 3/4 used in both
     // directions, whole 64-deep K-tiles per tap.  One 512-thread workgroup per CU: the split grid aims for 256 workgroups.
     pl->dma = 0;
+    pl->ncls = 0;
     if (a.prec == 1 && a16 && b16 && dg_get_option(DG_OPT_NO_DMA) == 0 && pl->kt == 64 && a.Ng >= 192 && a.M >= 192 &&
         g.C % 8 == 0 && g.K % 8 == 0 &&
         ((pl->mode == MODE_FWD && g.C % 64 == 0) || (pl->mode == MODE_DGRAD_S2 && g.K % 64 == 0) || pl->mode == MODE_WGRAD))
@@ -1357,6 +1372,7 @@ static void make_plan(const PlanReq& rq, Plan* pl) {
     const int BN = pl->dma == 2 ? 64 * pl->wn : (pl->dma >= 3 ? a.Ng : (pl->dma ? 256 : 64 * pl->wn));
     a.tilesM = (a.M + BM - 1) / BM;
     a.tilesN = (a.Ng + BN - 1) / BN;
+    pl->bm = BM; pl->bn = BN; pl->zmul = zmul;
     // workgroups of the launch before any K split; a grouped launch planned as a whole (plan_groups of the *_g entry points) counts all
     // its problems: the chip is filled by the group, each problem needs fewer splits (fewer slabs written and re-read)
     const int base = a.tilesM * a.tilesN * (pl->dma >= 3 ? 4 / pl->ncls : zmul) * (pl->dma ? 1 : rq.plan_groups);
@@ -1471,17 +1487,26 @@ static int run_plan(const char* who, Plan& pl, hipStream_t st) {
     }
     DG_CHECK_LAUNCH(who);
     }
+    // Two orders of summing an output vector's slabs: slab order (splitk_reduce_kernel, splitk_reduce_stats_kernel) and the lane kernel's --
+    // sixteen interleaved lanes of slabs, then the lanes (small outputs cut into many slabs).  Up to sixteen slabs they are the same sum;
+    // past that they differ in the last bits, and a plan that can emit statistics must give the same bits whether or not the call asks
+    // for them.  So such a plan has ONE order, that of the form its trainer uses: bf16 and plane operands always ask for statistics
+    // (slab order, the lane kernel stands back); fp32 tensors ask only in launches far too large for the lane kernel (its order, which
+    // the statistics reduction then follows).
+    const long total4 = (long)zmul * a.M * a.Ng / 4;
+    const bool many = pl.stat_rows > 0 && a.splits > 16;
+    const bool slab_order = many && (a.prec == 1 || a.a16 == 3);
+    const bool lanes = pl.mode != MODE_DGRAD_S2 && a.splits >= 8 && total4 <= 65536 && !slab_order;
     if (a.splits > 1 && a.stat != nullptr) {
         const int rc = pl.stat_rows;
         dim3 grid((a.Ng + 127) / 128, rc, ngrp);
-        if (pl.mode == MODE_DGRAD_S2) hipLaunchKernelGGL(splitk_reduce_stats_kernel<MODE_DGRAD_S2>, grid, dim3(256), 0, st, a, rc);
-        else hipLaunchKernelGGL(splitk_reduce_stats_kernel<MODE_FWD>, grid, dim3(256), 0, st, a, rc);
+        if (pl.mode == MODE_DGRAD_S2) hipLaunchKernelGGL(splitk_reduce_stats_kernel<MODE_DGRAD_S2>, grid, dim3(256), 0, st, a, rc, 0);
+        else hipLaunchKernelGGL(splitk_reduce_stats_kernel<MODE_FWD>, grid, dim3(256), 0, st, a, rc, (lanes && many) ? 1 : 0);
         DG_CHECK_LAUNCH("splitk_reduce_stats");
     } else if (a.splits > 1) {
-        const long total4 = (long)zmul * a.M * a.Ng / 4;
         int grid = (int)((total4 + 255) / 256);
         if (grid > 4096) grid = 4096;
-        if (pl.mode != MODE_DGRAD_S2 && a.splits >= 8 && total4 <= 65536) {
+        if (lanes) {
             hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((unsigned)((total4 + 15) / 16), 1, nout), dim3(256), 0, st, a, total4);
             DG_CHECK_LAUNCH("splitk_reduce_small");
             return DG_OK;
@@ -1580,6 +1605,19 @@ extern "C" int dg_conv_x3_planes_ok(int op, int N, int H, int W, int C, int K, i
     if (!query_plan("dg_conv_x3_planes_ok", op, N, H, W, C, K, stride, pad, DG_PREC_F32X3, 1, 3, 3, &pl)) return 0;
     if (pl.dma == 0 && x3_register_staged_planes_ok(op, pl)) return 4;
     return pl.dma == 5 ? 3 : (pl.dma == 3 ? (K % 64 == 0 ? 2 : 1) : (pl.dma == 2 ? 1 : 0));
+}
+// The plan of one request, field by field, for tests that must know which code a shape runs (host only: no device call; nothing in
+// the product path asks).  Same query_plan / make_plan and the same options as a launch.  Writes the first n_out of DG_PLAN_FIELDS
+// ints (order: include/discogan_hip.h) and returns DG_PLAN_FIELDS; a request without a plan returns 0 and writes nothing.
+extern "C" int dg_conv_plan_describe(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups, int a_form, int b_form,
+                                     int* out, int n_out) {
+    Plan pl;
+    if (!query_plan("dg_conv_plan_describe", op, N, H, W, C, K, stride, pad, prec, plan_groups, a_form, b_form, &pl)) return 0;
+    const IgemmArgs& a = pl.a;
+    const int f[DG_PLAN_FIELDS] = {pl.mode, a.prec, pl.wm, pl.wn, pl.kt, pl.dma, pl.ncls, a.M, a.Ng, pl.bm, pl.bn, a.tilesM, a.tilesN, pl.zmul,
+                                   a.nIt, a.splits, a.itPerSplit, a.xcd_group, pl.stat_rows, (a.abytes != 0 && a.bbytes != 0) ? 0 : 1};
+    for (int i = 0; i < DG_PLAN_FIELDS && i < n_out && out != nullptr; ++i) out[i] = f[i];
+    return DG_PLAN_FIELDS;
 }
 
 // ---- one conv call ---------------------------------------------------------------------------------------------------------

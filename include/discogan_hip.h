@@ -127,6 +127,20 @@ int dg_conv_wgrad(const float* dy, const float* x, float* dw, int N, int H, int 
 size_t dg_conv_workspace_bytes_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups);
 int dg_conv_bnstats_rows_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec);
 int dg_conv_plan_splits_p(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups);
+/* The whole plan of one request, for tests that must know which code a shape runs (host only: no device call; nothing in the product path
+ * asks).  a_form / b_form: 0 fp32 tensor, 1 bf16 tensor, 3 three bf16 planes.  The same planner and the same options as a launch (splitk, kt,
+ * no_dma, dma_mfma, pointer_path, no_xcd_group, target_wgs, split_below).  Returns DG_PLAN_FIELDS and writes the first n_out fields, in this
+ * order:  0 mode (0 forward, 1 stride-2 input gradient, 2 plain-GEMM input gradient of the 4x4 layers, 3 weight gradient)   1 the arithmetic
+ * actually used (DG_PREC_*: exact fp32 where the asked-for one has no kernel for the shape)   2 wm  3 wn (waves per tile)   4 kt (K-tile)
+ * 5 kernel family (0 register-staged tiles, 1 bf16 LDS-DMA, 2 f32x3 plane, 3 f32x3 window input gradient, 4 bf16 window input gradient)
+ * 6 ncls (parity classes per workgroup of the window kernels, else 0)   7 M  8 Ng (GEMM rows, columns)   9 BM  10 BN (tile)   11 tilesM
+ * 12 tilesN   13 zmul (4 parity classes of the stride-2 input gradient, else 1)   14 nIt (K-tiles)   15 splits   16 itPerSplit
+ * 17 xcd_group (blockIdx-to-tile order 0..3; the two window kernels ignore it)   18 stat_rows (partial rows of the fused BatchNorm
+ * statistics, 0: none)   19 addressing (0 buffer descriptors, 1 64-bit pointers).  A request without a plan (see above) returns 0 and
+ * writes nothing. */
+#define DG_PLAN_FIELDS 20
+int dg_conv_plan_describe(int op, int N, int H, int W, int C, int K, int stride, int pad, int prec, int plan_groups, int a_form, int b_form,
+                          int* out, int n_out);
 int dg_conv_fwd_g(int groups, const float* const* x, const float* const* w, float* const* y, int N, int H, int W, int C, int K, int stride,
                   int pad, int prec, int plan_groups, float* const* stat, size_t stat_floats, void* const* ws, size_t ws_bytes, dg_stream_t stream);
 int dg_conv_dgrad_g(int groups, const float* const* dy, const float* const* w, float* const* dx, int N, int H, int W, int C, int K, int stride,

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from discogan_modernized_amd import _lib, functional as F, model, ops  # noqa: E402
 from tests import shape_ref as R  # noqa: E402
-from tests.gpu_util import DEV, ambient, krsc, nhwc, options, with_shadow  # noqa: E402
+from tests.gpu_util import DEV, ambient, conv_operands, krsc, nhwc, options, with_shadow  # noqa: E402
 from tests.shape_ref import rnd  # noqa: E402
 
 ACTS = {"leaky": ops.ACT_LEAKY, "relu": ops.ACT_RELU, "none": ops.ACT_NONE}
@@ -223,15 +223,8 @@ def test_conv_non_square(form, shape):
     prec = {"x3": 2, "x3dgw": 2}.get(form, 1 if bf else 0)
     with options(bf16=prec, pointer_path=int(form == "ptr")), ambient(shadow=form in ("dma", "bf16dgw", "bf16io"), act16=out16,
                                                                         x3=form.startswith("x3")):
-        if out16:
-            xg, dyg = nhwc(x, torch.bfloat16), nhwc(dy, torch.bfloat16)
-        elif form in ("dma", "bf16dgw"):
-            xg, dyg = with_shadow(nhwc(x)), with_shadow(nhwc(dy))
-        else:
-            xg, dyg = nhwc(x), nhwc(dy)
-        wg = krsc(w)
-        if bf:
-            with_shadow(wg)
+        shadowed = form in ("dma", "bf16dgw")
+        xg, wg, dyg = conv_operands(x, w, dy, act16=out16, shadow_x=shadowed, shadow_dy=shadowed, shadow_w=bf)
         y = ops.conv_fwd(xg, wg, 2, 1)
         dx = ops.conv_dgrad(dyg, wg, (H, W), 2, 1)
         dw = ops.conv_wgrad(dyg, xg, 2, 1)
