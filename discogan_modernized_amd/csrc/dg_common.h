@@ -93,6 +93,10 @@ __device__ __forceinline__ float dg_apply_act(float u, int act, float slope) {
     return u;
 }
 
+// BatchNorm apply, gs = gamma * invstd (one fp32 product): norm_act.hip's kernels, and the 3-channel kernels of edge.hip that apply the
+// last decoder BatchNorm + ReLU to the values they load (BNL) -- one text, so the two agree bit for bit
+__device__ __forceinline__ float bn_norm(float y, float mean, float gs, float beta) { return fmaf(y - mean, gs, beta); }
+
 // fp32 -> three bf16 planes (the "f32x3" operand form of igemm.hip PREC 2 / igemm_dma_x3.hip): hi = bf16(v) (RNE),
 // mid = bf16(v - hi), lo = bf16(v - hi - mid); both subtractions are exact in fp32, hi + mid + lo carries 24 significand bits
 __device__ __forceinline__ void dg_split3(const f32x4& v, dg_bf16x4_t& hi, dg_bf16x4_t& mid, dg_bf16x4_t& lo) {

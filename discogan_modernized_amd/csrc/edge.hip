@@ -203,7 +203,13 @@ __global__ __launch_bounds__(256, 2) void c3_dgrad_mfma_kernel(const float* __re
 // the end of the current tile (one more set of 32 registers, not two) -- instead of a stand-alone act_bwd pass that reads both tensors
 // and writes a third (12 B per element at fp32) in front of this kernel.  Same expression as act_bwd_kernel / act_bwd16_kernel (bf16: fp32
 // product rounded to bf16, RNE): the input-gradient is bitwise the unfused one.
-template <bool IN16, bool MF16 = false, bool X3 = false, bool FACT = false>
+// BNL (fp32 dy, plain or X3; dg_conv4x4s2_c3_dgrad_bn_p): dy is the RAW input y of the decoder's last BatchNorm + ReLU and every value fetched becomes
+// relu(bn_norm(y, mean[k], gamma[k] * invstd[k], beta[k])) at the head of its tile -- the expression of bn_act_fwd_rows_kernel on the values this
+// kernel loads anyway, instead of a pass that reads y and writes z (and, on the f32x3 path, a plane triple nobody reads) in front of it.  The three
+// constants per channel sit in LDS (768 bytes): 48 more registers per lane would not fit beside areg, breg3 and acc at two workgroups per CU.
+// Out-of-image pixels are selected to 0 on fetch's own predicate -- they are the transposed conv's zero padding, not bn(0).  `aos` carries
+// (saved = [mean | invstd], gamma, beta) in its first three slots; nothing is added to the argument list, so the other forms compile to the code they had.
+template <bool IN16, bool MF16 = false, bool X3 = false, bool FACT = false, bool BNL = false>
 __global__ __launch_bounds__(256, 2) void c3_dgrad_scatter_kernel(const DgPtrs dys, const DgPtrs ws_, const DgPtrs dxs, int N, int H, int W, int act,
                                                                   int tiles_r, int tiles_c, int ntiles, unsigned dybytes, const DgPtrs aos, float slope) {
     // grouped launch (dg_conv4x4s2_c3_dgrad_g): blockIdx.y = problem
@@ -212,9 +218,11 @@ __global__ __launch_bounds__(256, 2) void c3_dgrad_scatter_kernel(const DgPtrs d
     float* __restrict__ dx = dg_pick<float>(dxs, blockIdx.y);
     static_assert(!MF16 || IN16, "the bf16 MFMA form takes a bf16 dy");
     static_assert(!X3 || (!IN16 && !MF16), "the f32x3 form takes an fp32 dy");
+    static_assert(!BNL || (!IN16 && !FACT), "the on-load BatchNorm form takes an fp32 dy and fuses nothing else");
     typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
     typedef float f32x8_d __attribute__((ext_vector_type(8)));
     __shared__ __attribute__((aligned(16))) float Ps[CS_PR * CS_PC * CS_LDP];
+    __shared__ __attribute__((aligned(16))) float bnS[BNL ? 3 * CD_K : 4];      // BNL: [mean | gamma * invstd | beta][64]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p = lane & 15, kq = lane >> 4;
     const int Ho = H >> 1, Wo = W >> 1;
@@ -302,11 +310,43 @@ __global__ __launch_bounds__(256, 2) void c3_dgrad_scatter_kernel(const DgPtrs d
     };
     fetch(blockIdx.x, 0);
     apply_act(0);
+    if constexpr (BNL) {
+        const float* saved = (const float*)aos.p[0];
+        if (tid < CD_K) {
+            bnS[tid] = saved[tid];
+            bnS[CD_K + tid] = ((const float*)aos.p[1])[tid] * saved[CD_K + tid];
+            bnS[2 * CD_K + tid] = ((const float*)aos.p[2])[tid];
+        }
+        __syncthreads();
+    }
+    // BNL: areg[set] (tile t) <- relu(bn(areg[set])) where the pixel is inside the image, 0 where it is padding
+    auto apply_bn = [&](int t, int set) {
+        if constexpr (BNL) {
+            const int tc = t % tiles_c, tr = (t / tiles_c) % tiles_r;
+            const int b = tc * CS_TC - 1 + p;
+            bool ok[2];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) ok[g] = (unsigned)(tr * CS_TR - 1 + wave + 4 * g) < (unsigned)Ho && (unsigned)b < (unsigned)Wo;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k0 = X3 ? 32 * (j >> 1) + 8 * kq + 4 * (j & 1) : 16 * kq + 4 * j;       // fetch's channel order
+                const f32x4 mean = *(const f32x4*)(bnS + k0), gs = *(const f32x4*)(bnS + CD_K + k0), beta = *(const f32x4*)(bnS + 2 * CD_K + k0);
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float z = dg_apply_act(bn_norm(areg[set][g][j][e], mean[e], gs[e], beta[e]), DG_ACT_RELU, 0.f);
+                        areg[set][g][j][e] = ok[g] ? z : 0.f;
+                    }
+            }
+        }
+    };
     auto tile = [&](auto SB, int t) {
         constexpr int S = decltype(SB)::value;
         const int tc = t % tiles_c, tr = (t / tiles_c) % tiles_r, n = t / (tiles_c * tiles_r);
         const int a0 = tr * CS_TR, b0 = tc * CS_TC;
         fetch(t + gridDim.x, S ^ 1);             // next tile's rows fly under this tile's MFMAs
+        apply_bn(t, S);
         f32x4 acc[2][3];
 #pragma unroll
         for (int g = 0; g < 2; ++g)
@@ -416,6 +456,7 @@ struct C3Dgrad {
     int dy_bf16, N, H, W, K, act, prec;
     const void* act_out;                    // fused LeakyReLU backward on dy (one problem): the layer's saved output, nullptr: none,
     float slope;                            // and its slope
+    const float *bn_saved, *bn_gamma, *bn_beta;   // on-load BatchNorm + ReLU (one problem): dy is the BatchNorm's input; nullptr: none
     void* ws;                               // the gather form's weight image
     size_t ws_bytes;
     hipStream_t st;
@@ -465,6 +506,29 @@ extern "C" int dg_conv4x4s2_c3_dgrad_g(int groups, const float* const* dy_nhwc, 
 static bool c3_dgrad_scatter_fits(int N, int H, int W, int K, int dy_bf16) {
     return K == CD_K && N >= 1 && (long)N * (H / 2) * (W / 2) * CD_K * (dy_bf16 ? 2 : 4) < (1L << 31);
 }
+// The on-load BatchNorm forms run in fp32 storage under the exact-fp32 and the f32x3 arithmetic
+static bool c3_bn_prec_ok(int prec) {
+    const int p = dg_resolve_prec(prec);
+    return prec >= DG_PREC_DEFAULT && (p == DG_PREC_F32 || p == DG_PREC_F32X3);
+}
+// 1 when dg_conv4x4s2_c3_dgrad_bn_p exists for this problem under the options in force: the scatter kernel on an fp32 y (K == 64, y under
+// 2^31 bytes, option "kt" != 16), exact-fp32 or f32x3 arithmetic.  Elsewhere the caller keeps dg_bn_act_fwd in front of dg_conv4x4s2_c3_dgrad_p.
+extern "C" int dg_c3_dgrad_bn_ok(int N, int H, int W, int K, int prec) {
+    return c3_dgrad_scatter_fits(N, H, W, K, 0) && dg_get_option(DG_OPT_KT) != 16 && c3_bn_prec_ok(prec) ? 1 : 0;
+}
+// The last decoder group [BatchNorm][ReLU][ConvTranspose2d(K, 3)][act] in one kernel: dx = act(dgrad(relu(bn(y)))), the BatchNorm apply
+// evaluated on the values the kernel loads (bn_act: DG_ACT_RELU, the decoder's activation, model.py:116)
+extern "C" int dg_conv4x4s2_c3_dgrad_bn_p(const float* y_nhwc, const float* saved, const float* gamma, const float* beta, int bn_act, const float* w,
+                                          float* dx_nchw, int N, int H, int W, int K, int act, int prec, dg_stream_t stream) {
+    C3_CHECK_PREC("dg_conv4x4s2_c3_dgrad_bn_p", prec);
+    DG_CHECK_ARG(saved && gamma && beta && bn_act == DG_ACT_RELU, "dg_conv4x4s2_c3_dgrad_bn_p: needs saved, gamma, beta and a ReLU (bn_act=%d)", bn_act);
+    DG_CHECK_ARG(dg_c3_dgrad_bn_ok(N, H, W, K, prec), "dg_conv4x4s2_c3_dgrad_bn_p: no on-load form for N=%d H=%d W=%d K=%d prec=%d (dg_c3_dgrad_bn_ok)", N,
+                 H, W, K, prec);
+    const void* y = y_nhwc;
+    C3Dgrad c = c3_dgrad_call("dg_conv4x4s2_c3_dgrad_bn_p", &y, 0, &w, &dx_nchw, N, H, W, K, act, prec, nullptr, 0, stream);
+    c.bn_saved = saved; c.bn_gamma = gamma; c.bn_beta = beta;
+    return c3_dgrad(c);
+}
 // 1 when the fused form (dg_conv4x4s2_c3_dgrad_act_p) exists for this problem under the options in force: the scatter kernel (K == 64,
 // dy under 2^31 bytes, option "kt" != 16).  Past that size the input-gradient runs on the VALU kernel, which has no fused activation backward.
 extern "C" int dg_c3_dgrad_act_ok(int N, int H, int W, int K, int dy_bf16) {
@@ -507,7 +571,13 @@ static int c3_dgrad(const C3Dgrad& c) {
                                    dim3(256), 0, c.st, pd, pw, px, N, H, W, c.act, tiles_r, tiles_c, (int)ntiles, dyb, pa, c.slope);
             });
         };
-        if (c.dy_bf16 && c.prec == DG_PREC_BF16) scatter(C3Yes{}, C3Yes{}, C3No{});
+        auto scatter_bn = [&](auto X3) {      // on-load BatchNorm + ReLU: fp32 y, its constants in the act_out argument's slots
+            const void* bn[3] = {c.bn_saved, c.bn_gamma, c.bn_beta};
+            hipLaunchKernelGGL((c3_dgrad_scatter_kernel<false, false, decltype(X3)::value, false, true>), grid, dim3(256), 0, c.st, pd, pw, px, N, H, W, c.act,
+                               tiles_r, tiles_c, (int)ntiles, dyb, dg_ptrs(bn, 3), 0.f);
+        };
+        if (c.bn_saved) c3_with_flag(c.prec == DG_PREC_F32X3, scatter_bn);
+        else if (c.dy_bf16 && c.prec == DG_PREC_BF16) scatter(C3Yes{}, C3Yes{}, C3No{});
         else if (c.dy_bf16) scatter(C3Yes{}, C3No{}, C3No{});
         else if (c.prec == DG_PREC_F32X3) scatter(C3No{}, C3No{}, C3Yes{});
         else scatter(C3No{}, C3No{}, C3No{});
@@ -939,7 +1009,10 @@ static int c3_fwd(const C3Fwd& c) {
 //       (dy * act'(act_out), act_out = the saved forward output), instead of a separate act_bwd pass.
 // IN16 (BUF only): dy and act_out are bf16.  A lane then loads ONE dword = channels (2 l31, 2 l31 + 1) of its pixel, so MFMA
 //       block i holds the channels of parity i: block i, row rho <-> channel 2 rho + i.
-template <bool BUF, bool FACT, bool IN16 = false>
+// BNL (BUF, fp32; dg_conv4x4s2_c3_wgrad_bn_p): dy is the raw input y of the decoder's last BatchNorm + ReLU; a value becomes
+//       relu(bn_norm(y, mean, gamma * invstd, beta)) in front of the MFMA that takes it (the lane's two channels: six constants), masked
+//       pixels stay 0.  `act_outs` carries (saved = [mean | invstd], gamma, beta) in its first three slots.
+template <bool BUF, bool FACT, bool IN16 = false, bool BNL = false>
 __global__ __launch_bounds__(256, 2) void c3_wgrad_mfma_kernel(const DgPtrs dys, const DgPtrs xs, const DgPtrs parts, int N, int H, int W, int K,
                                                                int lgHo, int lgWo, long npix, int pix_per_wave,
                                                                const DgPtrs act_outs, float slope) {
@@ -1049,21 +1122,39 @@ __global__ __launch_bounds__(256, 2) void c3_wgrad_mfma_kernel(const DgPtrs dys,
             }
         }
     };
-    auto mma_batch = [&](int set) {
+    static_assert(!BNL || (BUF && !FACT && !IN16), "the on-load BatchNorm form: buffer path, fp32 dy, nothing else fused");
+    float bn_mean[2], bn_gs[2], bn_beta[2];       // BNL: of the lane's channels kg * 64 + l31 (+ 32)
+    if constexpr (BNL) {
+        const float* saved = (const float*)act_outs.p[0];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int ch = kg * 64 + l31 + 32 * i;
+            bn_mean[i] = saved[ch];
+            bn_gs[i] = ((const float*)act_outs.p[1])[ch] * saved[K + ch];
+            bn_beta[i] = ((const float*)act_outs.p[2])[ch];
+        }
+    }
+    auto mma_batch = [&](int set, long p0) {
 #pragma unroll
         for (int st = 0; st < CW_B; ++st)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 2; ++i) {
+                float a = fa[set][st][i];
+                if constexpr (BNL) {
+                    a = dg_apply_act(bn_norm(a, bn_mean[i], bn_gs[i], bn_beta[i]), DG_ACT_RELU, 0.f);
+                    a = p0 + 2 * st + lh < p_end ? a : 0.f;      // load_batch's pok
+                }
 #pragma unroll
                 for (int jn = 0; jn < 2; ++jn)
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][st][i], fb[set][st][jn], acc[i][jn], 0, 0, 0);
+                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, fb[set][st][jn], acc[i][jn], 0, 0, 0);
+            }
     };
     load_batch(0, p_begin);
     for (long p0 = p_begin; p0 < p_end; p0 += 4 * CW_B) {
         load_batch(1, p0 + 2 * CW_B);
-        mma_batch(0);
+        mma_batch(0, p0);
         load_batch(0, p0 + 4 * CW_B);
-        mma_batch(1);
+        mma_batch(1, p0 + 2 * CW_B);
     }
     // the 4 waves' accumulators are summed through LDS in a fixed order -> one slab per workgroup:
     // part[block][K][48]
@@ -1226,6 +1317,8 @@ __global__ __launch_bounds__(256, 2) void c3_wgrad_bf16mfma_kernel(const float* 
 // loaded as fp32 pairs; both operands are split into their three bf16 planes in registers in front of the MFMAs and every block is
 // the six plane products of igemm.hip's PREC 2 -- fp32-accurate, 24 MFMAs of 32 cycles per 16 pixels and wave where the fp32-MFMA
 // kernel above needs 96 of 64, with coalesced image loads instead of its 24-lines-per-instruction gathers.
+// BNL (X3; dg_conv4x4s2_c3_wgrad_bn_p): as in c3_wgrad_mfma_kernel -- dy is the raw input of the decoder's last BatchNorm + ReLU, transformed where
+// FACT applies its activation backward (the lane's channels 2 l31, 2 l31 + 1: six constants); every item multiplied is inside the tensor.
 #define CWL_WOMAX 256
 template <typename F>
 __device__ __forceinline__ void c3_static_for4(F&& f) {
@@ -1234,7 +1327,7 @@ __device__ __forceinline__ void c3_static_for4(F&& f) {
     f(std::integral_constant<int, 2>{});
     f(std::integral_constant<int, 3>{});
 }
-template <bool FACT, bool X3 = false>
+template <bool FACT, bool X3 = false, bool BNL = false>
 __global__ __launch_bounds__(256, X3 ? 1 : 2) void c3_wgrad_lds_kernel(const DgPtrs dys, const DgPtrs xs, const DgPtrs parts, int N, int H, int W, int K,
                                                               long npix, int rows_per_wg, const DgPtrs act_outs, float slope) {
     // grouped launch (dg_conv4x4s2_c3_wgrad_g): blockIdx.z = problem
@@ -1349,12 +1442,28 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void c3_wgrad_lds_kernel(const DgP
         pl[1] = __builtin_convertvector(r1, bf16x8_l);
         pl[2] = __builtin_convertvector(r1 - __builtin_convertvector(pl[1], f32x8_l), bf16x8_l);
     };
+    static_assert(!BNL || (X3 && !FACT), "the on-load BatchNorm form: f32x3, nothing else fused");
+    float bn_mean[2], bn_gs[2], bn_beta[2];       // BNL: of the lane's channels kg * 64 + 2 l31 (+ 1)
+    if constexpr (BNL) {
+        const float* saved = (const float*)act_outs.p[0];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int ch = kg * 64 + 2 * l31 + i;
+            bn_mean[i] = saved[ch];
+            bn_gs[i] = ((const float*)act_outs.p[1])[ch] * saved[K + ch];
+            bn_beta[i] = ((const float*)act_outs.p[2])[ch];
+        }
+    }
     auto mma_x3 = [&](int set, int st, int b) {
         if constexpr (X3) {
             f32x8_l a0, a1;
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 f32x2_w v = fa2[set][t];
+                if constexpr (BNL) {
+                    v[0] = dg_apply_act(bn_norm(v[0], bn_mean[0], bn_gs[0], bn_beta[0]), DG_ACT_RELU, 0.f);
+                    v[1] = dg_apply_act(bn_norm(v[1], bn_mean[1], bn_gs[1], bn_beta[1]), DG_ACT_RELU, 0.f);
+                }
                 if constexpr (FACT) {
                     const f32x2_w o = fo2[set][t];
                     v[0] = o[0] > 0.f ? v[0] : v[0] * slope;
@@ -1538,6 +1647,7 @@ struct C3Wgrad {
     const void* const* act_out;             // fused LeakyReLU / ReLU backward on dy: the layer's saved outputs (read when act != DG_ACT_NONE),
     int act;                                // the activation,
     float slope;                            // and LeakyReLU's slope
+    const float *bn_saved, *bn_gamma, *bn_beta;   // on-load BatchNorm + ReLU (one problem): dy is the BatchNorm's input; nullptr: none
     float* const* dw;
     int io_bf16, N, H, W, K, prec, accumulate;    // io_bf16: dy and act_out are bf16
     void* const* ws;                        // per problem: the per-workgroup partial slabs
@@ -1585,6 +1695,28 @@ extern "C" int dg_conv4x4s2_c3_wgrad_g(int groups, int share, const float* const
     C3Wgrad c = c3_wgrad_call("dg_conv4x4s2_c3_wgrad_g", (const void* const*)dy_nhwc, (const void* const*)act_out_nhwc, 0, act, slope, x_nchw, dw, N, H, W, K,
                               prec, accumulate, ws, ws_bytes, stream);
     c.groups = groups; c.share = share;
+    return c3_wgrad(c);
+}
+static bool c3_wgrad_buf(const C3Wgrad& c);
+// 1 when dg_conv4x4s2_c3_wgrad_bn_p exists for this problem under the options in force: K == 64, rows of at least 16 output pixels (W >= 32),
+// both tensors on the buffer path (< 1 GiB, option "pointer_path" off), exact-fp32 or f32x3 arithmetic -- the fp32-MFMA kernel or, from 256-pixel
+// rows on under f32x3, the LDS kernel, whichever dg_conv4x4s2_c3_wgrad_p runs there.
+extern "C" int dg_c3_wgrad_bn_ok(int N, int H, int W, int K, int prec) {
+    C3Wgrad c = C3Wgrad();
+    c.N = N; c.H = H; c.W = W; c.K = K;
+    return K == 64 && N >= 1 && H >= 2 && W >= 32 && c3_wgrad_buf(c) && c3_bn_prec_ok(prec) ? 1 : 0;
+}
+// dw of the last decoder ConvTranspose2d(K, 3) from the RAW input y of the BatchNorm + ReLU in front of it: dw (+)= wgrad(relu(bn(y)), x), the
+// BatchNorm apply evaluated on the values the kernel loads; bitwise dg_conv4x4s2_c3_wgrad_p on the output of dg_bn_act_fwd
+extern "C" int dg_conv4x4s2_c3_wgrad_bn_p(const float* y_nhwc, const float* saved, const float* gamma, const float* beta, int bn_act, const float* x_nchw,
+                                          float* dw, int N, int H, int W, int K, int prec, int accumulate, void* ws, size_t ws_bytes, dg_stream_t stream) {
+    C3_CHECK_PREC("dg_conv4x4s2_c3_wgrad_bn_p", prec);
+    DG_CHECK_ARG(saved && gamma && beta && bn_act == DG_ACT_RELU, "dg_conv4x4s2_c3_wgrad_bn_p: needs saved, gamma, beta and a ReLU (bn_act=%d)", bn_act);
+    DG_CHECK_ARG(dg_c3_wgrad_bn_ok(N, H, W, K, prec), "dg_conv4x4s2_c3_wgrad_bn_p: no on-load form for N=%d H=%d W=%d K=%d prec=%d (dg_c3_wgrad_bn_ok)", N,
+                 H, W, K, prec);
+    const void* y = y_nhwc;
+    C3Wgrad c = c3_wgrad_call("dg_conv4x4s2_c3_wgrad_bn_p", &y, nullptr, 0, DG_ACT_NONE, 0.f, &x_nchw, &dw, N, H, W, K, prec, accumulate, &ws, ws_bytes, stream);
+    c.bn_saved = saved; c.bn_gamma = gamma; c.bn_beta = beta;
     return c3_wgrad(c);
 }
 static int c3_wgrad_reduce_g(int groups, int share, void* const* ws_tab, float* const* dw_tab, int nb, int total, int accumulate, hipStream_t st) {
@@ -1657,6 +1789,15 @@ static int c3_wgrad(const C3Wgrad& c) {
                                N, H, W, K, lgHo, lgWo, npix, ppw, pao, slope);
         });
     };
+    if (c.bn_saved) {      // on-load BatchNorm + ReLU (fp32 y on the buffer path: dg_c3_wgrad_bn_ok): the form the plain call takes, constants in act_out's slots
+        const void* bn[3] = {c.bn_saved, c.bn_gamma, c.bn_beta};
+        const DgPtrs pbn = dg_ptrs(bn, 3);
+        if (form == C3_WGRAD_LDS_X3)
+            hipLaunchKernelGGL((c3_wgrad_lds_kernel<false, true, true>), grid, dim3(256), 0, c.st, pdy, px, pws, N, H, W, K, npix, rpw, pbn, 0.f);
+        else
+            hipLaunchKernelGGL((c3_wgrad_mfma_kernel<true, false, false, true>), grid, dim3(256), 0, c.st, pdy, px, pws, N, H, W, K, lgHo, lgWo, npix, ppw, pbn,
+                               0.f);
+    } else
     switch (form) {
     case C3_WGRAD_LDS_X3: lds(C3Yes{}); break;
     case C3_WGRAD_LDS_BF16: lds(C3No{}); break;

@@ -54,7 +54,7 @@ __device__ __forceinline__ void bn_stp(float* p, const float (&v)[V]) {
     for (int h = 0; h < V / 4; ++h) *(f32x4*)(p + 4 * h) = (f32x4){v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
 }
 
-__device__ __forceinline__ float bn_norm(float y, float mean, float gs, float beta) { return fmaf(y - mean, gs, beta); }
+// (bn_norm, the apply expression of every kernel here, lives in dg_common.h: edge.hip's on-load forms evaluate the same text)
 
 // Grouped launches (dg_bn_*_g; round 4): the problems of one launch -- the same BatchNorm layer of the A-side and the B-side network, a
 // discriminator layer's real and fake pass (image_translation.py:342-361) -- share M, C and every launch parameter; each has its own

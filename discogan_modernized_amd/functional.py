@@ -288,6 +288,59 @@ class BatchNormActFn(Function):
                 None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
+class BatchNormActConvTransposeC3Fn(Function):
+    """The generators' last group [BatchNorm2d(K)][ReLU][ConvTranspose2d(K,3,4,2,1)][Sigmoid] (model.py:140-143) where
+    ops.c3_tail_bn_ok(y): BatchNormActFn followed by ConvTransposeC3Fn, kernel call for kernel call, except that the BatchNorm apply pass
+    is gone -- the two kernels that would read its output z (the transposed conv's forward and its weight-gradient) read y and apply
+    BatchNorm + ReLU to the values they load.  z and its plane triple are never written; y, which the BatchNorm backward keeps
+    anyway, is all that is saved.  Every result is bitwise the two-function form's."""
+
+    @_fwd
+    def forward(ctx, y, gamma, beta, running_mean, running_var, nbt, training, eps, momentum, bn_act, partials, w, act, dy_cm=False, dy_po=False):
+        y = ops.as_nhwc(y)
+        if training and partials is not None and partials.numel() > 0:
+            saved = ops.bn_stats_from_partials(partials, y, running_mean, running_var, nbt, eps, momentum)
+        elif training:
+            saved = ops.bn_train_stats(y, running_mean, running_var, nbt, eps, momentum)
+        else:
+            saved = torch.stack([running_mean, torch.rsqrt(running_var + eps)])
+        out = ops.c3_dgrad_bn(y, saved, gamma, beta, w, act, bn_act)
+        ctx.save_for_backward(y, saved, gamma, beta, w, out)
+        ctx.cfg = (bn_act, act, training, bool(dy_cm), bool(dy_po))
+        ctx.prefs = (gamma, beta)
+        ctx.wref = w
+        ctx.final = FINAL_PASS
+        return out
+
+    @_bwd
+    def backward(ctx, dout):
+        y, saved, gamma, beta, w, out = ctx.saved_tensors
+        bn_act, act, training, dy_cm, dy_po = ctx.cfg
+        if not training:
+            raise RuntimeError("BatchNormActConvTransposeC3Fn: backward in eval mode is not supported")
+        none = (None,) * 15
+        g = ops.act_bwd(dout, out, act) if act != ops.ACT_NONE else dout.contiguous()
+        need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dz = ops.c3_fwd(g, w, ops.ACT_NONE) if ctx.needs_input_grad[0] or need_p else None
+        dw = None
+        if ctx.needs_input_grad[11]:
+            fg = _flat_grad_of(ctx.wref)
+            if fg is not None and fg.is_contiguous():
+                ops.c3_wgrad_bn(y, saved, gamma, beta, g, out=fg, accumulate=True, bn_act=bn_act)
+                _final(ctx.final, ctx.wref)
+            else:
+                dw = ops.c3_wgrad_bn(y, saved, gamma, beta, g, bn_act=bn_act)
+        if dz is None:
+            return none[:11] + (dw,) + none[12:]
+        fgm, fb = _flat_grad_of(ctx.prefs[0]), _flat_grad_of(ctx.prefs[1])
+        if need_p and fgm is not None and fb is not None:
+            dy, _, _ = ops.bn_act_bwd(dz, y, saved, gamma, beta, bn_act, 0.0, out_grads=(fgm, fb), planes_cm=dy_cm, planes_only=dy_po)
+            _final(ctx.final, ctx.prefs[0], ctx.prefs[1])
+            return (dy,) + none[1:11] + (dw,) + none[12:]
+        dy, dgamma, dbeta = ops.bn_act_bwd(dz, y, saved, gamma, beta, bn_act, 0.0, need_param_grads=need_p, planes_cm=dy_cm, planes_only=dy_po)
+        return (dy, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None) + none[3:11] + (dw,) + none[12:]
+
+
 class ActFn(Function):
     """Stand-alone LeakyReLU / ReLU / Sigmoid (backward from the OUTPUT, in-place semantics)."""
 

@@ -249,6 +249,33 @@ def _first_layer_planes(x, nxt):
     return torch.is_grad_enabled() and nxt.weight.requires_grad and ops._x3_ok(2, n, h // 2, w // 2, nxt.in_channels, nxt.out_channels, 2, 1)
 
 
+TAIL_BN_ONLOAD = __import__("os").environ.get("DG_TAIL_BN_ONLOAD", "1") != "0"      # A/B switch of _tail_onload
+
+
+def _tail_onload(y, bn, act_mod, rest):
+    """The generators' last group: ``bn`` + ReLU are followed by ``rest`` = [ConvTranspose2d(K, 3)] or [ConvTranspose2d(K, 3), Sigmoid]
+    and the 3-channel kernels take BatchNorm + ReLU on load for ``y`` (ops.c3_tail_bn_ok) -> the modules of ``rest`` that
+    functional.BatchNormActConvTransposeC3Fn covers, else None: the BatchNorm apply pass and ConvTransposeC3Fn as before.  A module
+    with a forward hook keeps its own call (the hook wants its output)."""
+    if not (TAIL_BN_ONLOAD and isinstance(act_mod, ReLU) and 1 <= len(rest) <= 2):
+        return None
+    convT = rest[0]
+    if not (isinstance(convT, ConvTranspose2d) and convT.out_channels == 3 and convT.stride == 2) or \
+            (len(rest) == 2 and not isinstance(rest[1], Sigmoid)):
+        return None
+    if any(m._forward_hooks or m._forward_pre_hooks for m in (bn, act_mod, *rest)):
+        return None
+    need_wgrad = torch.is_grad_enabled() and convT.weight.requires_grad
+    return rest if ops.c3_tail_bn_ok(y, need_wgrad) else None
+
+
+def _tail_apply(y, bn, act, st, tail, dy_cm=False, dy_po=False):
+    """bn + ReLU on ``y`` (statistics from the partials ``st`` if any) inside the kernels of the 3-channel ConvTranspose2d (+ Sigmoid) ``tail``."""
+    return F.BatchNormActConvTransposeC3Fn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
+                                                 bn.eps, bn.momentum, act, st, tail[0].weight, tail[1].act if len(tail) == 2 else ops.ACT_NONE,
+                                                 dy_cm, dy_po)
+
+
 def drain(gen):
     """Run a ``*_steps`` generator to completion and return its value."""
     try:
@@ -276,6 +303,10 @@ def _run_fused_steps(layers, x):
         slope = act_mod.negative_slope if act_mod is not None else 0.0
         if bn is not None and bn.training and not ops.X3 and _fuse_stats(conv, x) and conv.emits_bn_stats:
             y, st = conv(x, want_stats=_fuse_stats(conv, x))       # BN statistics from the conv / split-K reduce kernel
+            tail = _tail_onload(y, bn, act_mod, layers[j + 1:])
+            if tail is not None:
+                yield
+                return _tail_apply(y, bn, act, st, tail)
             x = bn(y, act, slope, st)
         elif bn is not None:
             nxt = layers[j + (1 if act_mod is not None else 0)] if j + (1 if act_mod is not None else 0) < n else None
@@ -287,6 +318,9 @@ def _run_fused_steps(layers, x):
             else:
                 y = conv(x)
             yield
+            tail = _tail_onload(y, bn, act_mod, layers[j + 1:])
+            if tail is not None:
+                return _tail_apply(y, bn, act, st, tail, dy_cm, dy_po)
             x = bn(y, act, slope, st, z_cm, dy_cm, z_po, dy_po)
         elif isinstance(conv, Conv2d) and conv.in_channels == 3 and act in (ops.ACT_LEAKY, ops.ACT_RELU, ops.ACT_NONE):
             nxt = layers[j + (1 if act_mod is not None else 0)] if j + (1 if act_mod is not None else 0) < n else None

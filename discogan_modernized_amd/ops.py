@@ -801,6 +801,48 @@ def c3_wgrad(dy, x_nchw, out=None, accumulate=False, act_out=None, act=ACT_NONE,
     return dw
 
 
+def c3_tail_bn_ok(y, need_wgrad=True):
+    """Last decoder group [BatchNorm][ReLU][ConvTranspose2d(K, 3)]: do the 3-channel kernels take the BatchNorm's INPUT ``y`` and apply
+    BatchNorm + ReLU to the values they load (c3_dgrad_bn / c3_wgrad_bn) under the current context?  fp32 storage, exact-fp32 or f32x3
+    arithmetic, K == 64, and the sizes dg_c3_dgrad_bn_ok / dg_c3_wgrad_bn_ok accept."""
+    if _is16(y) or _CUR.act16 or _CUR.shadow:
+        return False
+    n, k, ho, wo = y.shape
+    L = _lib.load()
+    return bool(L.dg_c3_dgrad_bn_ok(n, 2 * ho, 2 * wo, k, _CUR.cprec)) and \
+        (not need_wgrad or bool(L.dg_c3_wgrad_bn_ok(n, 2 * ho, 2 * wo, k, _CUR.cprec)))
+
+
+def c3_dgrad_bn(y, saved, gamma, beta, w, act=ACT_NONE, bn_act=ACT_RELU):
+    """Bitwise c3_dgrad(bn_act_fwd(y, saved, gamma, beta, bn_act), w, act) without the BatchNorm apply pass: the scatter kernel reads
+    ``y`` and applies BatchNorm + ReLU on load (needs c3_tail_bn_ok(y))."""
+    _check_dev(y, saved, gamma, beta, w)
+    y = as_nhwc(y)
+    w = w.contiguous()
+    n, k, ho, wo = y.shape
+    dx = torch.empty((n, 3, 2 * ho, 2 * wo), device=y.device, dtype=torch.float32)
+    with _hbm("edge_c3_dgrad", 4.0 * y.numel() + 4.0 * dx.numel()):
+        _lib.check(_lib.load().dg_conv4x4s2_c3_dgrad_bn_p(_ptr(y), _ptr(saved), _ptr(gamma), _ptr(beta), bn_act, _ptr(w), _ptr(dx), n, 2 * ho, 2 * wo,
+                                                          k, act, _CUR.cprec, _stream()), "dg_conv4x4s2_c3_dgrad_bn_p")
+    return dx
+
+
+def c3_wgrad_bn(y, saved, gamma, beta, x_nchw, out=None, accumulate=False, bn_act=ACT_RELU):
+    """Bitwise c3_wgrad(bn_act_fwd(y, saved, gamma, beta, bn_act), x_nchw, out, accumulate) from the BatchNorm's input ``y``."""
+    _check_dev(y, saved, gamma, beta, x_nchw)
+    y = as_nhwc(y)
+    x = x_nchw.contiguous()
+    n, k, ho, wo = y.shape
+    h, wd = x.shape[2], x.shape[3]
+    dw = out if out is not None else torch.empty((k, 3, 4, 4), device=y.device, dtype=torch.float32)
+    L = _lib.load()
+    ws, wsb = _ws(L.dg_c3_wgrad_workspace_bytes(n, h, wd, k), y.device)
+    with _hbm("edge_c3_wgrad", 4.0 * y.numel() + 4.0 * x.numel()):
+        _lib.check(L.dg_conv4x4s2_c3_wgrad_bn_p(_ptr(y), _ptr(saved), _ptr(gamma), _ptr(beta), bn_act, _ptr(x), _ptr(dw), n, h, wd, k, _CUR.cprec,
+                                                int(accumulate), _ptr(ws), wsb, _stream()), "dg_conv4x4s2_c3_wgrad_bn_p")
+    return dw
+
+
 # ---- BatchNorm + activation -----------------------------------------------------------------------------
 def bn_train_stats(y, running_mean, running_var, nbt, eps, momentum):
     _check_dev(y, allow16=True)

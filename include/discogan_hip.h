@@ -240,6 +240,18 @@ int dg_conv4x4s2_c3_wgrad_p(const void* dy_nhwc, const void* act_out_nhwc, int i
 int dg_c3_dgrad_act_ok(int N, int H, int W, int K, int dy_bf16);
 int dg_conv4x4s2_c3_dgrad_act_p(const void* dy_nhwc, int dy_bf16, const void* act_out_nhwc, int in_act, float slope, const float* w,
                                 float* dx_nchw, int N, int H, int W, int K, int act, int prec, void* ws, size_t ws_bytes, dg_stream_t s);
+/* The last decoder group [BatchNorm2d(K)][ReLU][ConvTranspose2d(K,3,4,2,1)][Sigmoid] (model.py:140-143) without the BatchNorm apply pass: the
+ * two kernels that read the BatchNorm's output z take its INPUT y_nhwc[N,H/2,W/2,K] (fp32) instead and evaluate
+ * z = relu((y - mean) * (gamma * invstd) + beta), saved = [mean | invstd] (dg_bn_train_stats / dg_bn_stats_from_partials), on the values they
+ * load -- the expression of dg_bn_act_fwd, so both are bitwise dg_conv4x4s2_c3_dgrad_p / dg_conv4x4s2_c3_wgrad_p on dg_bn_act_fwd's output.
+ * bn_act = DG_ACT_RELU.  They exist where dg_c3_dgrad_bn_ok / dg_c3_wgrad_bn_ok (host only) return 1: K == 64, y under 2^31 bytes (weight
+ * gradient: both tensors under 1 GiB and W >= 32), prec exact fp32 or f32x3; elsewhere the caller keeps the apply pass. */
+int dg_c3_dgrad_bn_ok(int N, int H, int W, int K, int prec);
+int dg_conv4x4s2_c3_dgrad_bn_p(const float* y_nhwc, const float* saved, const float* gamma, const float* beta, int bn_act, const float* w,
+                               float* dx_nchw, int N, int H, int W, int K, int act, int prec, dg_stream_t s);
+int dg_c3_wgrad_bn_ok(int N, int H, int W, int K, int prec);
+int dg_conv4x4s2_c3_wgrad_bn_p(const float* y_nhwc, const float* saved, const float* gamma, const float* beta, int bn_act, const float* x_nchw,
+                               float* dw, int N, int H, int W, int K, int prec, int accumulate, void* ws, size_t ws_bytes, dg_stream_t s);
 int dg_conv4x4s2_c3_fwd_g(int groups, const float* const* x_nchw, const float* const* w, float* const* y_nhwc, int N, int H, int W, int K,
                           int act, float slope, int prec, dg_stream_t s);
 int dg_conv4x4s2_c3_dgrad_g(int groups, const float* const* dy_nhwc, const float* const* w, float* const* dx_nchw, int N, int H, int W, int K,
