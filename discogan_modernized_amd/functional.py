@@ -76,49 +76,65 @@ def _release_after_backward(dy, x):
     ops.derived_release(dy, x)
 
 
+def _conv_forward(ctx, transposed, x, w, stride, pad, want_stats):
+    """Forward of ConvFn (transposed=False: ops.conv_fwd) and ConvTransposeFn (True: the input-gradient op with the same weight)."""
+    x = ops.as_nhwc(x)
+    ctx.save_for_backward(x, w)
+    ctx.sp = (stride, pad)
+    ctx.wref = w
+    ctx.final = FINAL_PASS
+    if transposed:
+        hw = ((x.shape[2] - 1) * stride - 2 * pad + 4, (x.shape[3] - 1) * stride - 2 * pad + 4)
+        y = ops.conv_dgrad(x, w, hw, stride, pad, want_stats=want_stats)
+    else:
+        y = ops.conv_fwd(x, w, stride, pad, want_stats=want_stats)
+    _release_unless_wgrad(ctx, x)
+    if not want_stats:
+        return y
+    y, stat = y
+    if stat is None:
+        stat = torch.empty(0, device=y.device)
+    ctx.mark_non_differentiable(stat)
+    # without this autograd hands backward() a freshly zero-filled tensor of stat's shape for the non-differentiable output:
+    # one fill launch per fused-statistics conv and backward (48 per iteration at 512 px, rocprof round 3)
+    ctx.set_materialize_grads(False)
+    return y, stat
+
+
+def _conv_backward(ctx, transposed, dy):
+    if dy is None:                                     # (set_materialize_grads(False): an unused output arrives as None)
+        return None, None, None, None, None
+    x, _ = ctx.saved_tensors
+    w = ctx.wref                                       # the Parameter object itself (carries the bf16 shadow attribute)
+    stride, pad = ctx.sp
+    dy = ops.as_nhwc(dy)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dx = ops.conv_fwd(dy, w, stride, pad) if transposed else ops.conv_dgrad(dy, w, (x.shape[2], x.shape[3]), stride, pad)
+    # transposed: dw[cin][r][s][cout] = sum x[..cin] * dy[..cout]: conv wgrad with roles (dy := x, x := dy)
+    wg = (x, dy) if transposed else (dy, x)
+    dw = None
+    if ctx.needs_input_grad[1]:
+        fg = _flat_grad_of(w)
+        if fg is not None:
+            ops.conv_wgrad(*wg, stride, pad, out=fg, accumulate=True)
+            _final(ctx.final, w)
+        else:
+            dw = ops.conv_wgrad(*wg, stride, pad)
+    _release_after_backward(dy, x)
+    return dx, dw, None, None, None
+
+
 class ConvFn(Function):
     """nn.Conv2d(C,K,4,stride,pad,bias=False), interior (C % 32 == 0)."""
 
     @_fwd
     def forward(ctx, x, w, stride, pad, want_stats=False):
-        x = ops.as_nhwc(x)
-        ctx.save_for_backward(x, w)
-        ctx.sp = (stride, pad)
-        ctx.wref = w
-        ctx.final = FINAL_PASS
-        if not want_stats:
-            y = ops.conv_fwd(x, w, stride, pad)
-            _release_unless_wgrad(ctx, x)
-            return y
-        y, stat = ops.conv_fwd(x, w, stride, pad, want_stats=want_stats)
-        _release_unless_wgrad(ctx, x)
-        if stat is None:
-            stat = torch.empty(0, device=y.device)
-        ctx.mark_non_differentiable(stat)
-        # without this autograd hands backward() a freshly zero-filled tensor of stat's shape for the non-differentiable output:
-        # one fill launch per fused-statistics conv and backward (48 per iteration at 512 px, rocprof round 3)
-        ctx.set_materialize_grads(False)
-        return y, stat
+        return _conv_forward(ctx, False, x, w, stride, pad, want_stats)
 
     @_bwd
     def backward(ctx, dy, dstat=None):
-        if dy is None:                                 # (set_materialize_grads(False): an unused output arrives as None)
-            return None, None, None, None, None
-        x, w = ctx.saved_tensors
-        w = ctx.wref                                   # the Parameter object itself (carries the bf16 shadow attribute)
-        stride, pad = ctx.sp
-        dy = ops.as_nhwc(dy)
-        dx = ops.conv_dgrad(dy, w, (x.shape[2], x.shape[3]), stride, pad) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            fg = _flat_grad_of(ctx.wref)
-            if fg is not None:
-                ops.conv_wgrad(dy, x, stride, pad, out=fg, accumulate=True)
-                _final(ctx.final, ctx.wref)
-            else:
-                dw = ops.conv_wgrad(dy, x, stride, pad)
-        _release_after_backward(dy, x)
-        return dx, dw, None, None, None
+        return _conv_backward(ctx, False, dy)
 
 
 class ConvTransposeFn(Function):
@@ -127,48 +143,11 @@ class ConvTransposeFn(Function):
 
     @_fwd
     def forward(ctx, x, w, stride, pad, want_stats=False):
-        x = ops.as_nhwc(x)
-        ctx.save_for_backward(x, w)
-        ctx.sp = (stride, pad)
-        ctx.wref = w
-        ctx.final = FINAL_PASS
-        hin, win = x.shape[2], x.shape[3]
-        hout, wout = (hin - 1) * stride - 2 * pad + 4, (win - 1) * stride - 2 * pad + 4
-        ctx.out_hw = (hout, wout)
-        if not want_stats:
-            y = ops.conv_dgrad(x, w, (hout, wout), stride, pad)
-            _release_unless_wgrad(ctx, x)
-            return y
-        y, stat = ops.conv_dgrad(x, w, (hout, wout), stride, pad, want_stats=want_stats)
-        _release_unless_wgrad(ctx, x)
-        if stat is None:
-            stat = torch.empty(0, device=y.device)
-        ctx.mark_non_differentiable(stat)
-        # without this autograd hands backward() a freshly zero-filled tensor of stat's shape for the non-differentiable output:
-        # one fill launch per fused-statistics conv and backward (48 per iteration at 512 px, rocprof round 3)
-        ctx.set_materialize_grads(False)
-        return y, stat
+        return _conv_forward(ctx, True, x, w, stride, pad, want_stats)
 
     @_bwd
     def backward(ctx, dy, dstat=None):
-        if dy is None:
-            return None, None, None, None, None
-        x, w = ctx.saved_tensors
-        w = ctx.wref
-        stride, pad = ctx.sp
-        dy = ops.as_nhwc(dy)
-        dx = ops.conv_fwd(dy, w, stride, pad) if ctx.needs_input_grad[0] else None
-        # dw[cin][r][s][cout] = sum x[..cin] * dy[..cout]: conv wgrad with roles (dy := x, x := dy)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            fg = _flat_grad_of(ctx.wref)
-            if fg is not None:
-                ops.conv_wgrad(x, dy, stride, pad, out=fg, accumulate=True)
-                _final(ctx.final, ctx.wref)
-            else:
-                dw = ops.conv_wgrad(x, dy, stride, pad)
-        _release_after_backward(dy, x)
-        return dx, dw, None, None, None
+        return _conv_backward(ctx, True, dy)
 
 
 class ConvC3Fn(Function):
@@ -243,6 +222,16 @@ class ConvTransposeC3Fn(Function):
         return dx, dw, None
 
 
+def _bn_saved(y, partials, running_mean, running_var, nbt, training, eps, momentum):
+    """The [2, C] (mean, 1 / std) a BatchNorm pass normalises with: batch statistics in training mode (running buffers updated) --
+    merged from ``partials`` where the producing conv kernel's epilogue emitted them, else one pass over y -- or the running ones."""
+    if training and partials is not None and partials.numel() > 0:
+        return ops.bn_stats_from_partials(partials, y, running_mean, running_var, nbt, eps, momentum)
+    if training:
+        return ops.bn_train_stats(y, running_mean, running_var, nbt, eps, momentum)
+    return torch.stack([running_mean, torch.rsqrt(running_var + eps)])
+
+
 class BatchNormActFn(Function):
     """nn.BatchNorm2d (+ in-place LeakyReLU / ReLU).  Training mode updates the running buffers in
     the kernel exactly like PyTorch (momentum 0.1, unbiased running_var, num_batches_tracked += 1)."""
@@ -254,13 +243,7 @@ class BatchNormActFn(Function):
         input-grad kernel -> written in the quad-chunk layout; z_po / dy_po (ops.X3_PLANES_ONLY): every reader of z / dy is a plane
         kernel -> the fp32 copy is not written (model.py decides both from the neighbouring convolutions)."""
         y = ops.as_nhwc(y)
-        if training and partials is not None and partials.numel() > 0:
-            # statistics came out of the producing conv kernel's epilogue: no extra pass over y
-            saved = ops.bn_stats_from_partials(partials, y, running_mean, running_var, nbt, eps, momentum)
-        elif training:
-            saved = ops.bn_train_stats(y, running_mean, running_var, nbt, eps, momentum)
-        else:
-            saved = torch.stack([running_mean, torch.rsqrt(running_var + eps)])
+        saved = _bn_saved(y, partials, running_mean, running_var, nbt, training, eps, momentum)
         z = ops.bn_act_fwd(y, saved, gamma, beta, act, slope, planes_cm=z_cm, planes_only=z_po and training)
         ctx.save_for_backward(y, saved, gamma, beta)
         ctx.cfg = (act, slope, training)
@@ -298,12 +281,7 @@ class BatchNormActConvTransposeC3Fn(Function):
     @_fwd
     def forward(ctx, y, gamma, beta, running_mean, running_var, nbt, training, eps, momentum, bn_act, partials, w, act, dy_cm=False, dy_po=False):
         y = ops.as_nhwc(y)
-        if training and partials is not None and partials.numel() > 0:
-            saved = ops.bn_stats_from_partials(partials, y, running_mean, running_var, nbt, eps, momentum)
-        elif training:
-            saved = ops.bn_train_stats(y, running_mean, running_var, nbt, eps, momentum)
-        else:
-            saved = torch.stack([running_mean, torch.rsqrt(running_var + eps)])
+        saved = _bn_saved(y, partials, running_mean, running_var, nbt, training, eps, momentum)
         out = ops.c3_dgrad_bn(y, saved, gamma, beta, w, act, bn_act)
         ctx.save_for_backward(y, saved, gamma, beta, w, out)
         ctx.cfg = (bn_act, act, training, bool(dy_cm), bool(dy_po))

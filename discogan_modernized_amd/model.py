@@ -243,10 +243,11 @@ def _first_layer_planes(x, nxt):
     if not (ops.X3 and C3_PLANES and isinstance(nxt, Conv2d) and nxt.stride == 2):
         return False
     n, _, h, w = x.shape
-    if ops._x3_ok(0, n, h // 2, w // 2, nxt.in_channels, nxt.out_channels, 2, 1) and \
-            (ops.X3_RSP or getattr(nxt.weight, "_dg_x3", (None, 0, None))[2] is not None):
+    geom = (n, h // 2, w // 2, nxt.in_channels, nxt.out_channels, 2, 1)
+    planes = ops.x3_fwd_weight_planes(*geom, nxt.weight)        # which weight planes that forward reads (None: it reads no planes)
+    if planes == 1 or (planes == 0 and ops.X3_RSP):             # (the plain weight planes count under X3_RSP only, as they always did here)
         return True
-    return torch.is_grad_enabled() and nxt.weight.requires_grad and ops._x3_ok(2, n, h // 2, w // 2, nxt.in_channels, nxt.out_channels, 2, 1)
+    return torch.is_grad_enabled() and nxt.weight.requires_grad and ops._x3_ok(2, *geom)
 
 
 TAIL_BN_ONLOAD = __import__("os").environ.get("DG_TAIL_BN_ONLOAD", "1") != "0"      # A/B switch of _tail_onload

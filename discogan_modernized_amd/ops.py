@@ -8,6 +8,10 @@ Layout conventions (see include/discogan_hip.h):
 """
 from __future__ import annotations
 
+import collections
+import ctypes
+import os
+
 import torch
 
 from . import _lib
@@ -74,56 +78,47 @@ class use:
 # bench.py's roofline leg sets this to a list: every launch of the MFMA implicit-GEMM family then
 # appends (op, algorithmic FLOPs, start event, end event), recorded on the launch stream.
 PROFILE = None
-
-
-class _prof:
-    def __init__(self, name, flops):
-        self.on = PROFILE is not None
-        if self.on:
-            self.name, self.flops = name, flops
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e1 = torch.cuda.Event(enable_timing=True)
-
-    def __enter__(self):
-        if self.on:
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.e1.record()
-            PROFILE.append((self.name, self.flops, self.e0, self.e1))
-        return False
-
-
 # Same hook for the HBM-bound kernel families: (family, algorithmic bytes, start event, end event).
 PROFILE_HBM = None
 
 
-class _hbm:
-    def __init__(self, name, nbytes):
-        self.on = PROFILE_HBM is not None
-        if self.on:
-            self.name, self.nbytes = name, nbytes
+class _timed:
+    """``with _prof(name, flops):`` / ``with _hbm(name, nbytes):`` -- one record per block into the sink, when the sink is a list."""
+
+    def __init__(self, sink, name, amount):
+        self.sink = sink
+        if sink is not None:
+            self.name, self.amount = name, amount
             self.e0 = torch.cuda.Event(enable_timing=True)
             self.e1 = torch.cuda.Event(enable_timing=True)
 
     def __enter__(self):
-        if self.on:
+        if self.sink is not None:
             self.e0.record()
         return self
 
     def __exit__(self, *exc):
-        if self.on:
+        if self.sink is not None:
             self.e1.record()
-            PROFILE_HBM.append((self.name, self.nbytes, self.e0, self.e1))
+            self.sink.append((self.name, self.amount, self.e0, self.e1))
         return False
 
 
-def _need_fp32(t, who):
-    """Guard of the non-plane code paths: a plane-only tensor (X3_PLANES_ONLY) has no fp32 memory image to read."""
-    if getattr(t, "_dg_planes_only", False):
-        raise _lib.DiscoganHipError(f"{who}: the operand exists only as its plane triple, but this shape has no plane kernel")
+_UNTIMED = _timed(None, None, None)                   # (the hooks are off in training: no object per launch then)
+
+
+def _prof(name, flops):
+    return _UNTIMED if PROFILE is None else _timed(PROFILE, name, flops)
+
+
+def _hbm(name, nbytes):
+    return _UNTIMED if PROFILE_HBM is None else _timed(PROFILE_HBM, name, nbytes)
+
+
+def _env_flag(name, default):
+    """A switch from the environment: one that is on by default is turned off by "0", one that is off by default is turned on by "1"."""
+    v = os.environ.get(name)
+    return v != "0" if default else v == "1"
 
 
 def _stream():
@@ -134,12 +129,16 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+_TAB_TYPES = {}
+
+
 def _tab(ts):
     """Pointer table of a grouped C-ABI call: one device pointer per problem (None entries allowed)."""
-    import ctypes as C
     if ts is None:
         return None
-    return (C.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
+    n = len(ts)
+    table = _TAB_TYPES.get(n) or _TAB_TYPES.setdefault(n, ctypes.c_void_p * n)
+    return table(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
 def _check_dev(*ts, allow16=False, planes_ok=False):
@@ -177,7 +176,9 @@ def _act_dtype(channels):
 
 
 def is_nhwc(x):
-    return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
+    """Is the memory of the logical [N,C,H,W] tensor NHWC?  (x.permute(0, 2, 3, 1).is_contiguous() without building the view: every
+    conv call asks twice.  An empty tensor counts as it does there.)"""
+    return x.dim() == 4 and (x.is_contiguous(memory_format=torch.channels_last) or x.numel() == 0)
 
 
 def as_nhwc(x):
@@ -274,7 +275,7 @@ def krsc_param(w_logical):
 
 
 def is_krsc(w):
-    return w.dim() == 4 and w.permute(0, 2, 3, 1).is_contiguous()
+    return is_nhwc(w)
 
 
 def _krsc(w):
@@ -370,38 +371,38 @@ def _bf16_ok(op, n, h, wd, c, k, stride, pad):
 # <= 128 input channels, the input of the transposed convs with <= 128 output channels) in the QUAD-CHUNK layout
 # ([pixels/4][C/16][4][16], include/discogan_hip.h "plane_layout"): the window kernel then uses every byte of the 128-byte lines
 # it fetches instead of 32.  Bit-identical results; DG_X3_CM=0 keeps every triple pixel-major (A/B).
-X3_CM = __import__("os").environ.get("DG_X3_CM", "1") != "0"
+X3_CM = _env_flag("DG_X3_CM", True)
 # X3_PLANES_ONLY: a BatchNorm output whose every reader is a plane kernel (the next conv's forward and weight-grad; the
 # layer's own input-grad and weight-grad for a gradient) is written ONLY as its plane triple: the planes carry all 24 significand
 # bits (hi + mid + lo == the fp32 value), the fp32 tensor stays allocated but unwritten and is flagged ``_dg_planes_only`` --
 # every op wrapper that would read fp32 memory refuses such a tensor.  model.py decides per layer; DG_X3_PLANES_ONLY=0: off (A/B).
-X3_PLANES_ONLY = __import__("os").environ.get("DG_X3_PLANES_ONLY", "1") != "0"
+X3_PLANES_ONLY = _env_flag("DG_X3_PLANES_ONLY", True)
 # POISON_PLANES_ONLY (debug aid, DG_POISON_PLANES_ONLY=1; round-3 advisor finding): the fp32 memory of a plane-only tensor is never written
 # and its only protection is the ``_dg_planes_only`` attribute, which a view / a torch-native reader does not carry.  With the switch on that
 # memory is filled with NaN, so anything that reads it (instead of the planes) turns the losses NaN instead of using stale allocator bytes;
 # tests/test_model_gpu.py runs a training step under it and requires the results bitwise unchanged.
-POISON_PLANES_ONLY = __import__("os").environ.get("DG_POISON_PLANES_ONLY", "0") == "1"
+POISON_PLANES_ONLY = _env_flag("DG_POISON_PLANES_ONLY", False)
 # X3_FWW: forward convolutions with <= 128 output channels on the window forward kernel (csrc/igemm_dma_x3_fww.hip; planner code 3:
 # needs the transposed weight planes).  OFF by default: built, parity-tested and measured at the benchmark shape (64 -> 128 channels,
 # 512 px / batch 32) at 0.923 ms against 0.927 ms for the register-staged f32x3 tiles -- its window pixels are every OTHER pixel of a
 # pixel-major plane, 32 bytes of each 128-byte line per fetch, and those loads cost it 0.28 of its 0.92 ms.
 # DG_X3_FWW=1 turns it on.
-X3_FWW = __import__("os").environ.get("DG_X3_FWW", "0") == "1"
+X3_FWW = _env_flag("DG_X3_FWW", False)
 # X3_FUSE_STATS: on the plane path the BatchNorm batch statistics come out of the producing conv kernel's epilogue (or its split-K
 # reduction) as partial rows, merged by dg_bn_stats_from_partials -- no separate read pass over the conv output.  (On the exact-fp32
 # path of the 64 px network the same idea lengthened 140 us kernels by more than the pass it saved: model.FUSE_BN_STATS fuses only
 # launches of 40 GFLOP and more there; the plane kernels run for hundreds of microseconds per tile and do not notice ~400 VALU instructions per wave.)
-X3_FUSE_STATS = __import__("os").environ.get("DG_X3_FUSE_STATS", "1") != "0"
+X3_FUSE_STATS = _env_flag("DG_X3_FUSE_STATS", True)
 # FUSE_STATS16: the bf16 matrix path takes its BatchNorm statistics from the bf16 conv
 # kernels' fp32 accumulators too (LDS-DMA kernel, window input-grad, register-staged tiles, split-K reduction: stat argument of
 # dg_conv_fwd_mixed / _dgrad_mixed) instead of dropping to the exact-fp32 kernels for the fused layers.
-FUSE_STATS16 = __import__("os").environ.get("DG_FUSE_BN16", "1") != "0"
+FUSE_STATS16 = _env_flag("DG_FUSE_BN16", True)
 # X3_MFMA: the MFMA shape of the plane kernel's 256 x 256 tile (library option "x3_mfma").  16 = v_mfma_f32_16x16x32_bf16 with the
 # planes paired along k (three instructions per 16 x 16 block and K-tile instead of six 32x32x16 ones: the same products, a shape
 # under which the chip holds a higher clock; csrc/igemm_dma_x3.hip); 32 / 0 = the 32x32x16 body (default: the paired body is faster
 # per launch on the middle layers and not at all in the whole step).  The
 # environment variable is applied by _lib.load() like every DG_OPT_*; this constant is what tests restore the option to.
-X3_MFMA = int(__import__("os").environ.get("DG_OPT_X3_MFMA", "0"))
+X3_MFMA = int(os.environ.get("DG_OPT_X3_MFMA", "0"))
 
 
 # X3_RSP (off: measured 45 % SLOWER): forward convs without an LDS-DMA plane kernel (fewer than 192 output channels: the 64 -> 128
@@ -410,11 +411,36 @@ X3_MFMA = int(__import__("os").environ.get("DG_OPT_X3_MFMA", "0"))
 # operands inside the kernel.  Bit-identical, a quarter fewer instructions -- and 1.36 instead of 0.94 ms at 512 px / batch 32: a
 # 16-channel K-tile of a pixel-major plane is a 32-byte piece of a 128-byte line, three planes make it three times as many load
 # instructions of half the useful width (the fp32 operand: 64-byte pieces).  DG_X3_RSP=1 switches it on.  DESIGN.md 3.1.
-X3_RSP = __import__("os").environ.get("DG_X3_RSP", "0") == "1"
+X3_RSP = _env_flag("DG_X3_RSP", False)
+
+
+def _plane_code(*request):
+    """Which kernel reads plane triples for the request (op, n, h, wd, c, k, stride, pad): 0 none, 1 the LDS-DMA plane kernel, 2 the
+    window input-grad kernel with K % 64 == 0 (it takes quad-chunk planes), 3 the window forward kernel, 4 the register-staged tiles
+    reading planes (3 and 4: answers of the experiments library only)."""
+    return _lib.load().dg_conv_x3_planes_ok(*request)
+
+
+def _x3_code(op, n, h, wd, c, k, stride, pad):
+    """The plane code a launch under the current context goes by: 0 outside the f32x3 plane path and for the one-channel head."""
+    return _plane_code(op, n, h, wd, c, k, stride, pad) if (_CUR.x3 and k > 1) else 0
 
 
 def _plane_code_ok(code):
     return code in (1, 2) or (code == 3 and (X3_FWW or X3_RSP)) or (code == 4 and X3_RSP)
+
+
+def _fwd_weight_planes(code, w):
+    """Which planes of the weight ``w`` the FORWARD launch of a request with plane code ``code`` reads: 1 the transposed copy
+    [(r, s, c)][k] (the faster form; weights of a flat Adam group have one), 0 the plain planes, None: no plane launch.  The
+    register-staged tiles (code 4, and code 3 without the window forward kernel's transposed planes or without X3_FWW) read the PLAIN
+    planes and only under X3_RSP.  The one statement of this rule: _conv_form launches by it, model._first_layer_planes predicts by it."""
+    if not _plane_code_ok(code):
+        return None
+    has_transposed = getattr(w, "_dg_x3", (None, 0, None))[2] is not None
+    if code == 4 or (code == 3 and not (has_transposed and X3_FWW)):
+        return 0 if X3_RSP else None
+    return int(has_transposed)
 
 
 def planes_clear():
@@ -452,12 +478,13 @@ def planes_of(t, allow_cm=False):
 def x3_all_plane_readers(n, h, wd, c, k, forward_is_dgrad=False, need_wgrad=True):
     """Are the conv kernels that will READ a tensor all plane kernels?  For a layer input x of Conv2d(c, k, 4, 2, 1) on [n, c, h, wd]:
     its forward (op 0) and weight-grad (op 2); with forward_is_dgrad (ConvTranspose2d: the same geometry read as an input-grad): op 1
-    and op 2.  For a gradient dy: the layer's input-grad (op 1) and weight-grad -- the same question with forward_is_dgrad."""
+    and op 2.  For a gradient dy: the layer's input-grad (op 1) and weight-grad -- the same question with forward_is_dgrad.
+    (Looser than the launch in one case, kept: plane code 3 under X3_FWW counts although a weight without a transposed copy then takes
+    the fp32 form, which refuses a plane-only tensor.)"""
     if not (_CUR.x3 and X3_PLANES_ONLY):
         return False
-    L = _lib.load()
     first = 1 if forward_is_dgrad else 0
-    return _plane_code_ok(L.dg_conv_x3_planes_ok(first, n, h, wd, c, k, 2, 1)) and (not need_wgrad or L.dg_conv_x3_planes_ok(2, n, h, wd, c, k, 2, 1) >= 1)
+    return _plane_code_ok(_plane_code(first, n, h, wd, c, k, 2, 1)) and (not need_wgrad or _plane_code(2, n, h, wd, c, k, 2, 1) >= 1)
 
 
 def x3_window_dgrad(n, h, wd, c, k):
@@ -466,8 +493,7 @@ def x3_window_dgrad(n, h, wd, c, k):
     writes chunk-major planes (X3_CM)."""
     if not (_CUR.x3 and X3_CM) or k % 64 != 0:
         return False
-    L = _lib.load()
-    return L.dg_conv_x3_planes_ok(1, n, h, wd, c, k, 2, 1) == 2 and L.dg_conv_x3_planes_ok(2, n, h, wd, c, k, 2, 1) == 1
+    return _plane_code(1, n, h, wd, c, k, 2, 1) == 2 and _plane_code(2, n, h, wd, c, k, 2, 1) == 1
 
 
 def x3_transpose_table(convs):
@@ -508,10 +534,17 @@ def weight_planes(w, transposed=False):
 
 
 def _x3_ok(op, n, h, wd, c, k, stride, pad):
-    return _CUR.x3 and k > 1 and _plane_code_ok(_lib.load().dg_conv_x3_planes_ok(op, n, h, wd, c, k, stride, pad))
+    return _plane_code_ok(_x3_code(op, n, h, wd, c, k, stride, pad))
+
+
+def x3_fwd_weight_planes(n, h, wd, c, k, stride, pad, w):
+    """_fwd_weight_planes of the forward of Conv2d(c, k, 4, stride, pad) with weight ``w`` on [n, c, h, wd] under the current context."""
+    return _fwd_weight_planes(_x3_code(0, n, h, wd, c, k, stride, pad), w)
 
 
 # ---- interior convolutions ------------------------------------------------------------------------------
+# One call (_conv) = the operands prepared once, one request (_ConvReq: what is asked), one form choice (_conv_form: which entry point
+# family reads which operand forms) and one launch.  DESIGN.md 3.1 "Conv op wrappers".
 def _out_hw(h, w, stride, pad):
     return (h + 2 * pad - 4) // stride + 1, (w + 2 * pad - 4) // stride + 1
 
@@ -524,121 +557,195 @@ def _mixed_operand(t, allow_shadow=True):
     return (t16, 1) if t16 is not None else (t, 0)
 
 
+_CONV_NAME = ("conv_fwd", "conv_dgrad", "conv_wgrad")
+
+
+class _ConvReq:
+    """One interior conv request, built once per call from the operands a, b = (x, w) | (dy, w) | (dy, x) of op 0 forward | 1 input
+    gradient | 2 weight gradient: ``geom`` = (n, h, wd, c, k, stride, pad) of the Conv2d (x [n, c, h, wd], k output channels, dy
+    [n, k, ho, wo]), the feature-map result's shape and channels (op 0: y, op 1: dx), the current context's arithmetic, and the
+    roofline hook's name and algorithmic FLOPs."""
+    __slots__ = ("op", "geom", "c", "k", "out_shape", "out_channels", "prec", "name", "flops")
+
+    def __init__(self, op, a, b, stride, pad, x_hw=None):
+        if op == 1:                                    # the input's size is not in the operands
+            (n, k, ho, wo), c, (h, wd) = a.shape, b.shape[1], x_hw
+        else:
+            n, c, h, wd = (a if op == 0 else b).shape
+            k = b.shape[0] if op == 0 else a.shape[1]
+            ho, wo = _out_hw(h, wd, stride, pad) if op == 0 else (a.shape[2], a.shape[3])
+        self.op, self.geom, self.c, self.k, self.prec = op, (n, h, wd, c, k, stride, pad), c, k, _CUR.cprec
+        self.out_shape, self.out_channels = ((n, k, ho, wo), k) if op == 0 else ((n, c, h, wd), c)
+        self.name = _CONV_NAME[op] if k > 1 else "head1"
+        self.flops = 2.0 * n * ho * wo * k * c * 16
+
+    def workspace_bytes(self, plan_groups=1):
+        return _lib.load().dg_conv_workspace_bytes_p(self.op, *self.geom, self.prec, plan_groups)
+
+
+# What _conv_form chose: kind "x3" (plane triples; ``w_planes``: 1 the transposed weight copy, forward only; ``cm_ok``: the gradient
+# operand may be a quad-chunk triple), "mixed" (``a16 / b16 / o16``: operand A, operand B, the output are bf16), "g" (fp32 tensors, one
+# problem) or "refuse" (``why``); ``rows``: statistics rows a "mixed" / "g" launch writes (0: none; the plane form's rows are asked
+# for at the launch, once its operands exist); ``declined_planes``: see _conv.
+_ConvForm = collections.namedtuple("_ConvForm", "kind a16 b16 o16 rows w_planes cm_ok declined_planes why", defaults=(0, 0, 0, 0, 0, False, False, None))
+
+
+def _conv_form(rq, a, b, want_stats=False):
+    """The form one interior conv request is launched in, from the request, its two operands as they were handed over (dtype,
+    ``_dg_planes_only``, shadows, plane entries), ``want_stats`` (False | True | "split"), the current context and the switches X3_FWW,
+    X3_RSP, FUSE_STATS16.  Asks the library's host queries; allocates nothing, launches nothing.  The three ops are NOT mirror
+    images: every line marked (op ...) is a difference the three-wrapper form had, kept as it was."""
+    L = _lib.load()
+    op, geom, k, c = rq.op, rq.geom, rq.k, rq.c
+    # statistics rows of the fp32 form; "split": only where the split-K reduction kernel can emit them.  (op 2 has no statistics)
+    rows = L.dg_conv_bnstats_rows_p(op, *geom, rq.prec) if want_stats else 0
+    if want_stats == "split" and L.dg_conv_plan_splits_p(op, *geom, rq.prec, 1) <= 1:
+        rows = 0
+    # ---- plane triples (f32x3 plane path) ----
+    code = _x3_code(op, *geom)
+    # (op 0) the forward alone has weight-plane variants and may decline a plane code the predictors accept (_fwd_weight_planes)
+    w_planes = _fwd_weight_planes(code, b) if op == 0 else (0 if _plane_code_ok(code) else None)
+    if w_planes is not None:
+        # (op 1) a quad-chunk gradient triple is read by the window kernel only (code 2); (op 2) the plane weight-grad kernel takes
+        # either layout; (op 0) x is never chunk-major
+        return _ConvForm("x3", 0, 0, 0, 0, w_planes, (code == 2) if op == 1 else op == 2)
+    declined = _plane_code_ok(code)                    # (op 0 only; see _conv)
+    # ---- from here on the kernels read memory images ----
+    for t in (a, b) if op == 2 else (a,):
+        if getattr(t, "_dg_planes_only", False):
+            return _ConvForm("refuse", declined_planes=declined, why=f"{_CONV_NAME[op]}: the operand exists only as its plane triple, but "
+                                                                     "this shape has no plane kernel")
+    a16 = b16 = o16 = 0
+    if op == 2:
+        if k == 1:
+            b16 = int(_is16(b))                        # the one-channel head reads a bf16 x as it is (no shadows, dy stays fp32)
+        elif _bf16_ok(2, *geom) or _is16(b) or _is16(a):           # (op 2) bf16 TENSORS go to the mixed entry point whatever the query says
+            if c % 8 == 0:                             # (8-element granules of a bf16 x must not straddle a tap: its rows are C channels long)
+                b16 = _mixed_operand(b)[1]
+            if k % 8 == 0:                             # (the same for the K-channel rows of dy)
+                a16 = _mixed_operand(a)[1]
+        if (_is16(a) and not a16) or (_is16(b) and not b16):
+            return _ConvForm("refuse", why=f"conv_wgrad: no bf16 kernel for bf16 operands of shapes {tuple(a.shape)}, {tuple(b.shape)}")
+        return _ConvForm("mixed", a16, b16) if (a16 or b16) else _ConvForm("g")
+    if k == 1:
+        if op == 0:
+            a16 = int(_is16(a))                        # (op 0) head forward: a bf16 x is read as it is, the one-channel output stays fp32
+        else:
+            o16 = int(_act_dtype(c) == torch.bfloat16)             # (op 1) head input gradient: dy [N,1,1,1] is fp32, the result a feature map
+    elif (rows == 0 or FUSE_STATS16) and _bf16_ok(op, *geom):
+        if op == 0 or k % 8 == 0:                      # (op 1) dy's rows are K channels long: granule rule as in op 2; x's C % 32 == 0 always
+            a16 = _mixed_operand(a)[1]
+        b16 = int(_CUR.shadow and getattr(b, "_dg_bf16", None) is not None)      # (weight_shadow(b) is not None, without its refresh)
+        o16 = int(_act_dtype(rq.out_channels) == torch.bfloat16)
+    mixed = bool(a16 or b16 or o16)
+    if op == 0 and _is16(a) and not mixed:             # (op 0) tests the whole form ...
+        return _ConvForm("refuse", declined_planes=declined, why=f"conv_fwd: no bf16 kernel for a bf16 input of shape {tuple(a.shape)} -> {k} channels")
+    if op == 1 and _is16(a) and not a16:               # (op 1) ... the operand's own flag: kept from the three-wrapper form, reason not recorded
+        return _ConvForm("refuse", why=f"conv_dgrad: no bf16 kernel for a bf16 gradient of shape {tuple(a.shape)}")
+    if not mixed:
+        return _ConvForm("g", 0, 0, 0, rows, 0, False, declined)
+    # (op 1) the mixed statistics rows carry k > 1: kept from the three-wrapper form, reason not recorded (the head has no BatchNorm behind it)
+    mrows = L.dg_conv_mixed_bnstats_rows(op, *geom, a16, b16) if (want_stats and FUSE_STATS16 and (op == 0 or k > 1)) else 0
+    return _ConvForm("mixed", a16, b16, o16, mrows, 0, False, declined)
+
+
+def _stat_rows(rows, channels, device):
+    """Buffer for ``rows`` partial-statistics rows of a ``channels``-channel conv output (None for no rows)."""
+    return torch.empty((rows, 3 * channels + 4), device=device, dtype=torch.float32) if rows > 0 else None
+
+
+def _numel(t):
+    return t.numel() if t is not None else 0
+
+
+def _launch_g(rq, as_, bs, outs, plan_groups, stats, wsl, wsb, share=1, accumulate=False):
+    """The fp32-tensor form for a list of problems (one launch per kernel of the plan): arithmetic = the request's, passed with the call;
+    ``stats``: one statistics buffer per problem or None; ``wsl``: one workspace per problem."""
+    L, g = _lib.load(), len(as_)
+    with _prof(rq.name, rq.flops * g):
+        if rq.op == 2:
+            rc = L.dg_conv_wgrad_g(g, int(share), _tab(as_), _tab(bs), _tab(outs), *rq.geom, rq.prec, plan_groups, int(accumulate), _tab(wsl), wsb, _stream())
+        else:
+            rc = (L.dg_conv_dgrad_g if rq.op else L.dg_conv_fwd_g)(g, _tab(as_), _tab(bs), _tab(outs), *rq.geom, rq.prec, plan_groups, _tab(stats),
+                                                                   _numel(stats[0]) if stats else 0, _tab(wsl), wsb, _stream())
+    if rc != 0:
+        _lib.check(rc, f"dg_{_CONV_NAME[rq.op]}_g")
+
+
+def _conv(op, a, b, stride, pad, x_hw=None, want_stats=False, out=None, accumulate=False):
+    """One interior conv call, a, b as in _ConvReq: prepare the operands, build the request, choose the form, then fetch the derived
+    operands (they may split or refresh), allocate the output and the statistics rows, and launch.  Returns (output, statistics
+    rows or None)."""
+    _check_dev(*((a, b) if op == 2 else (a,)), allow16=True, planes_ok=True)
+    if op != 2:
+        _check_dev(b)
+    a, b = as_nhwc(a), (as_nhwc(b) if op == 2 else _krsc(b))
+    rq = _ConvReq(op, a, b, stride, pad, x_hw)
+    if op == 2 and out is None:
+        out = empty_krsc(rq.k, rq.c, a.device)
+    ws, wsb = _ws(rq.workspace_bytes(), a.device)
+    f = _conv_form(rq, a, b, want_stats)
+    if f.declined_planes:
+        # kept from the three-wrapper form, reason not recorded: a forward that declines its plane code (code 3 under X3_FWW, weight
+        # without a transposed copy) still brings the weight's triple up to date before it goes on in another form
+        weight_planes(b, transposed=True)
+    if f.kind == "refuse":
+        raise _lib.DiscoganHipError(f.why)
+    if f.kind == "g":
+        if out is None:
+            out = empty_nhwc(*rq.out_shape, a.device)
+        stat = _stat_rows(f.rows, rq.out_channels, a.device)
+        _launch_g(rq, [a], [b], [out], 1, None if stat is None else [stat], [ws], wsb, 1, accumulate)
+        return out, stat
+    L, geom = _lib.load(), rq.geom
+    if f.kind == "mixed":
+        if f.a16:
+            a = _mixed_operand(a)[0]
+        if f.b16:
+            b = _mixed_operand(b)[0] if op == 2 else weight_shadow(b)
+        rows = f.rows
+    elif op == 0:                                      # "x3" (op 0: the weight's planes first, then x; op 1: dy first -- the order of the splits, kept)
+        pb = weight_planes(b, transposed=bool(f.w_planes))
+        pa = planes_of(a)
+    else:
+        pa = planes_of(a, allow_cm=f.cm_ok)
+        pb = weight_planes(b) if op == 1 else planes_of(b)
+    if out is None:
+        out = empty_nhwc(*rq.out_shape, a.device, torch.bfloat16 if f.o16 else torch.float32)
+    if f.kind == "x3":                                 # (the plane form's statistics rows: asked for once its operands exist)
+        rows = L.dg_conv_x3_bnstats_rows(op, *geom) if (want_stats and op != 2) else 0
+    stat = _stat_rows(rows, rq.out_channels, a.device)
+    tail = (_ptr(ws), wsb, _stream())
+    with _prof(rq.name, rq.flops):
+        if f.kind == "mixed":
+            if op == 0:
+                rc = L.dg_conv_fwd_mixed(_ptr(a), f.a16, _ptr(b), f.b16, _ptr(out), f.o16, *geom, _ptr(stat), _numel(stat), *tail)
+            elif op == 1:
+                rc = L.dg_conv_dgrad_mixed(_ptr(a), f.a16, _ptr(b), f.b16, _ptr(out), f.o16, *geom, _ptr(stat), _numel(stat), *tail)
+            else:
+                rc = L.dg_conv_wgrad_mixed(_ptr(a), f.a16, _ptr(b), f.b16, _ptr(out), *geom, int(accumulate), *tail)
+        elif op == 0:                                  # pa / pb = (address, plane distance, chunk-major? | transposed?)
+            rc = L.dg_conv_fwd_x3(pa[0], pa[1], pb[0], pb[1], f.w_planes, _ptr(out), *geom, _ptr(stat), _numel(stat), *tail)
+        elif op == 1:
+            rc = L.dg_conv_dgrad_x3(*pa, pb[0], pb[1], _ptr(out), *geom, _ptr(stat), _numel(stat), *tail)
+        else:
+            rc = L.dg_conv_wgrad_x3(*pa, pb[0], pb[1], _ptr(out), *geom, int(accumulate), *tail)
+    if rc != 0:
+        _lib.check(rc, f"dg_{_CONV_NAME[op]}_{f.kind}")
+    return out, stat
+
+
 def conv_fwd(x, w, stride, pad, want_stats=False):
     """nn.Conv2d(C,K,4,stride,pad,bias=False) forward. x NHWC-memory [N,C,H,W], w [K,C,4,4] KRSC.
     want_stats: also return the BatchNorm partial-statistics rows of y (None if the layer has no fused path)."""
-    _check_dev(x, allow16=True, planes_ok=True)
-    _check_dev(w)
-    x = as_nhwc(x)
-    w = _krsc(w)
-    n, c, h, wd = x.shape
-    k = w.shape[0]
-    ho, wo = _out_hw(h, wd, stride, pad)
-    L = _lib.load()
-    prec = _CUR.cprec
-    ws, wsb = _ws(L.dg_conv_workspace_bytes_p(0, n, h, wd, c, k, stride, pad, prec, 1), x.device)
-    rows = L.dg_conv_bnstats_rows_p(0, n, h, wd, c, k, stride, pad, prec) if want_stats else 0
-    if want_stats == "split" and L.dg_conv_plan_splits_p(0, n, h, wd, c, k, stride, pad, prec, 1) <= 1:
-        rows = 0                      # statistics only where the split-K reduction kernel can emit them
-    code = L.dg_conv_x3_planes_ok(0, n, h, wd, c, k, stride, pad) if (_CUR.x3 and k > 1) else 0
-    if _plane_code_ok(code):
-        wp, wdist, wt = weight_planes(w, transposed=True)
-        if code == 4 or (code == 3 and not (wt and X3_FWW)):
-            # the register-staged tiles read the PLAIN planes (3 with transposed planes and X3_FWW: the window forward kernel)
-            wp, wdist, wt = (*weight_planes(w)[:2], 0) if X3_RSP else (None, 0, 0)
-        if wp is not None:
-            xp, xd, _ = planes_of(x)
-            y = empty_nhwc(n, k, ho, wo, x.device)
-            srows = L.dg_conv_x3_bnstats_rows(0, n, h, wd, c, k, stride, pad) if want_stats else 0
-            stat = torch.empty((srows, 3 * k + 4), device=x.device, dtype=torch.float32) if srows > 0 else None
-            with _prof("conv_fwd", 2.0 * n * ho * wo * k * c * 16):
-                _lib.check(L.dg_conv_fwd_x3(xp, xd, wp, wdist, wt, _ptr(y), n, h, wd, c, k, stride, pad, _ptr(stat),
-                                            stat.numel() if stat is not None else 0, _ptr(ws), wsb, _stream()), "dg_conv_fwd_x3")
-            return (y, stat) if want_stats else y
-    _need_fp32(x, "conv_fwd")
-    mixed = False
-    xa, x16, wa, w16, o16 = x, 0, w, 0, 0
-    if k == 1:
-        mixed = _is16(x)
-        x16 = int(mixed)
-    elif (rows == 0 or FUSE_STATS16) and _bf16_ok(0, n, h, wd, c, k, stride, pad):
-        xa, x16 = _mixed_operand(x)
-        wsh = weight_shadow(w)
-        if wsh is not None:
-            wa, w16 = wsh, 1
-        o16 = int(_act_dtype(k) == torch.bfloat16)
-        mixed = bool(x16 or w16 or o16)
-    if _is16(x) and not mixed:
-        raise _lib.DiscoganHipError(f"conv_fwd: no bf16 kernel for a bf16 input of shape {tuple(x.shape)} -> {k} channels")
-    y = empty_nhwc(n, k, ho, wo, x.device, torch.bfloat16 if o16 else torch.float32)
-    with _prof("conv_fwd" if k > 1 else "head1", 2.0 * n * ho * wo * k * c * 16):
-        if mixed:
-            mrows = L.dg_conv_mixed_bnstats_rows(0, n, h, wd, c, k, stride, pad, x16, w16) if (want_stats and FUSE_STATS16) else 0
-            stat = torch.empty((mrows, 3 * k + 4), device=x.device, dtype=torch.float32) if mrows > 0 else None
-            _lib.check(L.dg_conv_fwd_mixed(_ptr(xa), x16, _ptr(wa), w16, _ptr(y), o16, n, h, wd, c, k,
-                                           stride, pad, _ptr(stat), stat.numel() if stat is not None else 0, _ptr(ws), wsb, _stream()),
-                       "dg_conv_fwd_mixed")
-        else:       # the fp32-tensor form: arithmetic = this context's, passed with the call
-            stat = torch.empty((rows, 3 * k + 4), device=x.device, dtype=torch.float32) if rows > 0 else None
-            _lib.check(L.dg_conv_fwd_g(1, _tab([x]), _tab([w]), _tab([y]), n, h, wd, c, k, stride, pad, prec, 1, _tab([stat]) if rows > 0 else None,
-                                       stat.numel() if rows > 0 else 0, _tab([ws]), wsb, _stream()), "dg_conv_fwd_g")
+    y, stat = _conv(0, x, w, stride, pad, None, want_stats)
     return (y, stat) if want_stats else y
 
 
 def conv_dgrad(dy, w, x_hw, stride, pad, want_stats=False):
     """Input-gradient of that Conv2d == ConvTranspose2d forward. dy [N,K,Ho,Wo]; returns [N,C,H,W]
     (and, with want_stats, the BatchNorm partial-statistics rows of the result or None)."""
-    _check_dev(dy, allow16=True, planes_ok=True)
-    _check_dev(w)
-    dy = as_nhwc(dy)
-    w = _krsc(w)
-    n, k = dy.shape[0], dy.shape[1]
-    c = w.shape[1]
-    h, wd = x_hw
-    L = _lib.load()
-    prec = _CUR.cprec
-    ws, wsb = _ws(L.dg_conv_workspace_bytes_p(1, n, h, wd, c, k, stride, pad, prec, 1), dy.device)
-    rows = L.dg_conv_bnstats_rows_p(1, n, h, wd, c, k, stride, pad, prec) if want_stats else 0
-    if want_stats == "split" and L.dg_conv_plan_splits_p(1, n, h, wd, c, k, stride, pad, prec, 1) <= 1:
-        rows = 0
-    if _x3_ok(1, n, h, wd, c, k, stride, pad):
-        dp, dd, dcm = planes_of(dy, allow_cm=L.dg_conv_x3_planes_ok(1, n, h, wd, c, k, stride, pad) == 2)
-        wp, wdist, _ = weight_planes(w)
-        dx = empty_nhwc(n, c, h, wd, dy.device)
-        srows = L.dg_conv_x3_bnstats_rows(1, n, h, wd, c, k, stride, pad) if want_stats else 0
-        stat = torch.empty((srows, 3 * c + 4), device=dy.device, dtype=torch.float32) if srows > 0 else None
-        with _prof("conv_dgrad", 2.0 * n * dy.shape[2] * dy.shape[3] * k * c * 16):
-            _lib.check(L.dg_conv_dgrad_x3(dp, dd, dcm, wp, wdist, _ptr(dx), n, h, wd, c, k, stride, pad, _ptr(stat),
-                                          stat.numel() if stat is not None else 0, _ptr(ws), wsb, _stream()), "dg_conv_dgrad_x3")
-        return (dx, stat) if want_stats else dx
-    _need_fp32(dy, "conv_dgrad")
-    mixed = False
-    da, d16, wa, w16, o16 = dy, 0, w, 0, 0
-    if k == 1:
-        o16 = int(_act_dtype(c) == torch.bfloat16)
-        mixed = bool(o16)
-    elif (rows == 0 or FUSE_STATS16) and _bf16_ok(1, n, h, wd, c, k, stride, pad):
-        if k % 8 == 0:
-            da, d16 = _mixed_operand(dy)
-        wsh = weight_shadow(w)
-        if wsh is not None:
-            wa, w16 = wsh, 1
-        o16 = int(_act_dtype(c) == torch.bfloat16)
-        mixed = bool(d16 or w16 or o16)
-    if _is16(dy) and not d16:
-        raise _lib.DiscoganHipError(f"conv_dgrad: no bf16 kernel for a bf16 gradient of shape {tuple(dy.shape)}")
-    dx = empty_nhwc(n, c, h, wd, dy.device, torch.bfloat16 if o16 else torch.float32)
-    with _prof("conv_dgrad" if k > 1 else "head1", 2.0 * n * dy.shape[2] * dy.shape[3] * k * c * 16):
-        if mixed:
-            mrows = L.dg_conv_mixed_bnstats_rows(1, n, h, wd, c, k, stride, pad, d16, w16) if (want_stats and FUSE_STATS16 and k > 1) else 0
-            stat = torch.empty((mrows, 3 * c + 4), device=dy.device, dtype=torch.float32) if mrows > 0 else None
-            _lib.check(L.dg_conv_dgrad_mixed(_ptr(da), d16, _ptr(wa), w16, _ptr(dx), o16, n, h, wd, c, k,
-                                             stride, pad, _ptr(stat), stat.numel() if stat is not None else 0, _ptr(ws), wsb, _stream()),
-                       "dg_conv_dgrad_mixed")
-        else:
-            stat = torch.empty((rows, 3 * c + 4), device=dy.device, dtype=torch.float32) if rows > 0 else None
-            _lib.check(L.dg_conv_dgrad_g(1, _tab([dy]), _tab([w]), _tab([dx]), n, h, wd, c, k, stride, pad, prec, 1, _tab([stat]) if rows > 0 else None,
-                                         stat.numel() if rows > 0 else 0, _tab([ws]), wsb, _stream()), "dg_conv_dgrad_g")
+    dx, stat = _conv(1, dy, w, stride, pad, x_hw, want_stats)
     return (dx, stat) if want_stats else dx
 
 
@@ -674,42 +781,7 @@ def conv_dgrad_bias_act(x, w, bias, out_hw, stride, pad, act=ACT_NONE, slope=0.0
 
 def conv_wgrad(dy, x, stride, pad, out=None, accumulate=False):
     """Weight-gradient of that Conv2d: returns logical [K,C,4,4] (KRSC memory)."""
-    _check_dev(dy, x, allow16=True, planes_ok=True)
-    dy = as_nhwc(dy)
-    x = as_nhwc(x)
-    n, c, h, wd = x.shape
-    k = dy.shape[1]
-    dw = out if out is not None else empty_krsc(k, c, x.device)
-    L = _lib.load()
-    prec = _CUR.cprec
-    ws, wsb = _ws(L.dg_conv_workspace_bytes_p(2, n, h, wd, c, k, stride, pad, prec, 1), x.device)
-    if _x3_ok(2, n, h, wd, c, k, stride, pad):
-        dp, dd, dcm = planes_of(dy, allow_cm=True)
-        xp, xd, _ = planes_of(x)
-        with _prof("conv_wgrad", 2.0 * n * dy.shape[2] * dy.shape[3] * k * c * 16):
-            _lib.check(L.dg_conv_wgrad_x3(dp, dd, dcm, xp, xd, _ptr(dw), n, h, wd, c, k, stride, pad, int(accumulate), _ptr(ws), wsb,
-                                          _stream()), "dg_conv_wgrad_x3")
-        return dw
-    _need_fp32(dy, "conv_wgrad")
-    _need_fp32(x, "conv_wgrad")
-    da, d16, xa, x16 = dy, 0, x, 0
-    if k == 1:
-        x16 = int(_is16(x))
-    elif _bf16_ok(2, n, h, wd, c, k, stride, pad) or _is16(x) or _is16(dy):
-        if c % 8 == 0:                   # (8-element granules of a bf16 x must not straddle a tap: its rows are C channels long)
-            xa, x16 = _mixed_operand(x)
-        if k % 8 == 0:
-            da, d16 = _mixed_operand(dy)
-    if (_is16(dy) and not d16) or (_is16(x) and not x16):
-        raise _lib.DiscoganHipError(f"conv_wgrad: no bf16 kernel for bf16 operands of shapes {tuple(dy.shape)}, {tuple(x.shape)}")
-    with _prof("conv_wgrad" if k > 1 else "head1", 2.0 * n * dy.shape[2] * dy.shape[3] * k * c * 16):
-        if d16 or x16:
-            _lib.check(L.dg_conv_wgrad_mixed(_ptr(da), d16, _ptr(xa), x16, _ptr(dw), n, h, wd, c, k,
-                                             stride, pad, int(accumulate), _ptr(ws), wsb, _stream()), "dg_conv_wgrad_mixed")
-        else:
-            _lib.check(L.dg_conv_wgrad_g(1, 1, _tab([dy]), _tab([x]), _tab([dw]), n, h, wd, c, k, stride, pad, prec, 1, int(accumulate),
-                                         _tab([ws]), wsb, _stream()), "dg_conv_wgrad_g")
-    return dw
+    return _conv(2, dy, x, stride, pad, None, False, out, accumulate)[0]
 
 
 # ---- 3-channel edge layers ------------------------------------------------------------------------------
@@ -858,7 +930,7 @@ def bn_train_stats(y, running_mean, running_var, nbt, eps, momentum):
     return saved
 
 
-_PARTIALS_ONE_LAUNCH = __import__("os").environ.get("DG_BN_PARTIALS_ONE_LAUNCH", "0") == "1"     # same-box A/B of the two-level merge
+_PARTIALS_ONE_LAUNCH = _env_flag("DG_BN_PARTIALS_ONE_LAUNCH", False)     # same-box A/B of the two-level merge
 
 
 def bn_stats_from_partials(stat, y, running_mean, running_var, nbt, eps, momentum):
@@ -1258,67 +1330,37 @@ def _share_of(params):
     return run
 
 
+def _conv_g(op, as_, bs, stride, pad, x_hw=None, outs=None, accumulate=False, share=1):
+    """One grouped launch of the fp32-tensor form: the problems' operands as lists, in _ConvReq's order."""
+    who = _CONV_NAME[op] + "_g"
+    g = len(as_)
+    _check_dev(*as_, *bs)
+    as_ = [as_nhwc(t) for t in as_]
+    bs = [as_nhwc(t) if op == 2 else _krsc(t) for t in bs]
+    _same_shape(as_, who)
+    _same_shape(bs, who)
+    rq = _ConvReq(op, as_[0], bs[0], stride, pad, x_hw)
+    pg = _plan_groups(g)
+    wsl, wsb = _ws_g(rq.workspace_bytes(pg), g, as_[0].device)
+    if outs is None:
+        outs = [empty_nhwc(*rq.out_shape, as_[0].device) for _ in range(g)]
+    _launch_g(rq, as_, bs, outs, pg, None, wsl, wsb, share, accumulate)
+    return outs
+
+
 def conv_fwd_g(xs, ws_, stride, pad):
     """Conv2d forward of ``len(xs)`` problems in one launch (plus one split-K reduction launch)."""
-    g = len(xs)
-    _check_dev(*xs, *ws_)
-    xs = [as_nhwc(x) for x in xs]
-    ws_ = [_krsc(w) for w in ws_]
-    _same_shape(xs, "conv_fwd_g")
-    _same_shape(ws_, "conv_fwd_g")
-    n, c, h, wd = xs[0].shape
-    k = ws_[0].shape[0]
-    ho, wo = _out_hw(h, wd, stride, pad)
-    L = _lib.load()
-    prec = _CUR.cprec
-    pg = _plan_groups(g)
-    wsl, wsb = _ws_g(L.dg_conv_workspace_bytes_p(0, n, h, wd, c, k, stride, pad, prec, pg), g, xs[0].device)
-    ys = [empty_nhwc(n, k, ho, wo, xs[0].device) for _ in range(g)]
-    with _prof("conv_fwd" if k > 1 else "head1", 2.0 * g * n * ho * wo * k * c * 16):
-        _lib.check(L.dg_conv_fwd_g(g, _tab(xs), _tab(ws_), _tab(ys), n, h, wd, c, k, stride, pad, prec, pg, None, 0, _tab(wsl), wsb, _stream()),
-                   "dg_conv_fwd_g")
-    return ys
+    return _conv_g(0, xs, ws_, stride, pad)
 
 
 def conv_dgrad_g(dys, ws_, x_hw, stride, pad):
-    g = len(dys)
-    _check_dev(*dys, *ws_)
-    dys = [as_nhwc(d) for d in dys]
-    ws_ = [_krsc(w) for w in ws_]
-    _same_shape(dys, "conv_dgrad_g")
-    _same_shape(ws_, "conv_dgrad_g")
-    n, k = dys[0].shape[0], dys[0].shape[1]
-    c = ws_[0].shape[1]
-    h, wd = x_hw
-    L = _lib.load()
-    prec = _CUR.cprec
-    pg = _plan_groups(g)
-    wsl, wsb = _ws_g(L.dg_conv_workspace_bytes_p(1, n, h, wd, c, k, stride, pad, prec, pg), g, dys[0].device)
-    dxs = [empty_nhwc(n, c, h, wd, dys[0].device) for _ in range(g)]
-    with _prof("conv_dgrad" if k > 1 else "head1", 2.0 * g * n * dys[0].shape[2] * dys[0].shape[3] * k * c * 16):
-        _lib.check(L.dg_conv_dgrad_g(g, _tab(dys), _tab(ws_), _tab(dxs), n, h, wd, c, k, stride, pad, prec, pg, None, 0, _tab(wsl), wsb, _stream()),
-                   "dg_conv_dgrad_g")
-    return dxs
+    return _conv_g(1, dys, ws_, stride, pad, x_hw)
 
 
 def conv_wgrad_g(dys, xs, stride, pad, outs, accumulate, share=1):
     """Weight gradients of ``len(dys)`` problems into ``outs`` (accumulating views of the flat gradient buffer).  share > 1: every
     ``share`` consecutive problems name the same ``outs`` tensor and are summed into it in problem order."""
-    g = len(dys)
-    _check_dev(*dys, *xs)
-    dys = [as_nhwc(d) for d in dys]
-    xs = [as_nhwc(x) for x in xs]
-    _same_shape(dys, "conv_wgrad_g")
-    _same_shape(xs, "conv_wgrad_g")
-    n, c, h, wd = xs[0].shape
-    k = dys[0].shape[1]
-    L = _lib.load()
-    prec = _CUR.cprec
-    pg = _plan_groups(g)
-    wsl, wsb = _ws_g(L.dg_conv_workspace_bytes_p(2, n, h, wd, c, k, stride, pad, prec, pg), g, xs[0].device)
-    with _prof("conv_wgrad" if k > 1 else "head1", 2.0 * g * n * dys[0].shape[2] * dys[0].shape[3] * k * c * 16):
-        _lib.check(L.dg_conv_wgrad_g(g, int(share), _tab(dys), _tab(xs), _tab(outs), n, h, wd, c, k, stride, pad, prec, pg, int(accumulate),
-                                     _tab(wsl), wsb, _stream()), "dg_conv_wgrad_g")
+    _conv_g(2, dys, xs, stride, pad, None, outs, accumulate, share)
 
 
 def c3_fwd_g(xs, ws_, act=ACT_NONE, slope=0.2):

@@ -202,3 +202,28 @@ def test_graft_entry_build():
     import __graft_entry__ as g
     g.build()
     assert os.path.exists(_lib.LIB_PATH)
+
+
+def test_is_nhwc_is_the_permuted_view_being_contiguous():
+    """ops.is_nhwc / is_krsc ask torch for channels-last contiguity; that is the same predicate as `x.permute(0, 2, 3, 1).is_contiguous()`
+    for every shape and stride pattern: size-1 dimensions, broadcast strides, slices, every permutation, empty tensors."""
+    import random
+    rnd = random.Random(0)
+    base = torch.zeros(1 << 12)
+    seen = {True: 0, False: 0}
+    for _ in range(20000):
+        shape = [rnd.choice([0, 1, 1, 2, 3, 4]) for _ in range(4)]
+        if rnd.random() < 0.5:
+            perm = rnd.sample(range(4), 4)
+            t = torch.empty([shape[p] for p in perm]).permute(*[perm.index(i) for i in range(4)])
+            if rnd.random() < 0.3 and t.shape[1] > 1:
+                t = t[:, ::2]
+            if rnd.random() < 0.3 and t.shape[3] > 1:
+                t = t[..., 1:]
+        else:
+            t = base.as_strided(shape, [rnd.choice([0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 48]) for _ in range(4)])
+        want = t.permute(0, 2, 3, 1).is_contiguous()
+        assert ops.is_nhwc(t) == want and ops.is_krsc(t) == want, (tuple(t.shape), t.stride())
+        seen[want] += 1
+    assert min(seen.values()) > 1000, seen
+    assert not ops.is_nhwc(torch.zeros(2, 3, 4)) and not ops.is_krsc(torch.zeros(2, 3, 4, 5, 6))
