@@ -147,6 +147,7 @@ SIGNATURES = {
     "dg_conv_x3_bnstats_rows": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "dg_conv_fwd_x3": (_i, [_p, _l, _p, _l, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _z, _p]),
     "dg_x3_transpose_planes": (_i, [_p, _p, _z, _p, _p, _p, _i, _p]),
+    "dg_adam_step_group_x3": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _p, _p, _z, _p, _p, _p, _i, _p, _p, _i, _p]),
     "dg_conv_dgrad_x3": (_i, [_p, _l, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _z, _p]),
     "dg_conv_wgrad_x3": (_i, [_p, _l, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
     "dg_conv_mixed_bnstats_rows": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),

@@ -38,7 +38,7 @@ template <int... Q, typename F>
 __device__ __forceinline__ void dg_x3_static_for(std::integer_sequence<int, Q...>, F&& f) {
     (f(std::integral_constant<int, Q>{}), ...);
 }
-#define DG_X3T_MAX 48
+#include "x3_table.h"
 // 16x16x32 body: (block row, pair type) of the 24 MFMA groups of a K-tile, in issue order
 constexpr int G16_I[24] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 6, 7, 6, 6, 7, 7};
 constexpr int G16_T[24] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 0, 1, 2, 1, 2};
@@ -719,12 +719,7 @@ int dg_igemm_dma_x3_launch(int mode, int wm, int wn, const IgemmArgs& a, int zmu
 // ---- transposed weight planes for the forward form -------------------------------------------------------------------------
 // For every conv weight of a flat parameter group: planes [3][K][J] (J = 16 C, the KRSC image) -> [3][J][K] at the same flat
 // offset of a second plane buffer.  One launch for the whole group: 64 x 64 tiles through LDS, 128-byte rows both ways.
-struct X3TransposeTable {
-    int n;
-    int tile0[DG_X3T_MAX + 1];      // first tile of weight i (prefix sums); tile0[n] = grid
-    int K[DG_X3T_MAX], J[DG_X3T_MAX];
-    long off[DG_X3T_MAX];           // element offset of the weight inside a plane
-};
+// (X3TransposeTable: x3_table.h; the Adam step of a whole group writes the same copy itself, optim.hip adam_step_x3t_kernel)
 __global__ __launch_bounds__(256) void x3_transpose_kernel(const __bf16* __restrict__ src, __bf16* __restrict__ dst, long plane, X3TransposeTable t) {
     // the tile as 64 k rows x 32 words (a word = two neighbouring j of one k), pitch 33: the loads write rows, the stores read
     // columns -- 8 words W[8 q .. 8 q + 7][jp] give the 16-byte runs of output rows j = 2 jp (low halves) and 2 jp + 1 (high halves)

@@ -30,31 +30,22 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = p - step_size * (m / denom);
 }
+// The update of one flat range by blocks bid = 0 .. nb - 1 of 256 threads (grid-stride): the body of adam_step_kernel, and of one range of
+// adam_step_ranges_x3_kernel.
 // P16 = 1: also write a bf16 (RNE) shadow of the updated parameters for the bf16 matrix path (+2 B/param on 28);
 // P16 = 3: the three bf16 planes of the f32x3 matrix path (dg_split3; planes `pstride` elements apart, +6 B/param)
 template <int P16>
-__global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, long n,
-                                                        const double* __restrict__ state, float b1, float b2, float eps,
-                                                        float wd, float gscale, __bf16* __restrict__ p16, long pstride,
-                                                        const double* __restrict__ ctl) {
-    // ctl (or nullptr): the gradient scale and the go / no-go of this step come from device memory (dg_grad_clip_finalize on the same
-    // stream) instead of the host.  A skipped step returns before its first load: p, m, v and every derived form keep their bits.
-    if (ctl != nullptr) {
-        if (ctl[3] != 0.0) return;
-        gscale = (float)ctl[2];
-    }
-    const float step_size = (float)state[1];
-    const float bc2_sqrt = (float)state[2];
-    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+__device__ __forceinline__ void adam_range(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long n, float step_size, float bc2_sqrt, float omb1, float b2, float omb2,
+                                           float eps, float wd, float gscale, __bf16* __restrict__ p16, long pstride, long bid, long nb) {
     const long n4 = n >> 2;
-    long i0 = (long)blockIdx.x * 256 + threadIdx.x;
+    long i0 = bid * 256 + threadIdx.x;
     if constexpr (P16 == 3) {
         // plane outputs: 8 parameters per thread and trip, so that every plane store is 16 bytes (the 8-byte plane stores of the 4-parameter
         // trip made this form 15 % slower per byte than the plain one: 4.73 against 5.55 TB/s alone at 460 M parameters); same arithmetic
         typedef __bf16 bf16x8_a __attribute__((ext_vector_type(8)));
         const long n8 = (((size_t)p16 | (size_t)(pstride * 2)) & 15) == 0 ? n >> 3 : 0;      // a range that starts 8 bytes into a 16-byte plane granule keeps the 4-parameter trip
-        for (long i = i0; i < n8; i += (long)gridDim.x * 256) {
+        for (long i = i0; i < n8; i += nb * 256) {
             f32x4 pp[2], gg[2], mm[2], vv[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -83,7 +74,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
         }
         i0 += n8 * 2;                 // the 4-parameter loop below takes what is left (n8 > 0: at most one trip of one thread)
     }
-    for (long i = i0; i < n4; i += (long)gridDim.x * 256) {
+    for (long i = i0; i < n4; i += nb * 256) {
         f32x4 pp = *(const f32x4*)(p + i * 4);
         const f32x4 gg = *(const f32x4*)(g + i * 4);
         f32x4 mm = *(const f32x4*)(m + i * 4);
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
             *(dg_bf16x4_t*)(p16 + 2 * pstride + i * 4) = l;
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (bid == 0 && threadIdx.x == 0) {
         for (long e = n4 * 4; e < n; ++e) {
             float a = p[e], b = m[e], c = v[e];
             adam_one(a, g[e], b, c, gscale, wd, omb1, b2, omb2, bc2_sqrt, eps, step_size);
@@ -122,6 +113,22 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
             }
         }
     }
+}
+
+template <int P16>
+__global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, long n,
+                                                        const double* __restrict__ state, float b1, float b2, float eps,
+                                                        float wd, float gscale, __bf16* __restrict__ p16, long pstride,
+                                                        const double* __restrict__ ctl) {
+    // ctl (or nullptr): the gradient scale and the go / no-go of this step come from device memory (dg_grad_clip_finalize on the same
+    // stream) instead of the host.  A skipped step returns before its first load: p, m, v and every derived form keep their bits.
+    if (ctl != nullptr) {
+        if (ctl[3] != 0.0) return;
+        gscale = (float)ctl[2];
+    }
+    adam_range<P16>(p, g, m, v, n, (float)state[1], (float)state[2], 1.f - b1, b2, 1.f - b2, eps, wd, gscale, p16, pstride, (long)blockIdx.x,
+                    (long)gridDim.x);
 }
 
 extern "C" int dg_adam_advance(double* state, double lr, double beta1, double beta2, dg_stream_t stream) {
@@ -417,5 +424,200 @@ extern "C" int dg_adam_step_flat_c(float* p, const float* g, float* m, float* v,
         hipLaunchKernelGGL(adam_step_kernel<3>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
                            (__bf16*)out, (long)plane_elems, ctl);
     DG_CHECK_LAUNCH("adam_step_c");
+    return DG_OK;
+}
+
+// ---- the f32x3 step of a WHOLE group, transposed weight planes included (optim.Adam.step, active is None) -----------------------------
+// dg_adam_step_flat_x3 followed by dg_x3_transpose_planes reads back, microseconds later, the 6 B/param of planes the step wrote and
+// writes them again transposed (12 B/param on top of the step's 34).  Here the step of a conv weight keeps its plane values in LDS and
+// writes the transposed copy itself: 40 B/param, one pass.  One workgroup owns a 64 x TJ tile of a [K][J] weight image (J = 16 C;
+// K % 64 == 0 and J % TJ == 0: no ragged tile, no scalar path).  Thread (lk, lv) updates the 8-parameter runs lv and lv + TJ / 16 of
+// tile row lk -- adam_one / dg_split3 and the 16-byte plane stores of adam_range<3>'s 8-parameter trip --, then the tile leaves LDS
+// column-wise exactly as x3_transpose_kernel stores it.  TJ = 128 on 512 threads wherever J % 128 == 0 (every interior conv of the
+// model): rows of 512 contiguous bytes of p, g, m, v.  Alone on 224 M parameters of generator-shaped weights the 64 x 64 tile of the
+// transpose pass (256-byte rows) ran at 3.70 TB/s of its 40 B/param and 32 x 128 at 3.87, where the flat kernel makes 4.6-4.8 TB/s of its
+// 34 and the transpose pass 4.43 of its 12; 64 x 128 runs at 5.12 TB/s (1.75 ms against 1.58 + 0.61).  TJ = 64 on 256 threads serves
+// the weights with J % 128 == 64.  Everything else of the group (BatchNorm vectors, 3-channel
+// and ragged weights, the heads) goes through adam_step_ranges_x3_kernel: adam_range<3> over a table of ranges, ONE launch.
+#include "x3_table.h"
+template <int TJ>
+__global__ __launch_bounds__(4 * TJ) void adam_step_x3t_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const double* __restrict__ state, float b1, float b2,
+                                                            float eps, float wd, float gscale, __bf16* __restrict__ p3,
+                                                            __bf16* __restrict__ p3t, long plane, const double* __restrict__ ctl,
+                                                            X3TransposeTable t) {
+    // per plane the tile as 64 k rows x TJ / 2 words (a word = two neighbouring j of one k), pitch + 1: x3_transpose_kernel's tile
+    constexpr int TPR = TJ / 16;                 // threads per tile row, two 8-parameter runs each
+    __shared__ unsigned tile[3][64][TJ / 2 + 1];
+    typedef __bf16 bf16x8_a __attribute__((ext_vector_type(8)));
+    if (ctl != nullptr) {                 // (the same answer in every thread of the grid: nobody is left waiting at the barrier below)
+        if (ctl[3] != 0.0) return;
+        gscale = (float)ctl[2];
+    }
+    const float step_size = (float)state[1];
+    const float bc2_sqrt = (float)state[2];
+    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    int wi = 0;
+    while (wi + 1 < t.n && (int)blockIdx.x >= t.tile0[wi + 1]) ++wi;
+    const int K = t.K[wi], J = t.J[wi];
+    const long base = t.off[wi];
+    const int tj = J / TJ;
+    const int b = blockIdx.x - t.tile0[wi];
+    const int k0 = (b / tj) * 64, j0 = (b % tj) * TJ;
+    const int lk = threadIdx.x / TPR, lv = threadIdx.x % TPR;        // update: row k, 8-parameter runs lv and lv + TPR of the row
+    const int sq = threadIdx.x & 7, sjp = threadIdx.x >> 3;          // transposed store: k run 8 sq .. 8 sq + 7 of output rows 2 sjp, 2 sjp + 1
+    f32x4 pp[2][2], gg[2][2], mm[2][2], vv[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long e = base + (long)(k0 + lk) * J + j0 + (lv + TPR * h) * 8;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            pp[h][q] = *(const f32x4*)(p + e + 4 * q);
+            gg[h][q] = *(const f32x4*)(g + e + 4 * q);
+            mm[h][q] = *(const f32x4*)(m + e + 4 * q);
+            vv[h][q] = *(const f32x4*)(v + e + 4 * q);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long e = base + (long)(k0 + lk) * J + j0 + (lv + TPR * h) * 8;
+        dg_bf16x4_t hh[2], md[2], ll[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a = pp[h][q][j], bb = mm[h][q][j], c = vv[h][q][j];
+                adam_one(a, gg[h][q][j], bb, c, gscale, wd, omb1, b2, omb2, bc2_sqrt, eps, step_size);
+                pp[h][q][j] = a; mm[h][q][j] = bb; vv[h][q][j] = c;
+            }
+            *(f32x4*)(p + e + 4 * q) = pp[h][q];
+            *(f32x4*)(m + e + 4 * q) = mm[h][q];
+            *(f32x4*)(v + e + 4 * q) = vv[h][q];
+            dg_split3(pp[h][q], hh[q], md[q], ll[q]);
+        }
+        const bf16x8_a pl3[3] = {__builtin_shufflevector(hh[0], hh[1], 0, 1, 2, 3, 4, 5, 6, 7),
+                                 __builtin_shufflevector(md[0], md[1], 0, 1, 2, 3, 4, 5, 6, 7),
+                                 __builtin_shufflevector(ll[0], ll[1], 0, 1, 2, 3, 4, 5, 6, 7)};
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            *(bf16x8_a*)(p3 + pl * plane + e) = pl3[pl];
+            const u32x4 w = __builtin_bit_cast(u32x4, pl3[pl]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tile[pl][lk][(lv + TPR * h) * 4 + i] = w[i];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        unsigned w[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = tile[pl][8 * sq + i][sjp];
+        u32x4 lo, hi;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            lo[i] = (w[2 * i] & 0xffffu) | (w[2 * i + 1] << 16);
+            hi[i] = (w[2 * i] >> 16) | (w[2 * i + 1] & 0xffff0000u);
+        }
+        unsigned short* d = (unsigned short*)p3t + pl * plane + base + (long)(j0 + 2 * sjp) * K + k0 + 8 * sq;
+        *(u32x4*)d = lo;
+        *(u32x4*)(d + K) = hi;
+    }
+}
+
+#define DG_ADAM_RANGES_MAX 64
+struct AdamRangeTable {
+    int n;
+    int blk0[DG_ADAM_RANGES_MAX + 1];      // first block of range i (prefix sums); blk0[n] = grid
+    long off[DG_ADAM_RANGES_MAX], len[DG_ADAM_RANGES_MAX];
+};
+__global__ __launch_bounds__(256) void adam_step_ranges_x3_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                  float* __restrict__ v, const double* __restrict__ state, float b1,
+                                                                  float b2, float eps, float wd, float gscale, __bf16* __restrict__ p3,
+                                                                  long plane, const double* __restrict__ ctl, AdamRangeTable t) {
+    if (ctl != nullptr) {
+        if (ctl[3] != 0.0) return;
+        gscale = (float)ctl[2];
+    }
+    int ri = 0;
+    while (ri + 1 < t.n && (int)blockIdx.x >= t.blk0[ri + 1]) ++ri;
+    const long o = t.off[ri];
+    adam_range<3>(p + o, g + o, m + o, v + o, t.len[ri], (float)state[1], (float)state[2], 1.f - b1, b2, 1.f - b2, eps, wd, gscale, p3 + o,
+                  plane, (long)(blockIdx.x - t.blk0[ri]), (long)(t.blk0[ri + 1] - t.blk0[ri]));
+}
+
+// One f32x3 Adam step of a flat group of `numel` parameters as n_w tiled conv weights ([K][J] images at element offsets w_off: they
+// also get their transposed planes in pt_planes) and n_r plain ranges [r_off, r_off + r_len) (plain planes only).  ctl == nullptr: the
+// host's grad_scale; otherwise scale and go / no-go from the control block, as dg_adam_step_flat_c.  What neither list covers is left
+// untouched.  Host arrays, each list ascending and disjoint.
+extern "C" int dg_adam_step_group_x3(float* p, const float* g, float* m, float* v, size_t numel, const double* state, float beta1,
+                                     float beta2, float eps, float weight_decay, float grad_scale, const double* ctl, void* p_planes,
+                                     void* pt_planes, size_t plane_elems, const int64_t* w_off, const int* w_K, const int* w_J, int n_w,
+                                     const int64_t* r_off, const int64_t* r_len, int n_r, dg_stream_t stream) {
+    DG_CHECK_ARG(p && g && m && v && state && p_planes, "dg_adam_step_group_x3: null pointer");
+    DG_CHECK_ARG(n_w >= 0 && n_r >= 0 && (n_w == 0 || (pt_planes && w_off && w_K && w_J)) && (n_r == 0 || (r_off && r_len)),
+                 "dg_adam_step_group_x3: %d weights, %d ranges, or a null table", n_w, n_r);
+    DG_CHECK_ARG(plane_elems >= numel && plane_elems % 8 == 0, "dg_adam_step_group_x3: plane distance %zu for %zu parameters", plane_elems,
+                 numel);
+    DG_CHECK_ARG((((size_t)p | (size_t)g | (size_t)m | (size_t)v | (size_t)p_planes | (size_t)pt_planes) & 15) == 0,
+                 "dg_adam_step_group_x3: buffers must be 16-byte aligned");
+    int64_t end = 0;
+    for (int i = 0; i < n_w; ++i) {
+        const int K = w_K[i], J = w_J[i];
+        DG_CHECK_ARG(K >= 64 && J >= 64 && K % 64 == 0 && J % 64 == 0 && w_off[i] % 8 == 0 && w_off[i] >= end &&
+                         (size_t)(w_off[i] + (int64_t)K * J) <= numel,
+                     "dg_adam_step_group_x3: weight %d (K=%d, J=%d, offset %ld): K and J multiples of 64, offset a multiple of 8, ascending, "
+                     "inside %zu parameters", i, K, J, (long)w_off[i], numel);
+        end = w_off[i] + (int64_t)K * J;
+    }
+    end = 0;
+    for (int i = 0; i < n_r; ++i) {
+        DG_CHECK_ARG(r_len[i] >= 0 && r_off[i] % 8 == 0 && r_off[i] >= end && (size_t)(r_off[i] + r_len[i]) <= numel,
+                     "dg_adam_step_group_x3: range %d (offset %ld, %ld parameters): offset a multiple of 8, ascending, inside %zu parameters", i,
+                     (long)r_off[i], (long)r_len[i], numel);
+        end = r_off[i] + r_len[i];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    for (int TJ = 128; TJ >= 64; TJ -= 64) {      // the 64 x 128 tile where J allows it, 64 x 64 for the rest; 48 weights per launch
+        X3TransposeTable t;
+        t.n = 0;
+        long tiles = 0;
+        for (int i = 0; i <= n_w; ++i) {
+            if (i < n_w && (w_J[i] % 128 == 0) == (TJ == 128)) {
+                t.tile0[t.n] = (int)tiles;
+                t.K[t.n] = w_K[i]; t.J[t.n] = w_J[i]; t.off[t.n] = w_off[i];
+                tiles += (long)(w_K[i] / 64) * (w_J[i] / TJ);
+                ++t.n;
+            }
+            if (t.n == 0 || (i < n_w && t.n < DG_X3T_MAX)) continue;
+            DG_CHECK_ARG(tiles <= 0x7fffffffL, "dg_adam_step_group_x3: %ld tiles in one launch", tiles);
+            t.tile0[t.n] = (int)tiles;
+            if (TJ == 128)
+                hipLaunchKernelGGL(adam_step_x3t_kernel<128>, dim3((unsigned)tiles), dim3(512), 0, s, p, g, m, v, state, beta1, beta2, eps,
+                                   weight_decay, grad_scale, (__bf16*)p_planes, (__bf16*)pt_planes, (long)plane_elems, ctl, t);
+            else
+                hipLaunchKernelGGL(adam_step_x3t_kernel<64>, dim3((unsigned)tiles), dim3(256), 0, s, p, g, m, v, state, beta1, beta2, eps,
+                                   weight_decay, grad_scale, (__bf16*)p_planes, (__bf16*)pt_planes, (long)plane_elems, ctl, t);
+            DG_CHECK_LAUNCH("adam_step_x3t");
+            t.n = 0;
+            tiles = 0;
+        }
+    }
+    for (int i0 = 0; i0 < n_r; i0 += DG_ADAM_RANGES_MAX) {
+        AdamRangeTable t;
+        t.n = 0;
+        int blocks = 0;
+        for (int i = i0; i < n_r && t.n < DG_ADAM_RANGES_MAX; ++i) {
+            if (r_len[i] == 0) continue;
+            t.blk0[t.n] = blocks;
+            t.off[t.n] = r_off[i]; t.len[t.n] = r_len[i];
+            blocks += flat_grid((size_t)r_len[i] / 2);      // 8 parameters per thread and trip
+            ++t.n;
+        }
+        if (t.n == 0) continue;
+        t.blk0[t.n] = blocks;
+        hipLaunchKernelGGL(adam_step_ranges_x3_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, state, beta1, beta2, eps, weight_decay,
+                           grad_scale, (__bf16*)p_planes, (long)plane_elems, ctl, t);
+        DG_CHECK_LAUNCH("adam_step_ranges_x3");
+    }
     return DG_OK;
 }

@@ -40,14 +40,38 @@ def _bwd(f):
 FUSE_C3_DGRAD_ACT = __import__("os").environ.get("DG_FUSE_C3_DGRAD_ACT", "1") != "0"
 
 
-def _flat_grad_of(param):
-    """The flat-buffer gradient view of a parameter (optim.Adam installs it) when it is the live .grad:
-    backward kernels then accumulate into it directly and autograd gets None for that input, instead of
-    materialising a gradient tensor and running an ATen add per parameter per pass."""
+def _flat_grad_of(param, contiguous=False):
+    """(view, accumulate): the flat-buffer gradient view of a parameter (optim.Adam installs it) when it is the live .grad:
+    backward kernels then write into it directly and autograd gets None for that input, instead of
+    materialising a gradient tensor and running an ATen add per parameter per pass.  accumulate is False for the FIRST writer
+    since optim.Adam.zero_grad(lazy=True), which overwrites what the skipped fill left there, and True afterwards; asking clears the
+    mark, so the caller must write.  contiguous: the caller's kernel takes a contiguous view only; for any other it gets no view
+    and autograd's own accumulation adds to .grad, which is zero-filled here if it was still marked."""
     fg = getattr(param, "_dg_flat_grad", None)
-    if fg is not None and param.grad is fg:
-        return fg
-    return None
+    if fg is None or param.grad is not fg:
+        return None, True
+    fresh = getattr(param, "_dg_grad_unwritten", False)
+    if fresh:
+        param._dg_grad_unwritten = False
+    if contiguous and not fg.is_contiguous():
+        if fresh:
+            fg.zero_()
+        return None, True
+    return fg, not fresh
+
+
+def _flat_grad_pair(pa, pb):
+    """_flat_grad_of for two parameters one kernel writes under ONE accumulate flag (BatchNorm gamma and beta): views for both or for
+    neither; where only one of them has been written since a lazy zero_grad, the other is zero-filled and the kernel accumulates."""
+    (fa, acc_a), (fb, acc_b) = _flat_grad_of(pa), _flat_grad_of(pb)
+    if fa is None or fb is None:
+        for f, acc in ((fa, acc_a), (fb, acc_b)):
+            if f is not None and not acc:
+                f.zero_()
+        return None, None, True
+    if acc_a != acc_b:
+        (fb if acc_a else fa).zero_()
+    return fa, fb, acc_a or acc_b
 
 
 # Bucketed gradient exchange (trainer._GradBuckets): FINAL_PASS is True while the trainer issues the forward calls
@@ -115,9 +139,9 @@ def _conv_backward(ctx, transposed, dy):
     wg = (x, dy) if transposed else (dy, x)
     dw = None
     if ctx.needs_input_grad[1]:
-        fg = _flat_grad_of(w)
+        fg, acc = _flat_grad_of(w)
         if fg is not None:
-            ops.conv_wgrad(*wg, stride, pad, out=fg, accumulate=True)
+            ops.conv_wgrad(*wg, stride, pad, out=fg, accumulate=acc)
             _final(ctx.final, w)
         else:
             dw = ops.conv_wgrad(*wg, stride, pad)
@@ -184,9 +208,9 @@ class ConvC3Fn(Function):
             dx = ops.c3_dgrad(g, w, ops.ACT_NONE, act_out=y, in_act=act, slope=slope) if fuse else ops.c3_dgrad(g, w, ops.ACT_NONE)
         dw = None
         if ctx.needs_input_grad[1]:
-            fg = _flat_grad_of(ctx.wref)
-            if fg is not None and fg.is_contiguous():
-                ops.c3_wgrad(g, x, out=fg, accumulate=True, **fuse)
+            fg, acc = _flat_grad_of(ctx.wref, contiguous=True)
+            if fg is not None:
+                ops.c3_wgrad(g, x, out=fg, accumulate=acc, **fuse)
                 _final(ctx.final, ctx.wref)
             else:
                 dw = ops.c3_wgrad(g, x, **fuse)
@@ -213,9 +237,9 @@ class ConvTransposeC3Fn(Function):
         dx = ops.c3_fwd(g, w, ops.ACT_NONE) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
-            fg = _flat_grad_of(ctx.wref)
-            if fg is not None and fg.is_contiguous():
-                ops.c3_wgrad(x, g, out=fg, accumulate=True)
+            fg, acc = _flat_grad_of(ctx.wref, contiguous=True)
+            if fg is not None:
+                ops.c3_wgrad(x, g, out=fg, accumulate=acc)
                 _final(ctx.final, ctx.wref)
             else:
                 dw = ops.c3_wgrad(x, g)
@@ -260,9 +284,10 @@ class BatchNormActFn(Function):
         if not training:
             raise RuntimeError("BatchNormActFn: backward in eval mode is not supported")
         need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        fg, fb = _flat_grad_of(ctx.prefs[0]), _flat_grad_of(ctx.prefs[1])
-        if need_p and fg is not None and fb is not None:
-            dy, _, _ = ops.bn_act_bwd(dz, y, saved, gamma, beta, act, slope, out_grads=(fg, fb), planes_cm=ctx.dy_cm, planes_only=ctx.dy_po)
+        fg, fb, acc = _flat_grad_pair(ctx.prefs[0], ctx.prefs[1]) if need_p else (None, None, True)
+        if fg is not None:
+            dy, _, _ = ops.bn_act_bwd(dz, y, saved, gamma, beta, act, slope, out_grads=(fg, fb), planes_cm=ctx.dy_cm, planes_only=ctx.dy_po,
+                                      accumulate=acc)
             _final(ctx.final, ctx.prefs[0], ctx.prefs[1])
             return (dy,) + (None,) * 15
         dy, dgamma, dbeta = ops.bn_act_bwd(dz, y, saved, gamma, beta, act, slope, need_param_grads=need_p, planes_cm=ctx.dy_cm,
@@ -302,17 +327,18 @@ class BatchNormActConvTransposeC3Fn(Function):
         dz = ops.c3_fwd(g, w, ops.ACT_NONE) if ctx.needs_input_grad[0] or need_p else None
         dw = None
         if ctx.needs_input_grad[11]:
-            fg = _flat_grad_of(ctx.wref)
-            if fg is not None and fg.is_contiguous():
-                ops.c3_wgrad_bn(y, saved, gamma, beta, g, out=fg, accumulate=True, bn_act=bn_act)
+            fg, acc = _flat_grad_of(ctx.wref, contiguous=True)
+            if fg is not None:
+                ops.c3_wgrad_bn(y, saved, gamma, beta, g, out=fg, accumulate=acc, bn_act=bn_act)
                 _final(ctx.final, ctx.wref)
             else:
                 dw = ops.c3_wgrad_bn(y, saved, gamma, beta, g, bn_act=bn_act)
         if dz is None:
             return none[:11] + (dw,) + none[12:]
-        fgm, fb = _flat_grad_of(ctx.prefs[0]), _flat_grad_of(ctx.prefs[1])
-        if need_p and fgm is not None and fb is not None:
-            dy, _, _ = ops.bn_act_bwd(dz, y, saved, gamma, beta, bn_act, 0.0, out_grads=(fgm, fb), planes_cm=dy_cm, planes_only=dy_po)
+        fgm, fb, acc = _flat_grad_pair(ctx.prefs[0], ctx.prefs[1]) if need_p else (None, None, True)
+        if fgm is not None:
+            dy, _, _ = ops.bn_act_bwd(dz, y, saved, gamma, beta, bn_act, 0.0, out_grads=(fgm, fb), planes_cm=dy_cm, planes_only=dy_po,
+                                      accumulate=acc)
             _final(ctx.final, ctx.prefs[0], ctx.prefs[1])
             return (dy,) + none[1:11] + (dw,) + none[12:]
         dy, dgamma, dbeta = ops.bn_act_bwd(dz, y, saved, gamma, beta, bn_act, 0.0, need_param_grads=need_p, planes_cm=dy_cm, planes_only=dy_po)
@@ -462,9 +488,16 @@ def _all_or_none(grads, who):
 
 
 def _flat_grads_of(params):
-    fgs = [_flat_grad_of(p) for p in params]
-    if any(f is None for f in fgs):
-        raise RuntimeError("grouped launches need parameters whose .grad is the optimiser's flat gradient view (optim.Adam)")
+    """The flat gradient views of a grouped launch, which accumulates: a parameter no kernel has written since a lazy zero_grad
+    (_flat_grad_of) is zero-filled first."""
+    fgs = []
+    for p in params:
+        fg, acc = _flat_grad_of(p)
+        if fg is None:
+            raise RuntimeError("grouped launches need parameters whose .grad is the optimiser's flat gradient view (optim.Adam)")
+        if not acc:
+            fg.zero_()
+        fgs.append(fg)
     return fgs
 
 

@@ -76,6 +76,7 @@ class _FlatGradMixin:
             if flat is not None:
                 flat.zero_()
                 p.grad = flat
+                p._dg_grad_unwritten = False            # (optim.Adam.zero_grad(lazy=True) marks; this is a fill)
             elif p.grad is not None:
                 if set_to_none:
                     p.grad = None

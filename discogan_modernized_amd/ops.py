@@ -1007,8 +1007,9 @@ def bn_act_fwd(y, saved, gamma, beta, act, slope=0.2, planes_cm=False, planes_on
     return _bn_publish(form, z, extra, cm, po)
 
 
-def bn_act_bwd(dz, y, saved, gamma, beta, act, slope=0.2, need_param_grads=True, out_grads=None, planes_cm=False, planes_only=False):
-    """out_grads=(dgamma_buf, dbeta_buf): accumulate the parameter gradients into those buffers in place.
+def bn_act_bwd(dz, y, saved, gamma, beta, act, slope=0.2, need_param_grads=True, out_grads=None, planes_cm=False, planes_only=False,
+               accumulate=True):
+    """out_grads=(dgamma_buf, dbeta_buf): accumulate the parameter gradients into those buffers in place (accumulate=False: overwrite).
     planes_cm (f32x3 plane path): write dy's plane triple chunk-major (its reader is a window input-grad kernel)."""
     _check_dev(dz, y, allow16=True)
     dz = as_nhwc(dz)
@@ -1018,7 +1019,7 @@ def bn_act_bwd(dz, y, saved, gamma, beta, act, slope=0.2, need_param_grads=True,
     acc = 0
     if out_grads is not None:
         dgamma, dbeta = out_grads
-        acc = 1
+        acc = int(bool(accumulate))
     else:
         dgamma = torch.empty(c, device=y.device, dtype=torch.float32) if need_param_grads else None
         dbeta = torch.empty(c, device=y.device, dtype=torch.float32) if need_param_grads else None
@@ -1223,6 +1224,42 @@ def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scal
         _lib.check(_lib.load().dg_adam_step_flat(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1,
                                                  beta2,
                                                  eps, weight_decay, grad_scale, _stream()), "dg_adam_step_flat")
+
+
+# ADAM_FUSED_T: the f32x3 step of a whole group (optim.Adam.step, active is None) writes the transposed weight planes itself
+# (dg_adam_step_group_x3: 40 B/param of a conv weight) instead of dg_adam_step_flat_x3 followed by dg_x3_transpose_planes, which reads
+# the planes back (34 + 12 B/param).  Bit-identical; DG_ADAM_FUSED_T=0 restores the two-kernel form (A/B timing).
+ADAM_FUSED_T = _env_flag("DG_ADAM_FUSED_T", True)
+# LAZY_ZERO_GRAD: the trainer's iteration does not zero-fill the stepped flat gradient buffer (optim.Adam.zero_grad(lazy=True)); the
+# first weight-gradient kernel of every parameter overwrites instead of adding to zeros it would have to read (4 + 4 B/param).
+# 0 + x and x differ for x = -0 only, which changes no bit of p, m, v; DG_LAZY_ZERO_GRAD=0 restores the fill (A/B timing).
+LAZY_ZERO_GRAD = _env_flag("DG_LAZY_ZERO_GRAD", True)
+
+
+def adam_group_x3_table(weights, ranges):
+    """Host-side tables for adam_step_group_x3: weights = [(element offset, K, J = 16 C), ...] with K % 64 == 0 and J % 64 == 0 (stepped
+    by tiles, transposed planes included), ranges = [(begin, end), ...] for everything else; both ascending."""
+    import ctypes as C
+    nw, nr = len(weights), len(ranges)
+    return (nw, (C.c_int64 * max(nw, 1))(*[w[0] for w in weights]), (C.c_int * max(nw, 1))(*[w[1] for w in weights]),
+            (C.c_int * max(nw, 1))(*[w[2] for w in weights]),
+            nr, (C.c_int64 * max(nr, 1))(*[r[0] for r in ranges]), (C.c_int64 * max(nr, 1))(*[r[1] - r[0] for r in ranges]))
+
+
+def adam_step_group_x3(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale, p3, p3t, table, ctl=None):
+    """One f32x3 Adam step of the whole flat group ``p``: the weights of ``table`` also get their transposed planes in ``p3t``; the bits
+    of adam_step_flat(p3=...) followed by x3_transpose_planes.  ctl: as adam_step_flat (grad_scale is then unused)."""
+    _check_dev(p, g, m, v)
+    if ctl is not None:
+        _check_ctl(ctl, "adam_step_group_x3")
+    nw, w_off, w_k, w_j, nr, r_off, r_len = table
+    assert p3.shape == (3, p.numel()) and p3.stride(1) == 1 and (nw == 0 or (p3t.shape == p3.shape and p3t.stride(0) == p3.stride(0)))
+    nbytes = 40.0 * sum(int(w_k[i]) * int(w_j[i]) for i in range(nw)) + 34.0 * sum(int(r_len[i]) for i in range(nr))
+    with _hbm("adam", nbytes):
+        _lib.check(_lib.load().dg_adam_step_group_x3(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2, eps,
+                                                     weight_decay, grad_scale, _ptr(ctl), _ptr(p3), _ptr(p3t) if nw else None,
+                                                     p3.stride(0), w_off, w_k, w_j, nw, r_off, r_len, nr, _stream()),
+                   "dg_adam_step_group_x3")
 
 
 # ---- gradient norm / clipping / non-finite guard (include/discogan_hip.h: the control block ctl) ---------

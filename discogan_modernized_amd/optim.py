@@ -39,6 +39,7 @@ class Adam:
         self.state = torch.zeros(4, device=dev, dtype=torch.float64)
         self.offsets = offs
         self.ctl = None                                  # enable_grad_control()
+        self._unwritten = False                          # zero_grad(lazy=True): some parameter's gradient may still await its first writer
         with torch.no_grad():
             for p, off in zip(self.params, offs):
                 n = p.numel()
@@ -69,11 +70,28 @@ class Adam:
         self.flat_p3 = torch.empty((3, self.numel), device=self.flat_p.device, dtype=torch.bfloat16)
         ops.f32_to_bf16x3(self.flat_p, self.flat_p3)
         # the forward form of the plane kernel wants the conv weights' planes TRANSPOSED ([(r, s, c)][k]): a second buffer,
-        # same flat offsets, rewritten for all conv weights of the group by one launch behind every Adam step
+        # same flat offsets, rewritten with every Adam step: by the step's own kernel when the whole group is stepped (below),
+        # else for all conv weights of the group by one launch behind it
         convs = [(off, p.shape[0], 16 * p.shape[1]) for p, off in zip(self.params, self.offsets)
                  if p.dim() == 4 and tuple(p.shape[2:]) == (4, 4) and p.shape[0] > 1 and ops.is_krsc(p)]
         self.flat_p3t = torch.zeros((3, self.numel), device=self.flat_p.device, dtype=torch.bfloat16) if convs else None
         self._x3t_table = ops.x3_transpose_table(convs)
+        # a step of the WHOLE group writes the transposed planes itself (ops.adam_step_group_x3): the conv weights that are whole
+        # tiles (K and J multiples of 64) by tiles, every other parameter (with the padding behind it) as ranges, merged when adjacent, in one launch;
+        # conv weights among the ranges keep the transpose pass, over a table of just those
+        tiled = [c for c in convs if c[1] % 64 == 0 and c[2] % 64 == 0 and c[0] % 8 == 0]
+        tiled_offs = {c[0] for c in tiled}
+        rest = []
+        for p, off in zip(self.params, self.offsets):
+            if off in tiled_offs:
+                continue
+            end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            if rest and rest[-1][1] == off:
+                rest[-1][1] = end
+            else:
+                rest.append([off, end])
+        self._adam_group_table = ops.adam_group_x3_table(tiled, rest)
+        self._x3t_rest_table = ops.x3_transpose_table([c for c in convs if c[0] not in tiled_offs])
         conv_offs = {c[0] for c in convs}
         for p, off in zip(self.params, self.offsets):
             p._dg_x3 = (self.flat_p3, off, self.flat_p3t if off in conv_offs else None)
@@ -115,11 +133,44 @@ class Adam:
                 ops.x3_transpose_planes(self.flat_p3, self.flat_p3t, self._x3t_table)
 
     # -- torch.optim.Optimizer surface used by the reference loop ------------------------------------
-    def zero_grad(self, set_to_none: bool = True):
-        self.flat_g.zero_()
+    def zero_grad(self, set_to_none: bool = True, lazy: bool = False):
+        """``lazy`` (the trainer's own step; ops.LAZY_ZERO_GRAD): fill nothing, mark every parameter "not yet written" instead.  The
+        first backward kernel that writes a marked parameter's gradient (functional._flat_grad_of) OVERWRITES it and clears the mark;
+        what is still marked when the flat gradient is read (``step``, an exchange: ``fill_unwritten_grads``) is zero-filled then.
+        Until then ``p.grad`` of a marked parameter holds the last iteration's values: only for backward passes made of this
+        package's Functions (a torch-native AccumulateGrad would add to them).  The marks are host state that moves the same way
+        under hipGraph capture and in eager dispatch."""
+        if lazy and ops.LAZY_ZERO_GRAD:
+            self._unwritten = True
+        else:
+            self.flat_g.zero_()
+            self._unwritten = False
         for p in self.params:
+            p._dg_grad_unwritten = self._unwritten
             if p.grad is not p._dg_flat_grad:
                 p.grad = p._dg_flat_grad
+
+    def fill_unwritten_grads(self, ranges=None):
+        """Zero-fill the gradient of every parameter (inside the flat ``ranges``; None = the group) that no backward kernel has written
+        since ``zero_grad(lazy=True)``, on the current stream, neighbours in one fill: whoever reads the flat gradient calls this first."""
+        if not self._unwritten:
+            return
+        runs = []
+        for p, off in zip(self.params, self.offsets):
+            if not getattr(p, "_dg_grad_unwritten", False):
+                continue
+            end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            if ranges is not None and not any(b <= off and end <= e for b, e in ranges):
+                continue
+            p._dg_grad_unwritten = False
+            if runs and runs[-1][1] == off:
+                runs[-1][1] = end
+            else:
+                runs.append([off, end])
+        for b, e in runs:
+            self.flat_g[b:e].zero_()
+        if ranges is None:
+            self._unwritten = False
 
     def _sync_foreign_grads(self):
         # a caller may have replaced .grad (e.g. zero_grad(set_to_none=True) on a plain nn.Module)
@@ -127,9 +178,11 @@ class Adam:
             if p.grad is None:
                 p._dg_flat_grad.zero_()
                 p.grad = p._dg_flat_grad
+                p._dg_grad_unwritten = False
             elif p.grad is not p._dg_flat_grad and p.grad.data_ptr() != p._dg_flat_grad.data_ptr():
                 p._dg_flat_grad.copy_(p.grad)
                 p.grad = p._dg_flat_grad
+                p._dg_grad_unwritten = False
 
     def ranges_of(self, modules):
         """Flat [begin, end) ranges covering the parameters of the given modules (merged when adjacent)."""
@@ -152,6 +205,7 @@ class Adam:
         decay, no moment update.  None = the whole group."""
         g = self.param_groups[0]
         self._sync_foreign_grads()
+        self.fill_unwritten_grads()
         ranges = active if active is not None else [(0, self.numel)]
         ctl = self.ctl
         if ctl is not None:
@@ -165,6 +219,14 @@ class Adam:
         ops.adam_advance(self.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), ctl=ctl)
         p16 = getattr(self, "flat_p16", None)
         p3 = getattr(self, "flat_p3", None)
+        if p3 is not None and active is None and ops.ADAM_FUSED_T:
+            # the whole group on the f32x3 planes: one pass that also leaves the transposed weight planes (no transpose pass behind it)
+            ops.adam_step_group_x3(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.state, float(g["betas"][0]),
+                                   float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_scale), p3,
+                                   self.flat_p3t, self._adam_group_table, ctl=ctl)
+            if self._x3t_rest_table[0]:
+                ops.x3_transpose_planes(p3, self.flat_p3t, self._x3t_rest_table)
+            return
         for b, e in ranges:
             ops.adam_step_flat(self.flat_p[b:e], self.flat_g[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], self.state,
                                float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),

@@ -541,6 +541,7 @@ class DiscoGANTrainer:
         """all-reduce(sum) + Adam of flat ranges on the current stream (the step state was advanced by _adam_begin)."""
         from . import ops
         g = opt.param_groups[0]
+        opt.fill_unwritten_grads(ranges)                  # (networks outside the loss: nothing wrote their gradients)
         for b, e in ranges:
             scale = 1.0
             if self.xg is not None:
@@ -563,10 +564,11 @@ class DiscoGANTrainer:
             # left alone (it may still be in flight on the communication stream)
             if dstep and self._ev_dis_ready is not None and self._cap is None:
                 torch.cuda.current_stream(self.device).wait_event(self._ev_dis_ready)
-            (self.optim_dis if dstep else self.optim_gen).zero_grad()
+            # lazy: no fill -- the first weight-gradient kernel of every parameter overwrites (optim.Adam.zero_grad)
+            (self.optim_dis if dstep else self.optim_gen).zero_grad(lazy=True)
         else:
-            self.optim_gen.zero_grad()                   # image_translation.py:336-339
-            self.optim_dis.zero_grad()
+            self.optim_gen.zero_grad(lazy=not dstep)     # image_translation.py:336-339 (the side that is not stepped: a plain fill)
+            self.optim_dis.zero_grad(lazy=dstep)
         from . import ops as _ops
         # (the attributes may have been switched between iterations: tests run one trainer in several arithmetics)
         self.ctx.prec = {"f32": _ops.PREC_F32, "bf16": _ops.PREC_BF16, "f32x3": _ops.PREC_F32X3}[self.mfma_dtype]
@@ -639,6 +641,7 @@ class DiscoGANTrainer:
         """All-reduce (sum) of the stepped side's flat gradient buffer on the current stream; returns the 1/W scale."""
         if self.xg is None:
             return 1.0
+        opt.fill_unwritten_grads()
         if self.time_comm:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -675,6 +678,8 @@ class DiscoGANTrainer:
             return out
         if do_step:
             self.apply_step(iters)
+        else:
+            opt.fill_unwritten_grads()                        # the caller reads the gradients: none is left as the last iteration's
         return out
 
     def apply_step(self, iters):
@@ -723,6 +728,7 @@ class DiscoGANTrainer:
         else:
             out = self._fwd_bwd(A, B, iters, need_losses)
         if not do_step:
+            opt.fill_unwritten_grads()
             return out
         if dstep or not self._dec_done:
             # a D-step leaves on the communication stream; a G-step whose backward was not cut (two-chain schedule, gradient control)
@@ -1027,6 +1033,7 @@ class _GradBuckets:
         """After the backward: flush the buckets that did not report, then make the main stream wait for the updates."""
         tr = self.tr
         main = torch.cuda.current_stream(tr.device)
+        self.opt.fill_unwritten_grads()                   # before the flush reads them (every bucket launched early was written whole)
         for b in self.buckets:
             if not b["done"]:
                 self._launch(b, main, early=False, active=self.active)

@@ -510,6 +510,17 @@ int dg_adam_step_flat_x3(float* p, const float* g, float* m, float* v, size_t n,
                          void* p_planes, size_t plane_elems, dg_stream_t s);
 int dg_x3_transpose_planes(const void* src_planes, void* dst_planes, size_t plane_elems, const int64_t* w_off, const int* w_K,
                            const int* w_J, int n, dg_stream_t s);
+/* One f32x3 Adam step of a whole flat group of `numel` parameters that also writes the transposed weight planes: the bits of
+ * dg_adam_step_flat_x3 (ctl == NULL, the host's grad_scale) or dg_adam_step_flat_c form 3 (scale and go / no-go from ctl) followed by
+ * dg_x3_transpose_planes, without reading the plain planes back (40 instead of 34 + 12 B/param).  The group is given as two host
+ * lists, each ascending and disjoint: n_w conv weights ([K][J] images at element offsets w_off; K % 64 == 0, J % 64 == 0,
+ * w_off % 8 == 0), stepped by 64 x 128 tiles (64 x 64 where J % 128 != 0) that store p, m, v, the plain planes and the [J][K] planes in pt_planes; and n_r plain
+ * ranges [r_off, r_off + r_len) (r_off % 8 == 0: BatchNorm vectors, every other weight), stepped in ONE launch per 64 ranges with plain
+ * planes only.  Parameters in neither list keep their bits.  All buffers 16-byte aligned; p_planes and pt_planes are [3][plane_elems]. */
+int dg_adam_step_group_x3(float* p, const float* g, float* m, float* v, size_t numel, const double* state, float beta1, float beta2,
+                          float eps, float weight_decay, float grad_scale, const double* ctl, void* p_planes, void* pt_planes,
+                          size_t plane_elems, const int64_t* w_off, const int* w_K, const int* w_J, int n_w, const int64_t* r_off,
+                          const int64_t* r_len, int n_r, dg_stream_t s);
 /* plane_layout / dy_layout: 0 = pixel-major planes [M][C] (the tensor's own NHWC order); 1 = QUAD-CHUNK planes
  * [M / 4][C / 16][4 pixels][16 channels] (C % 64 == 0, M % 4 == 0): the 16-channel chunk of 4 consecutive pixels is one
  * 128-byte line, a 4-pixel block of all channels stays one contiguous run.  The window input-grad kernel fetches a 16-channel
