@@ -130,7 +130,10 @@ SIGNATURES = {
     "dg_dp_destroy": (_i, []),
     "dg_u8hwc_to_f32chw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "dg_image_prep": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "dg_sample_grid_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "dg_augment_draw": (_i, [C.c_uint64, _i, _l, _i, _i, _i, _i, _i, _p, _p]),
+    "dg_image_prep_aug": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "dg_augment_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
     "dg_adam_step_flat_bf16": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _p]),

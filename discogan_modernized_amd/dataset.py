@@ -22,6 +22,7 @@ There is no CPU fallback: batches are produced by the HIP kernel or not at all.
 """
 from __future__ import annotations
 
+import collections
 import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
@@ -30,7 +31,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 # dataset roots, adjustable like the reference's module-level paths (dataset.py:14-22)
 dataset_path = Path("./datasets")
@@ -187,14 +188,63 @@ def _crop_of(domain, width):
     raise ValueError(f"domain must be 'A', 'B' or None, got {domain!r}")
 
 
-def prepare_batch(src_u8, domain, image_size, out=None):
-    """Device batch uint8 [n, H, W, 3] -> float32 [n, 3, S, S] through ``dg_image_prep`` on the current stream."""
+# ---- training augmentation: random mirror + scale-jitter crop (DESIGN.md "Training augmentation") ---------------------------------------
+AUG_TOKENS = {"flip": 1, "crop": 2}       # DG_AUG_FLIP, DG_AUG_CROP
+
+
+class Augment(collections.namedtuple("Augment", "seed rank flags scale first_iteration")):
+    """What the training data's augmentation is keyed on: the draw of a sample is a pure function of (seed, rank, iteration, domain,
+    position in the batch); ``first_iteration`` is the iteration of the first batch a loader stages.  ``flags``: parse_augment's sum."""
+    __slots__ = ()
+
+    def size(self, image_size):
+        return augment_size(image_size, self.flags, self.scale)
+
+
+def parse_augment(spec):
+    """``--augment``: a comma list of ``flip`` and ``crop`` (empty = off) -> the flag sum the kernels take."""
+    flags = 0
+    for tok in (t.strip() for t in (spec or "").split(",")):
+        if not tok:
+            continue
+        if tok not in AUG_TOKENS:
+            raise ValueError(f"--augment takes a comma list of {sorted(AUG_TOKENS)}, got {tok!r}")
+        flags |= AUG_TOKENS[tok]
+    return flags
+
+
+def augment_name(flags):
+    return ",".join(t for t, bit in AUG_TOKENS.items() if flags & bit) or "off"
+
+
+def augment_size(image_size, flags, scale=1.125):
+    """The size L an image is (conceptually) prepared at before the S x S window is taken: round(S * scale) with ``crop``, else S."""
+    if not (scale >= 1.0 and scale < float("inf")):
+        raise ValueError(f"--augment_scale must be a finite number >= 1 (the window is cut OUT of the scaled image), got {scale}")
+    return max(int(round(image_size * scale)), image_size) if flags & AUG_TOKENS["crop"] else image_size
+
+
+def prepare_batch(src_u8, domain, image_size, out=None, aug=None):
+    """Device batch uint8 [n, H, W, 3] -> float32 [n, 3, S, S] through ``dg_image_prep`` on the current stream.
+    ``aug = (L, recs, rec_index)``: the augmented form (``dg_image_prep_aug``) -- prepared at L, the S x S window and mirror of each sample's
+    record; ``recs`` int32 [m, 4] on the device (ops.augment_draw), sample i takes row ``rec_index[i]`` (device int32 [>= n], every value a
+    row of ``recs``) or row i when ``rec_index`` is None."""
     if not (src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.shape[3] == 3 and src_u8.is_contiguous()):
         raise _lib.DiscoganHipError("prepare_batch needs a contiguous uint8 HIP tensor of shape [n, H, W, 3] (no CPU fallback)")
     n, h, w, _ = src_u8.shape
     x0, cw, erode, mode = _crop_of(domain, w)
     if out is None:
         out = torch.empty((n, 3, image_size, image_size), device=src_u8.device, dtype=torch.float32)
+    if aug is not None:
+        L, recs, rec_index = aug
+        ops.check_aug_table(recs, n if rec_index is None else 1, "prepare_batch")
+        if rec_index is not None and not (rec_index.is_cuda and rec_index.dtype == torch.int32 and rec_index.dim() == 1
+                                          and rec_index.is_contiguous() and rec_index.numel() >= n):
+            raise _lib.DiscoganHipError(f"prepare_batch: rec_index must be a contiguous int32 HIP vector of at least {n} positions")
+        _lib.check(_lib.load().dg_image_prep_aug(src_u8.data_ptr(), out.data_ptr(), n, h, w, x0, cw, erode, mode, image_size, int(L),
+                                                 recs.data_ptr(), None if rec_index is None else rec_index.data_ptr(),
+                                                 torch.cuda.current_stream().cuda_stream), "dg_image_prep_aug")
+        return out
     _lib.check(_lib.load().dg_image_prep(src_u8.data_ptr(), out.data_ptr(), n, h, w, x0, cw, erode, mode, image_size,
                                          torch.cuda.current_stream().cuda_stream), "dg_image_prep")
     return out
@@ -314,9 +364,14 @@ class DeviceLoader:
     The consumer's stream waits on the slot's event before it reads the batch, and the copy stream waits on the consumer's release
     event before it overwrites the slot's tensors (reference: DataLoader(num_workers=4, pin_memory=True) + ``.to(device)``,
     distributed_image_translation.py:209-216,462-463).  An exception in the background stage (a domain rule that does not fit an
-    image, a copy or kernel error) is re-raised in the consumer before the failed batch could be yielded -- never a stale batch."""
+    image, a copy or kernel error) is re-raised in the consumer before the failed batch could be yielded -- never a stale batch.
 
-    def __init__(self, source_A, source_B, domains, image_size, batches, device="cuda", workers=4, transform=None):
+    ``augment`` (an Augment record with flags; None = off): stage k draws the records of iteration ``first_iteration + k`` on the copy stream
+    (ops.augment_draw, one table per domain) and its prepare launches are the augmented ones.  A sample's record is that of its POSITION in
+    the batch, whatever image-size group it is launched with; the random stand-in for an unreadable file stays as it is.  The record tables
+    and the position vectors of the sub-launches belong to the slots and are allocated here, not in the stager thread."""
+
+    def __init__(self, source_A, source_B, domains, image_size, batches, device="cuda", workers=4, transform=None, augment=None):
         self.src = (source_A, source_B)
         self.domains = tuple(domains)
         self.S = image_size
@@ -330,6 +385,8 @@ class DeviceLoader:
         self.bmax = max((max(len(a), len(b)) for a, b in self.batches), default=0)
         self.pool = ThreadPoolExecutor(max_workers=max(1, workers))
         self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.augment = augment if augment is not None and augment.flags else None
+        self.L = self.augment.size(self.S) if self.augment else self.S
         self.slots = []
         for _ in range(2):
             slot = dict(ready=None, released=None, out=[None, None], error=None)
@@ -338,6 +395,11 @@ class DeviceLoader:
             slot["pinned"] = [torch.empty(max(c, 1), dtype=torch.uint8).pin_memory() for c in cap]
             slot["dev_u8"] = [torch.empty(max(c, 1), dtype=torch.uint8, device=self.device) for c in cap]
             slot["dev_f32"] = [torch.empty((self.bmax, 3, self.S, self.S), dtype=torch.float32, device=self.device) for _ in self.src]
+            if self.augment:
+                rows = max(self.bmax, 1)
+                slot["recs"] = [torch.empty((rows, 4), dtype=torch.int32, device=self.device) for _ in self.src]
+                slot["pos_pinned"] = [torch.empty(rows, dtype=torch.int32).pin_memory() for _ in self.src]
+                slot["pos_dev"] = [torch.empty(rows, dtype=torch.int32, device=self.device) for _ in self.src]
             self.slots.append(slot)
 
     def __len__(self):
@@ -378,6 +440,9 @@ class DeviceLoader:
                     view[r] = imgs[d][j]
                 plan.append((shape, pos, off))
                 off += len(pos) * per
+            if self.augment:                             # batch positions of every sub-launch, group after group (see the class docstring)
+                order = [j for _, pos, _ in plan for j in pos]
+                slot["pos_pinned"][d].numpy()[:len(order)] = order
             plans.append((plan, off, [j for j, im in enumerate(imgs[d]) if im is None]))
         with torch.cuda.stream(self.copy_stream):
             if slot["released"] is not None:             # the consumer of this slot's previous batch has finished reading
@@ -388,12 +453,24 @@ class DeviceLoader:
                 out = slot["dev_f32"][d][:n]
                 if used:
                     slot["dev_u8"][d][:used].copy_(slot["pinned"][d][:used], non_blocking=True)
-                for shape, pos, off in plan:             # one launch per image size (a batch of one size: one launch, in place)
+                aug = [None] * len(plan)
+                if self.augment and plan:
+                    a = self.augment
+                    recs = slot["recs"][d]
+                    ops.augment_draw(a.seed, a.rank, a.first_iteration + k, d, n, self.S, self.L, a.flags, out=recs)
+                    if len(plan[0][1]) == n:             # the whole batch in one launch: sample i is position i
+                        aug = [(self.L, recs, None)]
+                    else:
+                        placed = sum(len(pos) for _, pos, _ in plan)
+                        slot["pos_dev"][d][:placed].copy_(slot["pos_pinned"][d][:placed], non_blocking=True)
+                        first = [sum(len(pos) for _, pos, _ in plan[:g]) for g in range(len(plan))]
+                        aug = [(self.L, recs, slot["pos_dev"][d][f:f + len(pos)]) for f, (_, pos, _) in zip(first, plan)]
+                for (shape, pos, off), ag in zip(plan, aug):     # one launch per image size (a batch of one size: one launch, in place)
                     src = slot["dev_u8"][d][off:off + len(pos) * int(np.prod(shape))].view((len(pos),) + shape)
                     if len(pos) == n:
-                        prepare_batch(src, self.domains[d], self.S, out=out)
+                        prepare_batch(src, self.domains[d], self.S, out=out, aug=ag)
                     else:
-                        out[torch.tensor(pos, device=self.device)] = prepare_batch(src, self.domains[d], self.S)
+                        out[torch.tensor(pos, device=self.device)] = prepare_batch(src, self.domains[d], self.S, aug=ag)
                 for j in missing:                        # unreadable file: the reference substitutes np.random.rand(3, S, S)
                     out[j].copy_(torch.from_numpy(np.random.rand(3, self.S, self.S).astype(np.float32)))
                 slot["out"][d] = self.transform(out) if self.transform else out

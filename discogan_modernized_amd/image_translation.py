@@ -31,6 +31,10 @@ on the EMA weights (``trainer.ema_weights()``); the live weights and running sta
 Gradient control: ``--grad_clip F`` clips every step's gradient to the global norm F, ``--nonfinite_guard`` skips a step whose gradient holds
 an inf or a NaN, ``--log_grad_norm`` only measures; each of them appends `` GRAD: D <norm> G <norm> clipped c/n skipped s`` to the log line.
 All decided on the device (optim.Adam.enable_grad_control); the counters travel in ``train_state_*.pth``.
+Augmentation: ``--augment flip,crop`` (default: off) mirrors every training image with probability 1/2 and cuts a random ``image_size`` window
+out of its preparation at ``L = round(image_size * --augment_scale)`` -- one fused launch per batch and domain (dg_image_prep_aug for uint8
+rows, dg_augment_f32 for float tensors), records drawn on the device as a function of (seed, rank, iteration, domain, position), so
+``--resume`` continues the sequence without any saved state.  The held-out split, sample grids and evaluation are never augmented.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -105,6 +109,10 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
                    help="skip an optimiser step whose gradient holds an inf or a NaN (weights, Adam moments and step count stay as they are)")
     p.add_argument("--log_grad_norm", action="store_true",
                    help="append ' GRAD: D <norm> G <norm> clipped c/n skipped s' to every log line (implied by the two flags above)")
+    p.add_argument("--augment", type=str, default="",
+                   help="comma list of 'flip' (random left-right mirror) and 'crop' (prepare at --augment_scale times --image_size, cut a random "
+                        "--image_size window): training data only, on the device, keyed on (seed, rank, iteration); empty = off")
+    p.add_argument("--augment_scale", type=float, default=1.125, help="with --augment crop: L = round(image_size * scale), >= 1 (286/256 ~ 1.117)")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -152,29 +160,50 @@ def load_domains(args, device, rank=0, world_size=1):
     return A.to(device), B.to(device)
 
 
-class _ResidentData:
-    """Both domains resident in HBM (tensor files / synthetic): a batch is an index_select (+ the uint8 ingest kernel)."""
+def augment_of(args, rank=0):
+    """The dataset.Augment record of a run (``--augment`` / ``--augment_scale``), or None when augmentation is off.  Validates both."""
+    from . import dataset as ds
+    flags = ds.parse_augment(getattr(args, "augment", ""))
+    scale = float(getattr(args, "augment_scale", 1.125))
+    ds.augment_size(args.image_size, flags, scale)
+    return ds.Augment(int(args.seed), int(rank), flags, scale, 0) if flags else None
 
-    def __init__(self, A, B):
+
+class _ResidentData:
+    """Both domains resident in HBM (tensor files / synthetic): a batch is an index_select (+ the uint8 ingest kernel).
+    ``augment`` (dataset.Augment): batch ``start + i`` of the slice is augmented with the draw of iteration ``first_iteration + i``."""
+
+    def __init__(self, A, B, augment=None, image_size=None):
         self.A, self.B = A, B
         self.size = min(len(A), len(B))
+        self.augment, self.S = (augment if augment is not None and augment.flags else None), image_size
 
-    def epoch(self, batches, start=0):
-        for ia, ib in batches[start:]:
-            yield take_batch(self.A, ia), take_batch(self.B, ib)
+    def epoch(self, batches, start=0, first_iteration=None):
+        if self.augment is None:
+            for ia, ib in batches[start:]:
+                yield take_batch(self.A, ia), take_batch(self.B, ib)
+            return
+        it0 = start if first_iteration is None else first_iteration
+        for i, (ia, ib) in enumerate(batches[start:]):
+            yield (take_batch(self.A, ia, (self.augment, 0, it0 + i, self.S)), take_batch(self.B, ib, (self.augment, 1, it0 + i, self.S)))
 
 
 class _StreamedData:
     """Image files or pre-decoded shards: dataset.DeviceLoader stages the next batch while the current one trains."""
 
-    def __init__(self, src_A, src_B, domains, image_size, device, workers):
+    def __init__(self, src_A, src_B, domains, image_size, device, workers, augment=None):
         self.src, self.domains, self.S, self.device, self.workers = (src_A, src_B), domains, image_size, device, workers
         self.size = min(len(src_A), len(src_B))
+        self.augment = augment
 
-    def epoch(self, batches, start=0):
+    def epoch(self, batches, start=0, first_iteration=None):
         from . import dataset as ds
+        aug = self.augment
+        if aug is not None:
+            aug = aug._replace(first_iteration=start if first_iteration is None else first_iteration)
         loader = ds.DeviceLoader(self.src[0], self.src[1], self.domains, self.S,
-                                 [(a.cpu().numpy(), b.cpu().numpy()) for a, b in batches[start:]], device=self.device, workers=self.workers)
+                                 [(a.cpu().numpy(), b.cpu().numpy()) for a, b in batches[start:]], device=self.device, workers=self.workers,
+                                 augment=aug)
         try:
             yield from loader
         finally:
@@ -203,22 +232,35 @@ def open_data(args, device, rank=0, world_size=1):
                 src = "synthetic"
     domains = ds.task_domains(args.task_name)
     workers = getattr(args, "loader_workers", 4)
+    aug = augment_of(args, rank)                 # the TRAINING data only: the held-out split (samples.load_split) never passes through here
     if src == "files":
         data_A, data_B, _, _ = ds.get_data(args)
-        return _StreamedData(ds.FileSource(data_A), ds.FileSource(data_B), domains, args.image_size, device, workers), src
+        return _StreamedData(ds.FileSource(data_A), ds.FileSource(data_B), domains, args.image_size, device, workers, aug), src
     if src == "shards":
-        return _StreamedData(ds.ShardSource(args.shard_A), ds.ShardSource(args.shard_B), domains, args.image_size, device, workers), src
+        return _StreamedData(ds.ShardSource(args.shard_A), ds.ShardSource(args.shard_B), domains, args.image_size, device, workers, aug), src
     if src == "tensors" and not (args.data_A and args.data_B):
         raise ValueError("--data_source tensors needs --data_A and --data_B")
     if src == "synthetic":
         args = argparse.Namespace(**{**vars(args), "data_A": None, "data_B": None})
-    return _ResidentData(*load_domains(args, device, rank, world_size)), src
+    return _ResidentData(*load_domains(args, device, rank, world_size), augment=aug, image_size=args.image_size), src
 
 
-def take_batch(data, idx):
+def take_batch(data, idx, aug=None):
     """Rows ``idx`` of a resident domain as the float NCHW batch the networks take (image_translation.py:332-333).
-    uint8 [n,S,S,3] sources are normalised and transposed on the device (dataset.py:65-66)."""
+    uint8 [n,S,S,3] sources are normalised and transposed on the device (dataset.py:65-66).
+    ``aug = (dataset.Augment, domain 0 | 1, iteration, S)``: the augmented batch -- records drawn on the device for that iteration, then ONE
+    launch: dg_image_prep_aug on uint8 rows (the whole image, cv2's 8-bit resize), dg_augment_f32 on a float batch."""
     x = data.index_select(0, idx)
+    if aug is not None:
+        from . import dataset as ds, ops
+        a, d, iteration, S = aug
+        L = a.size(S)
+        recs = ops.augment_draw(a.seed, a.rank, iteration, d, len(idx), S, L, a.flags, device=x.device)
+        if x.dtype == torch.uint8:
+            return ds.prepare_batch(x, None, S, aug=(L, recs, None))
+        if x.shape[-1] != S:
+            raise ValueError(f"float training tensors are [n,3,S,S] with S = --image_size = {S}, got {tuple(x.shape)}")
+        return ops.augment_f32(x, L, recs)
     if x.dtype == torch.uint8:
         from . import ops
         return ops.u8hwc_to_f32chw(x)
@@ -276,6 +318,7 @@ def batches_per_epoch(args, data_size, world_size):
 def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=None):
     if args.task_name not in TASKS:
         raise ValueError(f"unknown task_name {args.task_name}; choose from {TASKS}")
+    aug = augment_of(args, rank)                          # a mistyped --augment token or a scale below 1 raises before anything is built
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
     if eval_interval > 0:
         from . import evaluate
@@ -296,6 +339,12 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     data_size = data.size
     if is_main:
         print(f"data source: {data_kind} ({data_size} images per domain)", flush=True)
+        if aug is not None:
+            from . import dataset as ds
+            parts = ([f"random {args.image_size} x {args.image_size} window"] if aug.flags & ds.AUG_TOKENS["crop"] else []) \
+                + (["random mirror"] if aug.flags & ds.AUG_TOKENS["flip"] else [])
+            print(f"augmentation: {ds.augment_name(aug.flags)} on the training data (prepared at L = {aug.size(args.image_size)}, "
+                  + ", ".join(parts) + "; keyed on seed, rank and iteration; held-out data is never augmented)", flush=True)
     # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
     # saving rank alone loads it, samples and evaluates
     split = None
@@ -336,7 +385,7 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     for epoch in range(start_epoch, args.epochs):
         batches = epoch_batches(args, epoch, data_size, rank, world_size, gperm, device)
         first = start_batch if epoch == start_epoch else 0
-        for i, (A, B) in enumerate(data.epoch(batches, first), start=first):
+        for i, (A, B) in enumerate(data.epoch(batches, first, iters), start=first):
             logging = iters % args.log_interval == 0
             out = trainer.train_iteration(A, B, iters, need_losses=logging or not lazy)
             if is_main and logging:

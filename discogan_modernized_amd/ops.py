@@ -218,6 +218,42 @@ def u8hwc_to_f32chw(x_u8, bgr=False):
     return y
 
 
+AUG_FLIP, AUG_CROP = 1, 2      # DG_AUG_* of include/discogan_hip.h
+
+
+def check_aug_table(recs, n, who):
+    """A record table as the augmentation kernels take it: int32 [m, 4] (ox, oy, flip, 0) on the device, contiguous, m >= n."""
+    if not (recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.shape[1] == 4 and recs.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who} needs a contiguous int32 HIP record table of shape [n, 4]")
+    if recs.shape[0] < n:
+        raise _lib.DiscoganHipError(f"{who}: the record table has {recs.shape[0]} rows for {n} samples")
+
+
+def augment_draw(seed, rank, iteration, domain, n, S, L, flags, out=None, device="cuda"):
+    """The augmentation records of one batch: int32 [n, 4] = (ox, oy, flip, 0) per position, drawn ON THE DEVICE as a pure function of
+    (seed, rank, iteration, domain 0 = A | 1 = B, position) -- dg_augment_draw; include/discogan_hip.h defines the generator.
+    ``out``: a table of at least n rows to fill (rows from n on stay as they are)."""
+    if out is None:
+        out = torch.empty((n, 4), device=device, dtype=torch.int32)
+    check_aug_table(out, n, "augment_draw")
+    _lib.check(_lib.load().dg_augment_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank), int(iteration), int(domain), int(n), int(S), int(L),
+                                           int(flags), _ptr(out), _stream()), "dg_augment_draw")
+    return out[:n]
+
+
+def augment_f32(x, L, recs):
+    """Float NCHW batch [n,3,S,S] -> [n,3,S,S]: bilinear resize to L x L (dg_image_prep's sampling, float arithmetic), the S x S window at
+    the record's (ox, oy), mirrored when its flip is set -- one launch (dg_augment_f32).  L = S with zero records returns x bitwise."""
+    _check_dev(x)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or not x.is_contiguous():
+        raise _lib.DiscoganHipError(f"augment_f32 needs a contiguous [n,3,S,S] batch, got {tuple(x.shape)}")
+    n, S = int(x.shape[0]), int(x.shape[3])
+    check_aug_table(recs, n, "augment_f32")
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().dg_augment_f32(_ptr(x), _ptr(out), n, S, int(L), _ptr(recs), _stream()), "dg_augment_f32")
+    return out
+
+
 def sample_grid(batches, rows, gap=2, bg=255):
     """1..8 float32 NCHW batches [n_c,3,S,S] (n_c >= rows) -> ONE uint8 canvas [rows*(S+gap)+gap, cols*(S+gap)+gap, 3] on the device:
     cell (r, c) = image r of batches[c], pixel = rint(clamp(x, 0, 1) * 255) (half to even, NaN -> 0), every other byte ``bg``

@@ -435,6 +435,32 @@ int dg_u8hwc_to_f32chw(const uint8_t* src, float* dst, int N, int H, int W, int 
  * and edge clamp (dataset.py:62), / 255 and CHW (dataset.py:65-66).  mode 0: float arithmetic, unrounded (what the
  * reference's float64 domain-'A' image gets); mode 1: cv2's 8-bit fixed-point path, result rounded to uint8 before / 255. */
 int dg_image_prep(const uint8_t* src, float* dst, int N, int H, int W, int x0, int cw, int erode, int mode, int S, dg_stream_t s);
+/* ---- training augmentation: random mirror (DG_AUG_FLIP) and scale-jitter crop (DG_AUG_CROP), on the device ----------------
+ * One training image, output size S: prepare it at L >= S exactly as dg_image_prep does (same crop, erosion, mode), take the window
+ * [oy, oy + S) x [ox, ox + S), 0 <= ox, oy <= L - S, and mirror it left-right when flip.  dg_image_prep_aug computes only the S x S output:
+ * its pixel (y, x) is pixel (oy + y, ox + (flip ? S - 1 - x : x)) of the size-L preparation, bitwise what dg_image_prep at L followed by
+ * the slice and the mirror gives; with L = S and a zero record it is bitwise dg_image_prep at S.
+ * A record is four int32 (ox, oy, flip, 0); a table is device int32 [n][4], 16-byte aligned.
+ *
+ * dg_augment_draw fills a table: record j is a pure function of (seed, rank, iteration, domain 0 = A | 1 = B, j) -- no generator state, no
+ * host value, no copy, no synchronisation.  With mix = the SplitMix64 output function (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ * z *= 0x94D049BB133111EB; z ^= z >> 31), G = 0x9E3779B97F4A7C15 and all arithmetic modulo 2^64:
+ *   k = mix(seed + G); k = mix(k ^ (uint64(uint32(rank)) << 32 | uint32(domain))); k = mix(k ^ uint64(iteration));
+ *   a = mix(k + G (2j + 1)); b = mix(k + G (2j + 2)); w0 = a >> 32, w1 = low 32 bits of a, w2 = b >> 32;
+ *   flip = w0 >> 31 (0 without DG_AUG_FLIP); ox = (uint64(w1) (L - S + 1)) >> 32, oy likewise from w2 (both 0 without DG_AUG_CROP).
+ *
+ * dg_image_prep_aug: sample i uses recs[rec_index[i]], or recs[i] when rec_index is NULL (rec_index: device int32 [N]; a launch over the
+ * images of one size out of a mixed-size batch passes their batch positions).  Every rec_index value must name a row of `recs`.  The
+ * record VALUES need no trust: offsets are clamped to [0, L - S], and every source coordinate is clamped into the cropped image.
+ * dg_augment_f32: the same on a resident float batch [N][3][S][S] -> [N][3][S][S] (no overlap): float bilinear resize S -> L (the sampling
+ * and float arithmetic of mode 0, no / 255; a tap of weight exactly 0 is left out), window, mirror; L = S with a zero record copies bitwise. */
+#define DG_AUG_FLIP 1
+#define DG_AUG_CROP 2
+int dg_augment_draw(uint64_t seed, int rank, int64_t iteration, int domain, int n, int S, int L, int flags,
+                    int32_t* recs /* device [n][4]: ox, oy, flip, 0 */, dg_stream_t s);
+int dg_image_prep_aug(const uint8_t* src, float* dst, int N, int H, int W, int x0, int cw, int erode, int mode, int S, int L,
+                      const int32_t* recs, const int32_t* rec_index /* or NULL */, dg_stream_t s);
+int dg_augment_f32(const float* src, float* dst, int N, int S, int L, const int32_t* recs, dg_stream_t s);
 /* ---- sample grids (image_translation.py:170-209): the inverse of the ingest, tiled -------------------------
    src: HOST table of `cols` device pointers, each a float batch [n_c][3][S][S] (NCHW, n_c >= rows).
    canvas: device uint8 [Hc][Wc][3], Hc = rows*(S+gap)+gap, Wc = cols*(S+gap)+gap.
