@@ -784,14 +784,15 @@ extern "C" int dg_x3_transpose_planes(const void* src_planes, void* dst_planes, 
                                       const int* w_K, const int* w_J, int n, dg_stream_t stream) {
     DG_CHECK_ARG(src_planes && dst_planes && w_off && w_K && w_J, "dg_x3_transpose_planes: null pointer");
     DG_CHECK_ARG(n >= 0, "dg_x3_transpose_planes: n=%d", n);
+    for (int i = 0; i < n; ++i)      // the whole table before the first launch: a refusal leaves dst untouched
+        DG_CHECK_ARG(w_K[i] >= 1 && w_J[i] >= 1 && w_off[i] >= 0 && (size_t)(w_off[i] + (long)w_K[i] * w_J[i]) <= plane_elems,
+                     "dg_x3_transpose_planes: weight %d (K=%d, J=%d, offset %ld) outside the plane", i, w_K[i], w_J[i], (long)w_off[i]);
     for (int i0 = 0; i0 < n; i0 += DG_X3T_MAX) {
         X3TransposeTable t;
         t.n = n - i0 < DG_X3T_MAX ? n - i0 : DG_X3T_MAX;
         int tiles = 0;
         for (int i = 0; i < t.n; ++i) {
             const int K = w_K[i0 + i], J = w_J[i0 + i];
-            DG_CHECK_ARG(K >= 1 && J >= 1 && w_off[i0 + i] >= 0 && (size_t)(w_off[i0 + i] + (long)K * J) <= plane_elems,
-                         "dg_x3_transpose_planes: weight %d (K=%d, J=%d, offset %ld) outside the plane", i0 + i, K, J, (long)w_off[i0 + i]);
             t.tile0[i] = tiles;
             t.K[i] = K; t.J[i] = J; t.off[i] = w_off[i0 + i];
             tiles += ((K + 63) / 64) * ((J + 63) / 64);

@@ -548,7 +548,8 @@ __global__ __launch_bounds__(256) void adam_step_ranges_x3_kernel(float* __restr
 // One f32x3 Adam step of a flat group of `numel` parameters as n_w tiled conv weights ([K][J] images at element offsets w_off: they
 // also get their transposed planes in pt_planes) and n_r plain ranges [r_off, r_off + r_len) (plain planes only).  ctl == nullptr: the
 // host's grad_scale; otherwise scale and go / no-go from the control block, as dg_adam_step_flat_c.  What neither list covers is left
-// untouched.  Host arrays, each list ascending and disjoint.
+// untouched.  Host arrays, each list ascending and disjoint in itself, and the two lists disjoint from each other (a weight that
+// overlaps a range is refused: its elements would be stepped twice); r_len[i] == 0 is accepted and covers nothing.
 extern "C" int dg_adam_step_group_x3(float* p, const float* g, float* m, float* v, size_t numel, const double* state, float beta1,
                                      float beta2, float eps, float weight_decay, float grad_scale, const double* ctl, void* p_planes,
                                      void* pt_planes, size_t plane_elems, const int64_t* w_off, const int* w_K, const int* w_J, int n_w,
@@ -576,6 +577,15 @@ extern "C" int dg_adam_step_group_x3(float* p, const float* g, float* m, float* 
                      (long)r_off[i], (long)r_len[i], numel);
         end = r_off[i] + r_len[i];
     }
+    // ... and from each other: one merge walk over the two ascending lists (a range of no parameters covers nothing)
+    for (int iw = 0, ir = 0; iw < n_w && ir < n_r;) {
+        const int64_t wb = w_off[iw], we = wb + (int64_t)w_K[iw] * w_J[iw], rb = r_off[ir], re = rb + r_len[ir];
+        if (r_len[ir] == 0 || re <= wb) ++ir;
+        else if (we <= rb) ++iw;
+        else
+            DG_CHECK_ARG(false, "dg_adam_step_group_x3: weight %d (offset %ld, %ld parameters) overlaps range %d (offset %ld, %ld parameters)",
+                         iw, (long)wb, (long)(we - wb), ir, (long)rb, (long)r_len[ir]);
+    }
     const hipStream_t s = (hipStream_t)stream;
     for (int TJ = 128; TJ >= 64; TJ -= 64) {      // the 64 x 128 tile where J allows it, 64 x 64 for the rest; 48 weights per launch
         X3TransposeTable t;
@@ -602,11 +612,11 @@ extern "C" int dg_adam_step_group_x3(float* p, const float* g, float* m, float* 
             tiles = 0;
         }
     }
-    for (int i0 = 0; i0 < n_r; i0 += DG_ADAM_RANGES_MAX) {
+    for (int i = 0; i < n_r;) {      // a table takes the next 64 ranges that hold parameters; the next one starts at the first range it left
         AdamRangeTable t;
         t.n = 0;
         int blocks = 0;
-        for (int i = i0; i < n_r && t.n < DG_ADAM_RANGES_MAX; ++i) {
+        for (; i < n_r && t.n < DG_ADAM_RANGES_MAX; ++i) {
             if (r_len[i] == 0) continue;
             t.blk0[t.n] = blocks;
             t.off[t.n] = r_off[i]; t.len[t.n] = r_len[i];

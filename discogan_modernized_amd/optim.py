@@ -15,6 +15,45 @@ from . import ops
 _ALIGN = 64  # floats (256 B)
 
 
+def _padded(n):
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n
+
+
+def x3_conv_images(entries):
+    """The conv weights of a flat group that get transposed planes, as (offset, K, J = 16 C) images.
+    entries = [(element offset, shape, is KRSC-strided), ...] in the group's order."""
+    return [(off, int(shape[0]), 16 * int(shape[1])) for off, shape, krsc in entries
+            if len(shape) == 4 and tuple(shape[2:]) == (4, 4) and shape[0] > 1 and shape[1] > 0 and krsc]
+
+
+def x3_group_partition(entries):
+    """How a step of the whole group (ops.adam_step_group_x3) takes the parameters ``entries`` (as x3_conv_images): (tiled, rest,
+    transposed_rest).  tiled: the conv images that are whole tiles (K and J multiples of 64, offset a multiple of 8), stepped by tiles
+    with their transposed planes; rest: [begin, end) ranges of every other parameter with the padding behind it, merged when adjacent,
+    none of them empty; transposed_rest: the conv images among the ranges, which keep the transpose pass.  Moves no tensor."""
+    convs = x3_conv_images(entries)
+    tiled = [c for c in convs if c[1] % 64 == 0 and c[2] % 64 == 0 and c[0] % 8 == 0]
+    tiled_offs = {c[0] for c in tiled}
+    rest = []
+    for off, shape, _ in entries:
+        n = _numel(shape)
+        if n == 0 or off in tiled_offs:      # (a parameter of no elements shares its offset with its successor and covers nothing)
+            continue
+        end = off + _padded(n)
+        if rest and rest[-1][1] == off:
+            rest[-1][1] = end
+        else:
+            rest.append([off, end])
+    return tiled, rest, [c for c in convs if c[0] not in tiled_offs]
+
+
 class Adam:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.params = [p for p in params]
@@ -72,26 +111,16 @@ class Adam:
         # the forward form of the plane kernel wants the conv weights' planes TRANSPOSED ([(r, s, c)][k]): a second buffer,
         # same flat offsets, rewritten with every Adam step: by the step's own kernel when the whole group is stepped (below),
         # else for all conv weights of the group by one launch behind it
-        convs = [(off, p.shape[0], 16 * p.shape[1]) for p, off in zip(self.params, self.offsets)
-                 if p.dim() == 4 and tuple(p.shape[2:]) == (4, 4) and p.shape[0] > 1 and ops.is_krsc(p)]
+        entries = [(off, tuple(p.shape), p.dim() == 4 and ops.is_krsc(p)) for p, off in zip(self.params, self.offsets)]
+        convs = x3_conv_images(entries)
         self.flat_p3t = torch.zeros((3, self.numel), device=self.flat_p.device, dtype=torch.bfloat16) if convs else None
         self._x3t_table = ops.x3_transpose_table(convs)
         # a step of the WHOLE group writes the transposed planes itself (ops.adam_step_group_x3): the conv weights that are whole
         # tiles (K and J multiples of 64) by tiles, every other parameter (with the padding behind it) as ranges, merged when adjacent, in one launch;
         # conv weights among the ranges keep the transpose pass, over a table of just those
-        tiled = [c for c in convs if c[1] % 64 == 0 and c[2] % 64 == 0 and c[0] % 8 == 0]
-        tiled_offs = {c[0] for c in tiled}
-        rest = []
-        for p, off in zip(self.params, self.offsets):
-            if off in tiled_offs:
-                continue
-            end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-            if rest and rest[-1][1] == off:
-                rest[-1][1] = end
-            else:
-                rest.append([off, end])
+        tiled, rest, transposed_rest = x3_group_partition(entries)
         self._adam_group_table = ops.adam_group_x3_table(tiled, rest)
-        self._x3t_rest_table = ops.x3_transpose_table([c for c in convs if c[0] not in tiled_offs])
+        self._x3t_rest_table = ops.x3_transpose_table(transposed_rest)
         conv_offs = {c[0] for c in convs}
         for p, off in zip(self.params, self.offsets):
             p._dg_x3 = (self.flat_p3, off, self.flat_p3t if off in conv_offs else None)

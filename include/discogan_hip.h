@@ -529,7 +529,8 @@ int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, int x_bf16, 
  * dg_conv_fwd_x3 with w_transposed != 0 reads the weight planes as wT[(r, s, c)][k] (k contiguous): a K-tile of the weight
  * operand is then 16 rows of 512 contiguous bytes instead of 256 pieces of 32 bytes (forward K loop 49-81 % -> ~90 % of the
  * matrix rate).  dg_x3_transpose_planes writes that copy for n conv weights of a plane buffer in one launch per 48 weights
- * ([K][J] images, J = 16 C, at element offsets w_off inside each plane; host arrays). */
+ * ([K][J] images, J = 16 C, at element offsets w_off inside each plane; host arrays, any order; the whole table is checked
+ * before the first launch). */
 int dg_f32_to_bf16x3(const float* x, void* y_planes, size_t n, size_t plane_elems, dg_stream_t s);
 int dg_adam_step_flat_x3(float* p, const float* g, float* m, float* v, size_t n, const double* state,
                          float beta1, float beta2, float eps, float weight_decay, float grad_scale,
@@ -539,7 +540,7 @@ int dg_x3_transpose_planes(const void* src_planes, void* dst_planes, size_t plan
 /* One f32x3 Adam step of a whole flat group of `numel` parameters that also writes the transposed weight planes: the bits of
  * dg_adam_step_flat_x3 (ctl == NULL, the host's grad_scale) or dg_adam_step_flat_c form 3 (scale and go / no-go from ctl) followed by
  * dg_x3_transpose_planes, without reading the plain planes back (40 instead of 34 + 12 B/param).  The group is given as two host
- * lists, each ascending and disjoint: n_w conv weights ([K][J] images at element offsets w_off; K % 64 == 0, J % 64 == 0,
+ * lists, each ascending and disjoint in itself and the two disjoint from each other (an overlap is refused): n_w conv weights ([K][J] images at element offsets w_off; K % 64 == 0, J % 64 == 0,
  * w_off % 8 == 0), stepped by 64 x 128 tiles (64 x 64 where J % 128 != 0) that store p, m, v, the plain planes and the [J][K] planes in pt_planes; and n_r plain
  * ranges [r_off, r_off + r_len) (r_off % 8 == 0: BatchNorm vectors, every other weight), stepped in ONE launch per 64 ranges with plain
  * planes only.  Parameters in neither list keep their bits.  All buffers 16-byte aligned; p_planes and pt_planes are [3][plane_elems]. */

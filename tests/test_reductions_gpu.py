@@ -14,6 +14,8 @@ from discogan_modernized_amd import _lib, losses, ops  # noqa: E402
 from tests import shape_ref as R  # noqa: E402
 from tests import test_ops_gpu as T  # noqa: E402
 from tests.gpu_util import DEV, nhwc  # noqa: E402
+from tests.adam_ref import hyper, split3  # noqa: E402
+from tests.adam_ref import one_step as adam_one_step  # noqa: E402
 from tests.shape_ref import assert_within, f64, gamma, rnd, violations  # noqa: E402
 
 EPS = 1e-5
@@ -404,14 +406,6 @@ def test_activations_past_the_grid_cap(act):
         assert float((f64(got)[-5:] - ref[-5:]).abs().max()) <= rtol * float(ref.abs().max()) + 1e-7
 
 
-def split3(p):
-    """torch's own three-plane split of an fp32 CPU tensor."""
-    hi = p.bfloat16()
-    mid = (p - hi.float()).bfloat16()
-    lo = (p - hi.float() - mid.float()).bfloat16()
-    return torch.stack([hi, mid, lo])
-
-
 @pytest.mark.parametrize("n,off", [(4194304 + 4 * 256 + 3, 4), (8388608 + 8 * 1000 + 5, 0)])
 def test_adam_forms_past_the_grid_cap(n, off):
     """test_adam_forms_agree's assertions at sizes where every thread takes a second trip (4096 blocks of 256 threads: four
@@ -423,17 +417,13 @@ def test_adam_forms_past_the_grid_cap(n, off):
     step, bc2 = lr / (1.0 - b1 ** 1), (1.0 - b2 ** 1) ** 0.5            # dg_adam_advance at t = 1
     st = state.cpu()
     assert float(st[0]) == 1.0 and abs(float(st[1]) - step) <= 1e-15 * step and abs(float(st[2]) - bc2) <= 1e-15 * bc2
-    # the kernel takes its hyper-parameters as fp32: the reference uses those values
-    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
-    b1f, b2f, epsf, wdf = f32(b1), f32(b2), f32(eps), f32(wd)
-    omb1, omb2 = f32(1.0 - b1f), f32(1.0 - b2f)                           # (both exact in fp32)
+    # the kernel takes its hyper-parameters as fp32: the reference uses those values (tests/adam_ref.py), and the device's own state
+    hp = hyper(b1, b2, eps, wd)
+    b2f, wdf, omb1, omb2 = hp["b2"], hp["wd"], hp["omb1"], hp["omb2"]
     sl = slice(off, off + n)
 
     def one_step(p0, g0, m0, v0):
-        gr = g0 + wdf * p0
-        m = m0 + (gr - m0) * omb1
-        v = v0 * b2f + omb2 * gr * gr
-        return p0 - step * (m / (v.sqrt() / bc2 + epsf)), m, v
+        return adam_one_step(p0, g0, m0, v0, hp, float(st[1]), float(st[2]))
 
     p0, g0, m0, v0 = (f64(t[sl]) for t in base)
     pr, mr, vr = one_step(p0, g0, m0, v0)
