@@ -35,6 +35,12 @@ Augmentation: ``--augment flip,crop`` (default: off) mirrors every training imag
 out of its preparation at ``L = round(image_size * --augment_scale)`` -- one fused launch per batch and domain (dg_image_prep_aug for uint8
 rows, dg_augment_f32 for float tensors), records drawn on the device as a function of (seed, rank, iteration, domain, position), so
 ``--resume`` continues the sequence without any saved state.  The held-out split, sample grids and evaluation are never augmented.
+Image history pool: ``--image_pool N`` (default 0 = off; 50 is customary) keeps N generated images per domain on the device
+(``N * 3 * image_size^2 * 4`` bytes each).  In a D-step -- only there -- each discriminator is trained on the pool's exchange of the newest
+fakes: stored and passed on while the pool fills, afterwards swapped with a random stored image with probability 1/2 (CycleGAN's
+``ImagePool``).  One fused launch per domain (dg_pool_exchange) on records drawn on the device from (seed, rank, iteration, domain), so graph
+replay and ``--resume`` reproduce the run bitwise; the pools travel in ``train_state_*.pth`` (key ``image_pool``).  A D-step's logged GEN / FM
+values are then computed on the pooled fakes; G-steps, reconstructions, sample grids and evaluation never see a pool.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -55,7 +61,7 @@ from pathlib import Path
 
 import torch
 
-from .trainer import DiscoGANTrainer
+from .trainer import DiscoGANTrainer, check_image_pool
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -113,6 +119,9 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
                    help="comma list of 'flip' (random left-right mirror) and 'crop' (prepare at --augment_scale times --image_size, cut a random "
                         "--image_size window): training data only, on the device, keyed on (seed, rank, iteration); empty = off")
     p.add_argument("--augment_scale", type=float, default=1.125, help="with --augment crop: L = round(image_size * scale), >= 1 (286/256 ~ 1.117)")
+    p.add_argument("--image_pool", type=int, default=0,
+                   help="history pool of generated images per domain for the discriminator steps (CycleGAN's ImagePool; 50 is the customary "
+                        "size; 0 = off): N * 3 * image_size^2 * 4 bytes of device memory per domain, keyed on (seed, rank, iteration)")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -319,6 +328,7 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     if args.task_name not in TASKS:
         raise ValueError(f"unknown task_name {args.task_name}; choose from {TASKS}")
     aug = augment_of(args, rank)                          # a mistyped --augment token or a scale below 1 raises before anything is built
+    image_pool = check_image_pool(getattr(args, "image_pool", 0))           # likewise: a negative --image_pool
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
     if eval_interval > 0:
         from . import evaluate
@@ -345,6 +355,10 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                 + (["random mirror"] if aug.flags & ds.AUG_TOKENS["flip"] else [])
             print(f"augmentation: {ds.augment_name(aug.flags)} on the training data (prepared at L = {aug.size(args.image_size)}, "
                   + ", ".join(parts) + "; keyed on seed, rank and iteration; held-out data is never augmented)", flush=True)
+        if image_pool > 0:
+            print(f"image pool: {image_pool} images per domain ({image_pool * 3 * args.image_size ** 2 * 4 / 2 ** 20:.1f} MiB each) for the "
+                  "discriminator steps; keyed on seed, rank and iteration; generator steps and reconstructions see the newest fakes",
+                  flush=True)
     # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
     # saving rank alone loads it, samples and evaluates
     split = None

@@ -254,6 +254,51 @@ def augment_f32(x, L, recs):
     return out
 
 
+POOL_MAX_BATCH = 4096          # samples per pool batch (dg_pool_draw scans the batch in every thread)
+
+
+def check_pool_table(recs, n, who):
+    """A record table as the pool kernels take it: int32 [m, 4] (src, slot, st_src, 0) on the device, contiguous, m >= n."""
+    if not (recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.shape[1] == 4 and recs.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who} needs a contiguous int32 HIP record table of shape [n, 4]")
+    if recs.shape[0] < n:
+        raise _lib.DiscoganHipError(f"{who}: the record table has {recs.shape[0]} rows for {n} samples")
+
+
+def pool_draw(seed, rank, iteration, domain, n, P, filled, out=None, device="cuda"):
+    """The image-pool records of one batch: int32 [n, 4] = (src, slot, st_src, 0) per position, the in-order semantics of a pool of P slots
+    with ``filled`` in use resolved ON THE DEVICE as a pure function of (seed, rank, iteration, domain 0 = A | 1 = B, position) --
+    dg_pool_draw; include/discogan_hip.h defines the draw and the record rule.  ``out``: a table of at least n rows to fill (rows from n on
+    stay as they are).  The caller advances ``filled`` to min(P, filled + n)."""
+    if out is None:
+        out = torch.empty((n, 4), device=device, dtype=torch.int32)
+    check_pool_table(out, n, "pool_draw")
+    _lib.check(_lib.load().dg_pool_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank), int(iteration), int(domain), int(n), int(P), int(filled),
+                                        _ptr(out), _stream()), "dg_pool_draw")
+    return out[:n]
+
+
+def pool_exchange(x, pool, recs, out=None):
+    """Apply a record table to a batch ``x`` [n, ...] and a pool [P, ...] of images of the same shape, in ONE launch (dg_pool_exchange):
+    ``out[j] = pool[slot] if src == -1 else x[src]``, and where ``slot >= 0`` then ``pool[slot] = x[st_src]``.  Returns ``out`` (a new
+    tensor like x unless given); the pool is updated in place, x is only read.  A copy: every bit pattern survives."""
+    _check_dev(x, pool, out)
+    if x.dim() < 2 or pool.dim() != x.dim() or tuple(pool.shape[1:]) != tuple(x.shape[1:]) or not (x.is_contiguous() and pool.is_contiguous()):
+        raise _lib.DiscoganHipError(f"pool_exchange needs a contiguous batch [n, ...] and pool [P, ...] of one image shape, got "
+                                    f"{tuple(x.shape)} and {tuple(pool.shape)}")
+    n, P = int(x.shape[0]), int(pool.shape[0])
+    if n < 1 or P < 1 or x[0].numel() < 1:
+        raise _lib.DiscoganHipError(f"pool_exchange: empty batch, pool or image ({tuple(x.shape)}, {tuple(pool.shape)})")
+    check_pool_table(recs, n, "pool_exchange")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+        raise _lib.DiscoganHipError(f"pool_exchange: out must be contiguous and shaped like x, got {tuple(out.shape)}")
+    elems = x[0].numel()
+    _lib.check(_lib.load().dg_pool_exchange(_ptr(x), _ptr(pool), _ptr(out), n, P, elems, _ptr(recs), _stream()), "dg_pool_exchange")
+    return out
+
+
 def sample_grid(batches, rows, gap=2, bg=255):
     """1..8 float32 NCHW batches [n_c,3,S,S] (n_c >= rows) -> ONE uint8 canvas [rows*(S+gap)+gap, cols*(S+gap)+gap, 3] on the device:
     cell (r, c) = image r of batches[c], pixel = rint(clamp(x, 0, 1) * 255) (half to even, NaN -> 0), every other byte ``bg``

@@ -26,6 +26,7 @@ Differences that do not change any result:
 from __future__ import annotations
 
 import contextlib
+import numbers
 from itertools import chain
 from types import SimpleNamespace
 
@@ -36,13 +37,14 @@ from . import functional as F_
 from . import losses as L
 from . import optim
 from .model import Discriminator, Generator
+from .pool import ImagePool
 
 LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A", "recon_loss_B",
             "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")
 
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
-                ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False)
+                ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0)
 
 
 def check_ema_decay(decay):
@@ -61,11 +63,34 @@ def check_grad_clip(grad_clip):
     return grad_clip
 
 
+def check_image_pool(size):
+    """``image_pool``: 0 = no history pool of generated images, else the number of image slots per domain (50 is customary).  Returns it
+    as an int."""
+    if isinstance(size, bool) or not isinstance(size, numbers.Integral) or size < 0:
+        raise ValueError(f"image_pool must be an integer >= 0 (0 = off), got {size!r}")
+    return int(size)
+
+
 def format_grad_suffix(dis, gen):
     """The log suffix of gradient control from the two optimisers' ``grad_stats()``: each side's norm of its last step, then the
     counters of both sides together."""
     return (f" GRAD: D {dis['norm']:.4e} G {gen['norm']:.4e} clipped {dis['clipped'] + gen['clipped']}/{dis['steps'] + gen['steps']}"
             f" skipped {dis['skipped'] + gen['skipped']}")
+
+
+class IterationOutputs(SimpleNamespace):
+    """What ``forward_losses`` / ``train_iteration`` return: the loss scalars and the tensors of the iteration as attributes, plus
+    ``BA_seen`` / ``AB_seen`` = the fake batches the discriminators were given -- ``BA`` / ``AB`` themselves unless a history pool
+    exchanged them (``seen``: None, or ``dict(BA=, AB=)`` of a pooled D-step).  The two are properties, not attributes of their own:
+    whatever enumerates the returned tensors (``vars(out)``: bench.py --dump-outputs) finds the same set with and without the feature."""
+
+    @property
+    def BA_seen(self):
+        return self.BA if self.seen is None else self.seen["BA"]
+
+    @property
+    def AB_seen(self):
+        return self.AB if self.seen is None else self.seen["AB"]
 
 
 def default_args(**over):
@@ -133,6 +158,19 @@ class DiscoGANTrainer:
         if self.grad_control:
             self.optim_gen.enable_grad_control(grad_clip, guard)
             self.optim_dis.enable_grad_control(grad_clip, guard)
+        # History pool of generated images (image_pool = P > 0; pool.ImagePool): in a D-step -- and only there -- D_A is trained on
+        # pool_BA.exchange(BA) and D_B on pool_AB.exchange(AB), a mix of this iteration's fakes and earlier ones, instead of BA / AB.  The
+        # two record tables are drawn on the device ahead of the iteration's dispatch, outside any capture (_pool_draw), keyed on
+        # (seed, data-parallel rank, iteration, domain): every rank pools its own fakes, and a resumed run continues the sequence.  Each
+        # exchange is ONE launch on the stream of the discriminator pass that consumes it, reading only fixed device addresses, so it is
+        # captured like any other kernel.  G-steps, the reconstruction passes and sampling never see a pool.
+        P = check_image_pool(getattr(self.args, "image_pool", 0))
+        self.pool_BA = self.pool_AB = None
+        if P > 0:
+            rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+            pseed = 0 if seed is None else seed
+            self.pool_BA = ImagePool(P, image_size, pseed, rank, 0, device=self.device)      # domain A: the fakes D_A sees
+            self.pool_AB = ImagePool(P, image_size, pseed, rank, 1, device=self.device)      # domain B: the fakes D_B sees
         self._graphs = {}
         self._static = None
         # The A-side chain (G_A, D_A) runs on a second HIP stream next to the B-side chain (G_B, D_B):
@@ -321,8 +359,8 @@ class DiscoGANTrainer:
             return ra, rb
 
         want_recon = need_losses or not (dstep and skip)
-        BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake = \
-            self._two_chain_forward(A, B, lv, pair, gen_ctx, main, side, want_recon)
+        (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
+         seen) = self._two_chain_forward(A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side)
         assert nfm == len(A_feats_real)
         sl = [lv[i] for i in range(8 + 2 * nfm)]
         terms = {}
@@ -363,14 +401,14 @@ class DiscoGANTrainer:
         (gen_loss_A, gen_loss_B, fm_loss_A, fm_loss_B, dis_loss_A, dis_loss_B, gen_loss, dis_loss) = \
             F_.LossMixFn.apply(lv, nfm, rate, arch, which, idx, *[terms[i] for i in idx])
         recon_loss_A, recon_loss_B = terms[0], terms[1]
-        return SimpleNamespace(
+        return IterationOutputs(
             gen_loss=gen_loss, dis_loss=dis_loss, gen_loss_A=gen_loss_A, gen_loss_B=gen_loss_B,
             fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=recon_loss_A, recon_loss_B=recon_loss_B,
-            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB,
+            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
             A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
             A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv)
 
-    def _two_chain_forward(self, A, B, lv, pair, gen_ctx, main, side, want_recon):
+    def _two_chain_forward(self, A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side):
         """The symmetric two-chain order: G_A(B) | G_B(A), G_A(AB) | G_B(BA), D_A(A) | D_B(B), D_A(BA) | D_B(AB), each pair in lock step.
         (Round 4 tried a DEPHASED order -- side: D_A(A), G_A(B), G_A(AB), D_A(BA); main: G_B(A), D_B(B), G_B(BA), D_B(AB) -- so that one
         chain's HBM-bound BatchNorm kernels would meet the other chain's conv kernels instead of its BatchNorm kernels: bitwise
@@ -416,9 +454,18 @@ class DiscoGANTrainer:
             lv[:2].fill_(float("nan"))
         (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = pair(
             self.discriminator_A.forward_steps(A), self.discriminator_B.forward_steps(B))
+        # the fakes the discriminators see: in a D-step with a history pool the exchanged batches, each on its consumer's stream (BA was
+        # produced on `side`, where D_A runs; AB on `main`, where D_B runs: no new join)
+        BA_seen, AB_seen, seen = BA, AB, None
+        if dstep and self.pool_BA is not None:
+            with on_side():
+                BA_seen = self.pool_BA.exchange(BA)
+            AB_seen = self.pool_AB.exchange(AB)
+            seen = dict(BA=BA_seen, AB=AB_seen)
         (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = pair(
-            self.discriminator_A.forward_steps(BA), self.discriminator_B.forward_steps(AB))
-        return BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake
+            self.discriminator_A.forward_steps(BA_seen), self.discriminator_B.forward_steps(AB_seen))
+        return (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
+                seen)
 
     def _forward_losses_grouped(self, A, B, iters, need_losses=True):
         """image_translation.py:342-382 with every pair of passes as grouped launches (model.group_generators /
@@ -466,10 +513,14 @@ class DiscoGANTrainer:
         else:
             lv[:2].fill_(float("nan"))
             terms[0], terms[1] = sl[0], sl[1]
+        BA_seen, AB_seen, seen = BA, AB, None
         with on_side():
             if dstep:
+                if self.pool_BA is not None:                 # the history pool: both exchanges on the discriminators' stream
+                    BA_seen, AB_seen = self.pool_BA.exchange(BA), self.pool_AB.exchange(AB)
+                    seen = dict(BA=BA_seen, AB=AB_seen)
                 (A_dis_real, A_feats_real), (A_dis_fake, A_feats_fake), (B_dis_real, B_feats_real), (B_dis_fake, B_feats_fake) = \
-                    group_discriminators([dA, dA, dB, dB], [A, BA, B, AB])
+                    group_discriminators([dA, dA, dB, dB], [A, BA_seen, B, AB_seen])
             else:
                 with torch.no_grad():
                     (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = group_discriminators([dA, dB], [A, B])
@@ -488,10 +539,10 @@ class DiscoGANTrainer:
         which, idx = (7, (2, 3, 5, 6)) if dstep else (6, tuple([0, 1, 4, 7] + fmA + fmB))
         (gen_loss_A, gen_loss_B, fm_loss_A, fm_loss_B, dis_loss_A, dis_loss_B, gen_loss, dis_loss) = \
             F_.LossMixFn.apply(lv, nfm, rate, 0, which, idx, *[terms[i] for i in idx])
-        return SimpleNamespace(
+        return IterationOutputs(
             gen_loss=gen_loss, dis_loss=dis_loss, gen_loss_A=gen_loss_A, gen_loss_B=gen_loss_B,
             fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=terms[0], recon_loss_B=terms[1],
-            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB,
+            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
             A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
             A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, backward_cut=cut)
 
@@ -651,12 +702,26 @@ class DiscoGANTrainer:
             return scale
         return self.xg.all_reduce_sum_(opt.flat_g)
 
+    def _pool_draw(self, A, B, iters):
+        """With a history pool, ahead of a D-step's dispatch and outside any capture: the record tables of this iteration's two
+        exchanges (BA = G_A(B) has B's batch size, AB = G_B(A) has A's).  Eager launches on the current stream, which everything the
+        iteration issues -- eagerly or by graph replay -- is ordered behind."""
+        if self.pool_BA is not None and self.is_dis_step(iters):
+            self.pool_BA.draw(iters, B.shape[0])
+            self.pool_AB.draw(iters, A.shape[0])
+
     def train_iteration(self, A, B, iters, do_step=True, need_losses=True):
         """One full iteration; returns the namespace of (device) loss scalars.  need_losses=False tells the
         trainer that this iteration's loss values will not be read (no log line): a D-step then skips the two
-        reconstruction passes, which feed only the log (weights and optimiser state are unaffected)."""
+        reconstruction passes, which feed only the log (weights and optimiser state are unaffected).
+
+        The namespace carries ``BA_seen`` / ``AB_seen``, the fake batches the discriminators were given: ``BA`` / ``AB`` themselves in a
+        G-step and without a history pool; with ``image_pool > 0`` a D-step's exchanged batches (detached).  Every fake pass of a D-step
+        then runs on the pooled fakes, so the GEN and FM values a D-step LOGS (they step nothing there) are computed on them too;
+        RECON always comes from the unpooled ``AB`` / ``BA``."""
         dstep = self.is_dis_step(iters)
         opt = self.optim_dis if dstep else self.optim_gen
+        self._pool_draw(A, B, iters)
         if self.graph_overlap:
             return self._train_iteration_graph_overlap(A, B, iters, do_step, need_losses)
         bucketed = self._buckets is not None and not dstep and do_step and self.xg is not None and not self.grad_control
@@ -854,6 +919,8 @@ class DiscoGANTrainer:
                   optim_gen=self.optim_gen.state_dict(), optim_dis=self.optim_dis.state_dict())
         if self.ema is not None:
             st["ema"] = self.ema.state_dict()
+        if self.pool_BA is not None:
+            st["image_pool"] = dict(BA=self.pool_BA.state_dict(), AB=self.pool_AB.state_dict())
         if extra:
             st["loader"] = dict(extra)
         return st
@@ -868,6 +935,15 @@ class DiscoGANTrainer:
                 self.ema.load_state_dict(st["ema"])
             else:                                  # a state written without the EMA: the next qualifying G-step starts it with a copy
                 self.ema.ready, self.ema.updates = False, 0
+        if self.pool_BA is not None:
+            if "image_pool" in st:
+                self.pool_BA.load_state_dict(st["image_pool"]["BA"])
+                self.pool_AB.load_state_dict(st["image_pool"]["AB"])
+            else:                                  # a state written without the pool: it fills again from the next D-step on
+                self.pool_BA.clear()
+                self.pool_AB.clear()
+                print(f"image pool: the loaded training state holds no image_pool; both pools ({self.pool_BA.size} images per domain) "
+                      "start empty", flush=True)
         self._graphs = {}
         start = int(st["iters"])
         # like a fresh run, the first D,G,G cycle after a resume is dispatched eagerly before anything is captured

@@ -461,6 +461,36 @@ int dg_augment_draw(uint64_t seed, int rank, int64_t iteration, int domain, int 
 int dg_image_prep_aug(const uint8_t* src, float* dst, int N, int H, int W, int x0, int cw, int erode, int mode, int S, int L,
                       const int32_t* recs, const int32_t* rec_index /* or NULL */, dg_stream_t s);
 int dg_augment_f32(const float* src, float* dst, int N, int S, int L, const int32_t* recs, dg_stream_t s);
+/* ---- image history pool of the discriminators (Shrivastava et al. 2017; CycleGAN's ImagePool.query) ----------------------
+ * A pool is a buffer of P image slots of `elems` floats for one domain, `filled` of them in use (0 <= filled <= P).  A batch x[0..n) is
+ * processed IN ORDER; sample j does one of three things:
+ *   insert (filled + j < P):  pool[filled + j] = x[j], out[j] = x[j];
+ *   otherwise one bit and one slot s uniform in [0, P) are drawn --
+ *   swap (bit set):  out[j] = pool[s], then pool[s] = x[j];        pass (bit clear):  out[j] = x[j];
+ * afterwards filled = min(P, filled + n).  A later sample of the batch that draws a slot an earlier sample i touched receives x[i].
+ *
+ * The draw is a pure function of (seed, rank, iteration, domain 0 = A | 1 = B, j): the key chain of dg_augment_draw (mix, G as above) with
+ * one more link, so that a pool draw never coincides with an augmentation draw of the same (seed, rank, iteration, domain):
+ *   k = mix(seed + G); k = mix(k ^ (uint64(uint32(rank)) << 32 | uint32(domain))); k = mix(k ^ uint64(iteration)); k = mix(k ^ 0x706F6F6C);
+ *   a = mix(k + G (j + 1));  swap = a >> 63;  s = (uint64(low 32 bits of a) P) >> 32.
+ *
+ * dg_pool_draw resolves the in-order semantics of one batch into a record table, device int32 [n][4] = (src, slot, st_src, 0), 16-byte
+ * aligned, which one parallel launch can apply without a read / write race on a slot:
+ *   out[j] = pool_before[slot] if src == -1, else x[src];
+ *   if slot >= 0: pool[slot] = x[st_src], written by the thread(s) of sample j, after their read of that slot where they read it.
+ * With "touch" = insert or swap, prev(j) = the largest i < j touching j's slot (-1: none) and last(j) = the largest i >= j touching it:
+ *   pass (j, -1, j, 0);  insert (j, s, last, 0);  swap with prev < 0 (-1, s, last, 0);  swap with prev >= 0 (prev, -1, j, 0).
+ * So only the first toucher of a slot carries its store, the stored image is the last toucher's, and no slot is read by one record and
+ * written by another.  Rows past n are left untouched.  1 <= n <= 4096 (every thread scans the batch), P >= 1, 0 <= filled <= P.
+ *
+ * dg_pool_exchange applies a table in ONE launch: x, out [n][elems] and pool [P][elems] floats (elems = 3 S S), pairwise disjoint.  A copy:
+ * every bit pattern (NaN payloads, denormals) survives; 16 bytes per lane where the three bases are 16-byte aligned and elems % 4 == 0,
+ * else 4.  The record VALUES need no trust: a record with a field out of range (src outside [-1, n), slot outside [-1, P), st_src outside
+ * [0, n), or src == -1 without a slot) is applied as the pass record (j, -1, j, 0).  A hand-made table that names one slot twice is
+ * memory-safe, but which writer wins is unspecified.  The caller advances `filled`. */
+int dg_pool_draw(uint64_t seed, int rank, int64_t iteration, int domain, int n, int P, int filled,
+                 int32_t* recs /* device [n][4]: src, slot, st_src, 0 */, dg_stream_t s);
+int dg_pool_exchange(const float* x, float* pool, float* out, int n, int P, size_t elems, const int32_t* recs, dg_stream_t s);
 /* ---- sample grids (image_translation.py:170-209): the inverse of the ingest, tiled -------------------------
    src: HOST table of `cols` device pointers, each a float batch [n_c][3][S][S] (NCHW, n_c >= rows).
    canvas: device uint8 [Hc][Wc][3], Hc = rows*(S+gap)+gap, Wc = cols*(S+gap)+gap.
