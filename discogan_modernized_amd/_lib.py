@@ -104,15 +104,13 @@ SIGNATURES = {
     "dg_device_cu_count": (_i, []),
     "dg_loss_mix_fwd": (_i, [_p, _p, _i, _f, _i, _p]),
     "dg_loss_mix_bwd": (_i, [_p, _p, _i, _f, _i, _i, _p]),
-    "dg_adam_advance": (_i, [_p, _d, _d, _d, _p]),
-    "dg_adam_step_flat": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p]),
+    "dg_adam_advance": (_i, [_p, _d, _d, _d, _p, _p]),
+    "dg_adam_step_flat": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _p, _i, _z, _p]),
     "dg_ema_update_flat": (_i, [_p, _p, _z, _f, _p]),
     "dg_swap_flat": (_i, [_p, _p, _z, _p]),
     "dg_grad_stats_workspace_bytes": (_z, []),
     "dg_grad_sumsq_partial": (_i, [_p, _z, _p, _z, _i, C.POINTER(_i), _p]),
     "dg_grad_clip_finalize": (_i, [_p, _i, _d, _d, _i, _p, _p]),
-    "dg_adam_advance_c": (_i, [_p, _d, _d, _d, _p, _p]),
-    "dg_adam_step_flat_c": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _p, _p, _i, _z, _p]),
     "dg_bce_target_fwd": (_i, [_p, _p, _i, _p, _p]),
     "dg_bce_target_bwd": (_i, [_p, _p, _i, _p, _p, _p]),
     "dg_hinge_fwd": (_i, [_p, _p, _z, _f, _p, _p, _z, _p]),
@@ -138,13 +136,11 @@ SIGNATURES = {
     "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
-    "dg_adam_step_flat_bf16": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _p]),
     "dg_f32_to_bf16": (_i, [_p, _p, _z, _p]),
     "dg_bn_act_fwd_bf16": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _p]),
     "dg_bn_act_bwd_bf16": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _p, _p, _i, _p, _z, _p]),
     "dg_conv_bf16_operands_ok": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "dg_f32_to_bf16x3": (_i, [_p, _p, _z, _z, _p]),
-    "dg_adam_step_flat_x3": (_i, [_p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _f, _p, _z, _p]),
     "dg_conv4x4s2_c3_fwd_x3": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _p]),
     "dg_conv_x3_planes_ok": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "dg_bn_act_fwd_x3": (_i, [_p, _p, _p, _z, _i, _i, _i, _p, _p, _p, _i, _f, _p]),

@@ -1809,7 +1809,7 @@ extern "C" int dg_conv_wgrad(const float* dy, const float* x, float* dw, int N, 
 
 // ---- bf16 shadow operands (option "bf16" = 1 only) -------------------------------------------------------------------
 // The same three ops with either operand given as a bf16 tensor of the same logical layout.  Producers write the shadow
-// next to the fp32 tensor (dg_adam_step_flat_bf16 for weights, dg_bn_act_fwd_bf16 / dg_bn_act_bwd_bf16 / the c3 forward for
+// next to the fp32 tensor (dg_adam_step_flat form 1 for weights, dg_bn_act_fwd_bf16 / dg_bn_act_bwd_bf16 / the c3 forward for
 // activations and gradients); the result is bit-identical to passing the fp32 tensors (same RNE rounding, same order).
 // The K == 1 head (the discriminator's 4x4 head, plain reductions) takes only the ACTIVATION side as bf16 (x of forward / weight-grad,
 // dx of input-grad); the [N] vector and the weights are fp32.
@@ -1850,7 +1850,7 @@ extern "C" int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, i
 // ---- fp32 operands as three bf16 planes (option "bf16" = 2 only): igemm_dma_x3.hip -----------------------------------------
 // a3 / b3 point at plane 0 (hi) of an operand; planes 1 (mid) and 2 (lo) follow a_plane / b_plane BYTES further on (>= the
 // tensor's 2 * numel; a weight inside a flat parameter group has the group's plane distance).  Written by dg_f32_to_bf16x3 or
-// by the fused producers (dg_adam_step_flat_x3, dg_bn_act_fwd_x3, dg_bn_act_bwd_x3); outputs are fp32.
+// by the fused producers (dg_adam_step_flat form 3, dg_bn_act_fwd_x3, dg_bn_act_bwd_x3); outputs are fp32.
 static int x3_plan_rules(const ConvCall& c, const Plan& pl) {
     const char* who = c.who;
     const bool rs_planes = pl.dma == 0 && x3_register_staged_planes_ok(c.op, pl);

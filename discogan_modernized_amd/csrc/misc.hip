@@ -15,7 +15,7 @@ int dg_fail(int code, const char* fmt, ...) {
 }
 int dg_get_option(int idx) { return (idx >= 0 && idx < DG_OPT_COUNT) ? g_options[idx] : 0; }
 
-extern "C" int dg_version(void) { return 100; }
+extern "C" int dg_version(void) { return 101; }
 // bit 0: the experiments build (kernels that lost their A/B: window forward kernel, register-staged plane reader, persistent window
 // input-grad, paired-plane 16x16x32 body); bit 1: the timing build (operand-dropping switch).  The product library returns 0.
 extern "C" int dg_build_flags(void) {

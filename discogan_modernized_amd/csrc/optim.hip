@@ -131,49 +131,44 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
                     (long)gridDim.x);
 }
 
-extern "C" int dg_adam_advance(double* state, double lr, double beta1, double beta2, dg_stream_t stream) {
+static inline int flat_grid(size_t n) {
+    size_t grid = (n / 4 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    return (int)grid;
+}
+// ctl == nullptr: an unconditional advance; otherwise state is left untouched when ctl[3] != 0
+extern "C" int dg_adam_advance(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t stream) {
     DG_CHECK_ARG(state, "dg_adam_advance: null state");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2, (const double*)nullptr);
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2, ctl);
     DG_CHECK_LAUNCH("adam_advance");
     return DG_OK;
 }
-extern "C" int dg_adam_step_flat(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1,
-                                 float beta2, float eps, float weight_decay, float grad_scale, dg_stream_t stream) {
+// The one flat step.  ctl == nullptr: the host's grad_scale; otherwise the gradient scale (float)ctl[2] and the skip flag ctl[3] are
+// read on the device and grad_scale is ignored.
+// form 0: out unused; 1: out = the bf16 shadow; 3: out = plane 0 of the range (hi / mid / lo planes plane_elems elements apart).
+extern "C" int dg_adam_step_flat(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1, float beta2,
+                                 float eps, float weight_decay, float grad_scale, const double* ctl, void* out, int form,
+                                 size_t plane_elems, dg_stream_t stream) {
     DG_CHECK_ARG(p && g && m && v && state, "dg_adam_step_flat: null pointer");
+    DG_CHECK_ARG(form == 0 || form == 1 || form == 3, "dg_adam_step_flat: form %d (0 plain, 1 bf16 shadow, 3 planes)", form);
+    DG_CHECK_ARG(form == 0 || out, "dg_adam_step_flat: form %d without an output", form);
+    DG_CHECK_ARG(form != 3 || (plane_elems >= n && plane_elems % 8 == 0), "dg_adam_step_flat: plane distance %zu for %zu parameters",
+                 plane_elems, n);
     if (n == 0) return DG_OK;
-    long grid = ((long)(n / 4) + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adam_step_kernel<0>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)nullptr, 0L, (const double*)nullptr);
+    const dim3 grid(flat_grid(n)), block(256);
+    const hipStream_t s = (hipStream_t)stream;
+    const float gscale = ctl ? 1.f : grad_scale;
+    if (form == 0)
+        hipLaunchKernelGGL(adam_step_kernel<0>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, gscale,
+                           (__bf16*)nullptr, 0L, ctl);
+    else if (form == 1)
+        hipLaunchKernelGGL(adam_step_kernel<1>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, gscale,
+                           (__bf16*)out, 0L, ctl);
+    else
+        hipLaunchKernelGGL(adam_step_kernel<3>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, gscale,
+                           (__bf16*)out, (long)plane_elems, ctl);
     DG_CHECK_LAUNCH("adam_step");
-    return DG_OK;
-}
-extern "C" int dg_adam_step_flat_bf16(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1,
-                                      float beta2, float eps, float weight_decay, float grad_scale, void* p16, dg_stream_t stream) {
-    DG_CHECK_ARG(p && g && m && v && state && p16, "dg_adam_step_flat_bf16: null pointer");
-    if (n == 0) return DG_OK;
-    long grid = ((long)(n / 4) + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adam_step_kernel<1>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p16, 0L, (const double*)nullptr);
-    DG_CHECK_LAUNCH("adam_step_bf16");
-    return DG_OK;
-}
-// the same step, also writing the parameters' three bf16 planes (hi / mid / lo, plane_elems elements apart; plane_elems >= n, % 8 == 0)
-extern "C" int dg_adam_step_flat_x3(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1,
-                                    float beta2, float eps, float weight_decay, float grad_scale, void* p3, size_t plane_elems,
-                                    dg_stream_t stream) {
-    DG_CHECK_ARG(p && g && m && v && state && p3, "dg_adam_step_flat_x3: null pointer");
-    DG_CHECK_ARG(plane_elems >= n && plane_elems % 8 == 0, "dg_adam_step_flat_x3: plane distance %zu for %zu parameters", plane_elems, n);
-    if (n == 0) return DG_OK;
-    long grid = ((long)(n / 4) + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adam_step_kernel<3>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, state,
-                       beta1, beta2, eps, weight_decay, grad_scale, (__bf16*)p3, (long)plane_elems, (const double*)nullptr);
-    DG_CHECK_LAUNCH("adam_step_x3");
     return DG_OK;
 }
 // fp32 -> bf16 (RNE) copy: initial weight shadow / shadows of tensors that have no fused producer
@@ -265,12 +260,6 @@ __global__ __launch_bounds__(256) void swap_flat_kernel(unsigned int* __restrict
             a[e] = b[e];
             b[e] = x;
         }
-}
-static inline int flat_grid(size_t n) {
-    size_t grid = (n / 4 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    return (int)grid;
 }
 extern "C" int dg_ema_update_flat(float* ema, const float* p, size_t n, float w, dg_stream_t stream) {
     DG_CHECK_ARG(ema && p, "dg_ema_update_flat: null pointer");
@@ -395,40 +384,9 @@ extern "C" int dg_grad_clip_finalize(const double* ws, int slots, double pre_sca
     DG_CHECK_LAUNCH("grad_clip_finalize");
     return DG_OK;
 }
-extern "C" int dg_adam_advance_c(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t stream) {
-    DG_CHECK_ARG(state && ctl, "dg_adam_advance_c: null pointer");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2, ctl);
-    DG_CHECK_LAUNCH("adam_advance_c");
-    return DG_OK;
-}
-// dg_adam_step_flat / _bf16 / _x3 with the gradient scale (float)ctl[2] and the skip flag ctl[3] read on the device.
-// form 0: out unused; 1: out = the bf16 shadow; 3: out = plane 0 of the range, planes plane_elems elements apart.
-extern "C" int dg_adam_step_flat_c(float* p, const float* g, float* m, float* v, size_t n, const double* state, float beta1, float beta2,
-                                   float eps, float weight_decay, const double* ctl, void* out, int form, size_t plane_elems,
-                                   dg_stream_t stream) {
-    DG_CHECK_ARG(p && g && m && v && state && ctl, "dg_adam_step_flat_c: null pointer");
-    DG_CHECK_ARG(form == 0 || form == 1 || form == 3, "dg_adam_step_flat_c: form %d (0 plain, 1 bf16 shadow, 3 planes)", form);
-    DG_CHECK_ARG(form == 0 || out, "dg_adam_step_flat_c: form %d without an output", form);
-    DG_CHECK_ARG(form != 3 || (plane_elems >= n && plane_elems % 8 == 0), "dg_adam_step_flat_c: plane distance %zu for %zu parameters",
-                 plane_elems, n);
-    if (n == 0) return DG_OK;
-    const dim3 grid(flat_grid(n)), block(256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (form == 0)
-        hipLaunchKernelGGL(adam_step_kernel<0>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
-                           (__bf16*)nullptr, 0L, ctl);
-    else if (form == 1)
-        hipLaunchKernelGGL(adam_step_kernel<1>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
-                           (__bf16*)out, 0L, ctl);
-    else
-        hipLaunchKernelGGL(adam_step_kernel<3>, grid, block, 0, s, p, g, m, v, (long)n, state, beta1, beta2, eps, weight_decay, 1.f,
-                           (__bf16*)out, (long)plane_elems, ctl);
-    DG_CHECK_LAUNCH("adam_step_c");
-    return DG_OK;
-}
 
 // ---- the f32x3 step of a WHOLE group, transposed weight planes included (optim.Adam.step, active is None) -----------------------------
-// dg_adam_step_flat_x3 followed by dg_x3_transpose_planes reads back, microseconds later, the 6 B/param of planes the step wrote and
+// dg_adam_step_flat (form 3) followed by dg_x3_transpose_planes reads back, microseconds later, the 6 B/param of planes the step wrote and
 // writes them again transposed (12 B/param on top of the step's 34).  Here the step of a conv weight keeps its plane values in LDS and
 // writes the transposed copy itself: 40 B/param, one pass.  One workgroup owns a 64 x TJ tile of a [K][J] weight image (J = 16 C;
 // K % 64 == 0 and J % TJ == 0: no ragged tile, no scalar path).  Thread (lk, lv) updates the 8-parameter runs lv and lv + TJ / 16 of
@@ -547,7 +505,7 @@ __global__ __launch_bounds__(256) void adam_step_ranges_x3_kernel(float* __restr
 
 // One f32x3 Adam step of a flat group of `numel` parameters as n_w tiled conv weights ([K][J] images at element offsets w_off: they
 // also get their transposed planes in pt_planes) and n_r plain ranges [r_off, r_off + r_len) (plain planes only).  ctl == nullptr: the
-// host's grad_scale; otherwise scale and go / no-go from the control block, as dg_adam_step_flat_c.  What neither list covers is left
+// host's grad_scale; otherwise scale and go / no-go from the control block, as dg_adam_step_flat.  What neither list covers is left
 // untouched.  Host arrays, each list ascending and disjoint in itself, and the two lists disjoint from each other (a weight that
 // overlaps a range is refused: its elements would be stepped twice); r_len[i] == 0 is accepted and covers nothing.
 extern "C" int dg_adam_step_group_x3(float* p, const float* g, float* m, float* v, size_t numel, const double* state, float beta1,

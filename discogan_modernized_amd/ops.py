@@ -1278,37 +1278,22 @@ def adam_advance(state, lr, beta1, beta2, ctl=None):
     """ctl: the step's control block (grad_clip_finalize); a skipped step (ctl[3] != 0) leaves the state untouched."""
     if ctl is not None:
         _check_ctl(ctl, "adam_advance")
-        _lib.check(_lib.load().dg_adam_advance_c(_ptr(state), lr, beta1, beta2, _ptr(ctl), _stream()), "dg_adam_advance_c")
-        return
-    _lib.check(_lib.load().dg_adam_advance(_ptr(state), lr, beta1, beta2, _stream()), "dg_adam_advance")
+    _lib.check(_lib.load().dg_adam_advance(_ptr(state), lr, beta1, beta2, _ptr(ctl), _stream()), "dg_adam_advance")
 
 
 def adam_step_flat(p, g, m, v, state, beta1, beta2, eps, weight_decay, grad_scale=1.0, p16=None, p3=None, ctl=None):
-    if ctl is not None:     # the gradient scale (float32(ctl[2])) and the skip flag (ctl[3]) are read on the device; grad_scale is unused
+    """p3: (plane-0 address of this range, plane distance in elements), the f32x3 plane triples; p16: the bf16 shadow.  ctl: the gradient
+    scale (float32(ctl[2])) and the skip flag (ctl[3]) are read on the device; grad_scale is then unused."""
+    if ctl is not None:
         _check_ctl(ctl, "adam_step_flat")
-        form, out, dist = (3, p3[0], p3[1]) if p3 is not None else ((1, _ptr(p16), 0) if p16 is not None else (0, None, 0))
-        with _hbm("adam", (28.0 + 2.0 * form) * p.numel()):
-            _lib.check(_lib.load().dg_adam_step_flat_c(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2, eps,
-                                                       weight_decay, _ptr(ctl), out, form, dist, _stream()), "dg_adam_step_flat_c")
-        return
-    if p3 is not None:      # (plane-0 address of this range, plane distance in elements): the f32x3 plane triples
-        with _hbm("adam", 34.0 * p.numel()):
-            _lib.check(_lib.load().dg_adam_step_flat_x3(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2,
-                                                        eps, weight_decay, grad_scale, p3[0], p3[1], _stream()), "dg_adam_step_flat_x3")
-        return
-    if p16 is not None:
-        with _hbm("adam", 30.0 * p.numel()):
-            _lib.check(_lib.load().dg_adam_step_flat_bf16(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2,
-                                                          eps, weight_decay, grad_scale, _ptr(p16), _stream()), "dg_adam_step_flat_bf16")
-        return
-    with _hbm("adam", 28.0 * p.numel()):
-        _lib.check(_lib.load().dg_adam_step_flat(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1,
-                                                 beta2,
-                                                 eps, weight_decay, grad_scale, _stream()), "dg_adam_step_flat")
+    form, out, dist = (3, p3[0], p3[1]) if p3 is not None else ((1, _ptr(p16), 0) if p16 is not None else (0, None, 0))
+    with _hbm("adam", (28.0 + 2.0 * form) * p.numel()):
+        _lib.check(_lib.load().dg_adam_step_flat(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(state), beta1, beta2, eps,
+                                                 weight_decay, grad_scale, _ptr(ctl), out, form, dist, _stream()), "dg_adam_step_flat")
 
 
 # ADAM_FUSED_T: the f32x3 step of a whole group (optim.Adam.step, active is None) writes the transposed weight planes itself
-# (dg_adam_step_group_x3: 40 B/param of a conv weight) instead of dg_adam_step_flat_x3 followed by dg_x3_transpose_planes, which reads
+# (dg_adam_step_group_x3: 40 B/param of a conv weight) instead of dg_adam_step_flat (form 3) followed by dg_x3_transpose_planes, which reads
 # the planes back (34 + 12 B/param).  Bit-identical; DG_ADAM_FUSED_T=0 restores the two-kernel form (A/B timing).
 ADAM_FUSED_T = _env_flag("DG_ADAM_FUSED_T", True)
 # LAZY_ZERO_GRAD: the trainer's iteration does not zero-fill the stepped flat gradient buffer (optim.Adam.zero_grad(lazy=True)); the

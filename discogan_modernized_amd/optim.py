@@ -69,7 +69,7 @@ class Adam:
             if p.dtype != torch.float32 or p.device != dev:
                 raise RuntimeError("all parameters must be fp32 on one device")
             offs.append(total)
-            total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            total += _padded(p.numel())
         self.numel = total
         self.flat_p = torch.zeros(total, device=dev)
         self.flat_g = torch.zeros(total, device=dev)
@@ -185,10 +185,9 @@ class Adam:
         if not self._unwritten:
             return
         runs = []
-        for p, off in zip(self.params, self.offsets):
+        for p, off, end in self.extents():
             if not getattr(p, "_dg_grad_unwritten", False):
                 continue
-            end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
             if ranges is not None and not any(b <= off and end <= e for b, e in ranges):
                 continue
             p._dg_grad_unwritten = False
@@ -213,13 +212,17 @@ class Adam:
                 p.grad = p._dg_flat_grad
                 p._dg_grad_unwritten = False
 
+    def extents(self):
+        """(parameter, begin, end) of every parameter in the flat buffers, the padding behind it included."""
+        for p, off in zip(self.params, self.offsets):
+            yield p, off, off + _padded(p.numel())
+
     def ranges_of(self, modules):
         """Flat [begin, end) ranges covering the parameters of the given modules (merged when adjacent)."""
         ids = {id(p) for m in modules for p in m.parameters()}
         out = []
-        for p, off in zip(self.params, self.offsets):
+        for p, off, end in self.extents():
             if id(p) in ids:
-                end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
                 if out and out[-1][1] == off:
                     out[-1][1] = end
                 else:
@@ -232,7 +235,6 @@ class Adam:
         torch.optim.Adam, parameters whose ``.grad`` would be None (a network outside the loss of the
         ``recongan`` / ``gan`` architectures, image_translation.py:377-382) are left untouched: no weight
         decay, no moment update.  None = the whole group."""
-        g = self.param_groups[0]
         self._sync_foreign_grads()
         self.fill_unwritten_grads()
         ranges = active if active is not None else [(0, self.numel)]
@@ -245,24 +247,53 @@ class Adam:
             for b, e in ranges:
                 slots += ops.grad_sumsq_partial(self.flat_g[b:e], self._stats_ws, slots)
             ops.grad_clip_finalize(self._stats_ws, slots, float(grad_scale), self.max_norm, self.guard, ctl)
-        ops.adam_advance(self.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), ctl=ctl)
-        p16 = getattr(self, "flat_p16", None)
+        self._advance(ctl)
         p3 = getattr(self, "flat_p3", None)
         if p3 is not None and active is None and ops.ADAM_FUSED_T:
             # the whole group on the f32x3 planes: one pass that also leaves the transposed weight planes (no transpose pass behind it)
+            g = self.param_groups[0]
             ops.adam_step_group_x3(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.state, float(g["betas"][0]),
                                    float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_scale), p3,
                                    self.flat_p3t, self._adam_group_table, ctl=ctl)
             if self._x3t_rest_table[0]:
                 ops.x3_transpose_planes(p3, self.flat_p3t, self._x3t_rest_table)
             return
+        self.step_ranges(ranges, grad_scale, ctl)
+        self.finish_step()
+
+    def _advance(self, ctl):
+        g = self.param_groups[0]
+        ops.adam_advance(self.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), ctl=ctl)
+
+    # A step issued in slices (an exchange that overlaps the backward pass): begin_step(), step_ranges() per slice as its gradients
+    # arrive, in any order and on any stream ordered behind begin_step(), then finish_step() behind every slice.
+    @torch.no_grad()
+    def begin_step(self):
+        """Advance the step count and the bias corrections once, ahead of the slices.  Not under gradient control: the global norm
+        needs the whole gradient before the first slice is stepped."""
+        if self.ctl is not None:
+            raise RuntimeError("begin_step(): a step issued in slices cannot be norm-controlled (enable_grad_control is on); use step()")
+        self._sync_foreign_grads()
+        self._advance(None)
+
+    @torch.no_grad()
+    def step_ranges(self, ranges, grad_scale: float = 1.0, ctl=None):
+        """The update of the flat ``ranges`` [(begin, end), ...] with every derived form the group keeps (bf16 shadow, f32x3 planes):
+        one launch per range.  Fills no unwritten gradient: whoever exchanges the gradients does that first (fill_unwritten_grads)."""
+        g = self.param_groups[0]
+        b1, b2, eps, wd = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"])
+        p16 = getattr(self, "flat_p16", None)
+        p3 = getattr(self, "flat_p3", None)
         for b, e in ranges:
-            ops.adam_step_flat(self.flat_p[b:e], self.flat_g[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], self.state,
-                               float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+            ops.adam_step_flat(self.flat_p[b:e], self.flat_g[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], self.state, b1, b2, eps, wd,
                                float(grad_scale), p16=None if p16 is None else p16[b:e],
                                p3=None if p3 is None else (p3.data_ptr() + 2 * b, self.numel), ctl=ctl)
-        if p3 is not None and self.flat_p3t is not None:
-            ops.x3_transpose_planes(p3, self.flat_p3t, self._x3t_table)
+
+    @torch.no_grad()
+    def finish_step(self):
+        """Behind every slice of the step: the transposed copy of the conv weights' planes, where the group keeps one."""
+        if getattr(self, "flat_p3t", None) is not None:
+            ops.x3_transpose_planes(self.flat_p3, self.flat_p3t, self._x3t_table)
 
     def state_dict(self):
         sd = dict(step=self.state[0:1].clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),

@@ -568,7 +568,7 @@ class DiscoGANTrainer:
             ev.record(main)
             self.comm_stream.wait_event(ev)
             with torch.cuda.stream(self.comm_stream):
-                self._adam_begin(opt)
+                opt.begin_step()
                 self._exchange_and_step_ranges(opt, self._gen_ranges()[1], "G")
             self._dec_done = True
         else:
@@ -582,30 +582,12 @@ class DiscoGANTrainer:
             self._gen_rng = (enc, dec)
         return self._gen_rng
 
-    def _adam_begin(self, opt):
-        g = opt.param_groups[0]
-        opt._sync_foreign_grads()
-        from . import ops
-        ops.adam_advance(opt.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]))
-
     def _exchange_and_step_ranges(self, opt, ranges, kind):
-        """all-reduce(sum) + Adam of flat ranges on the current stream (the step state was advanced by _adam_begin)."""
-        from . import ops
-        g = opt.param_groups[0]
+        """all-reduce(sum) + Adam of flat ranges on the current stream (the step state was advanced by opt.begin_step())."""
         opt.fill_unwritten_grads(ranges)                  # (networks outside the loss: nothing wrote their gradients)
         for b, e in ranges:
-            scale = 1.0
-            if self.xg is not None:
-                if self.time_comm:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    scale = self.xg.all_reduce_sum_(opt.flat_g[b:e])
-                    e1.record()
-                    self.comm_events[kind].append((e0, e1))
-                else:
-                    scale = self.xg.all_reduce_sum_(opt.flat_g[b:e])
-            ops.adam_step_flat(opt.flat_p[b:e], opt.flat_g[b:e], opt.exp_avg[b:e], opt.exp_avg_sq[b:e], opt.state,
-                               float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(scale))
+            opt.step_ranges([(b, e)], self._all_reduce(opt.flat_g[b:e], kind))
+        opt.finish_step()
 
     def _fwd_bwd(self, A, B, iters, need_losses=True):
         dstep = self.is_dis_step(iters)
@@ -688,19 +670,26 @@ class DiscoGANTrainer:
         ent[0].replay()
         return ent[1]
 
+    def _all_reduce(self, flat_slice, kind):
+        """All-reduce (sum) of a slice of a flat gradient buffer on the current stream, between two timing events under time_comm;
+        returns the 1/W scale (1.0 on one device, where nothing is exchanged)."""
+        if self.xg is None:
+            return 1.0
+        if not self.time_comm:
+            return self.xg.all_reduce_sum_(flat_slice)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        scale = self.xg.all_reduce_sum_(flat_slice)
+        e1.record()
+        self.comm_events[kind].append((e0, e1))
+        return scale
+
     def _exchange(self, opt, kind):
         """All-reduce (sum) of the stepped side's flat gradient buffer on the current stream; returns the 1/W scale."""
         if self.xg is None:
             return 1.0
         opt.fill_unwritten_grads()
-        if self.time_comm:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            scale = self.xg.all_reduce_sum_(opt.flat_g)
-            e1.record()
-            self.comm_events[kind].append((e0, e1))
-            return scale
-        return self.xg.all_reduce_sum_(opt.flat_g)
+        return self._all_reduce(opt.flat_g, kind)
 
     def _pool_draw(self, A, B, iters):
         """With a history pool, ahead of a D-step's dispatch and outside any capture: the record tables of this iteration's two
@@ -1029,10 +1018,9 @@ class _GradBuckets:
         for net in (trainer.generator_A, trainer.generator_B):
             ids = {id(p) for p in net.parameters()}
             cur = None
-            for p, off in zip(opt.params, opt.offsets):
+            for p, off, end in opt.extents():
                 if id(p) not in ids:
                     continue
-                end = off + (p.numel() + optim._ALIGN - 1) // optim._ALIGN * optim._ALIGN
                 if cur is None or cur["end"] - cur["begin"] >= target:
                     cur = dict(begin=off, end=end, nparams=0, pending=0, done=False)
                     self.buckets.append(cur)
@@ -1057,10 +1045,7 @@ class _GradBuckets:
         # the step counter / bias corrections advance once, on the communication stream, behind everything queued
         tr.comm_stream.wait_stream(main)
         with torch.cuda.stream(tr.comm_stream):
-            g = opt.param_groups[0]
-            opt._sync_foreign_grads()
-            from . import ops
-            ops.adam_advance(opt.state, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]))
+            opt.begin_step()
         F_.FINAL_HOOK = self.notify
 
     def notify(self, param):
@@ -1082,26 +1067,9 @@ class _GradBuckets:
         ev.record(producer_stream)
         tr.comm_stream.wait_event(ev)
         with torch.cuda.stream(tr.comm_stream):
-            sl = slice(b["begin"], b["end"])
-            scale = 1.0
-            if tr.xg is not None:
-                if tr.time_comm:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    scale = tr.xg.all_reduce_sum_(opt.flat_g[sl])
-                    e1.record()
-                    tr.comm_events["G"].append((e0, e1))
-                else:
-                    scale = tr.xg.all_reduce_sum_(opt.flat_g[sl])
+            scale = tr._all_reduce(opt.flat_g[b["begin"]:b["end"]], "G")
             if active is None or any(lo <= b["begin"] and b["end"] <= hi for lo, hi in active):
-                g = opt.param_groups[0]
-                from . import ops
-                p16 = getattr(opt, "flat_p16", None)
-                p3 = getattr(opt, "flat_p3", None)          # f32x3 plane path: the slice's plane triples with the update
-                ops.adam_step_flat(opt.flat_p[sl], opt.flat_g[sl], opt.exp_avg[sl], opt.exp_avg_sq[sl], opt.state,
-                                   float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                                   float(scale), p16=None if p16 is None else p16[sl],
-                                   p3=None if p3 is None else (p3.data_ptr() + 2 * b["begin"], opt.numel))
+                opt.step_ranges([(b["begin"], b["end"])], scale)    # (with the slice's bf16 shadow / f32x3 plane triples)
         if early:
             self.launched += 1
 
@@ -1113,11 +1081,8 @@ class _GradBuckets:
         for b in self.buckets:
             if not b["done"]:
                 self._launch(b, main, early=False, active=self.active)
-        opt = tr.optim_gen
-        if getattr(opt, "flat_p3t", None) is not None:      # every bucket's planes are written: the transposed weight copy follows
-            from . import ops
-            with torch.cuda.stream(tr.comm_stream):
-                ops.x3_transpose_planes(opt.flat_p3, opt.flat_p3t, opt._x3t_table)
+        with torch.cuda.stream(tr.comm_stream):
+            self.opt.finish_step()                        # every bucket's planes are written: the transposed weight copy follows
         main.wait_stream(tr.comm_stream)
 
 

@@ -65,6 +65,8 @@ typedef void* dg_stream_t;
  * final reduction adds them in problem order, bitwise what consecutive accumulating calls leave. */
 #define DG_MAX_GROUPS 4
 
+/* 101: exported symbols were removed (dg_adam_advance_c, dg_adam_step_flat_c / _bf16 / _x3: dg_adam_advance and dg_adam_step_flat take
+ * their arguments), and those two changed their argument lists. */
 int dg_version(void);
 /* 0 = the product library.  bit 0: experiments build (csrc/Makefile EXPERIMENTS=1: kernels that lost their A/B, behind options "x3_mfma",
  * "dgw_persist" and the window-forward / plane-reader planner codes); bit 1: timing build (TIMING=1: option "dbg_zero"). */
@@ -350,12 +352,17 @@ int dg_loss_mix_bwd(const float* gout, float* gvec, int nfm, float rate, int arc
 
 /* ---- Adam over flat buffers (optim.Adam, image_translation.py:275-287) ------------------------
  * state (device, 4 x float64): [0] step count, [1] lr/(1-b1^t), [2] sqrt(1-b2^t), [3] spare.
- * dg_adam_advance increments the step and refreshes the scalars ON DEVICE (graph-capturable).
- */
-int dg_adam_advance(double* state, double lr, double beta1, double beta2, dg_stream_t s);
+ * dg_adam_advance increments the step and refreshes the scalars ON DEVICE (graph-capturable).  ctl: NULL, or the control block of
+ *   the gradient statistics below: state is left untouched when ctl[3] != 0.
+ * dg_adam_step_flat: the one step of a flat range.  form 0: p, m, v only (28 B/param), out unused; 1: out = the bf16 shadow of p
+ *   (+2 B/param); 3: out = plane 0 of the range's three bf16 planes, plane_elems elements apart (>= n, % 8 == 0; +6 B/param).
+ *   ctl == NULL: the host's grad_scale.  Otherwise grad_scale is ignored and the scale is (float)ctl[2]; when ctl[3] != 0 every thread
+ *   returns before its first load: p, m, v, the shadow and the planes keep their bits.  A step that is taken is bitwise the
+ *   host-scaled call with grad_scale = (float)ctl[2].  n == 0 launches nothing. */
+int dg_adam_advance(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t s);
 int dg_adam_step_flat(float* p, const float* g, float* m, float* v, size_t n, const double* state,
                       float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                      dg_stream_t s);
+                      const double* ctl, void* out, int form, size_t plane_elems, dg_stream_t s);
 /* Exponential moving average of a flat parameter buffer: ema += (p - ema) * w, w = 1 - decay in [0, 1], the three operations
  * rounded one by one (p == ema leaves ema bitwise unchanged for every w).  dg_swap_flat exchanges the contents of two buffers
  * bit for bit; a == b is a no-op, ranges that overlap otherwise are refused.  Pointers 16-byte aligned; n == 0 launches nothing. */
@@ -363,8 +370,8 @@ int dg_ema_update_flat(float* ema, const float* p, size_t n, float w, dg_stream_
 int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t s);
 
 /* ---- Gradient norm, clipping by it and the non-finite guard of an Adam step (optim.Adam.enable_grad_control) --------------------
- * Everything stays on the device and on one stream: partials of every stepped flat range, one finalize, then the *_c forms of the Adam
- * entry points, which take their gradient scale and their go / no-go from the control block the finalize wrote.
+ * Everything stays on the device and on one stream: partials of every stepped flat range, one finalize, then the Adam entry points above
+ * with ctl, which take their gradient scale and their go / no-go from the control block the finalize wrote.
  *
  * dg_grad_sumsq_partial: sum of squares of g[0..n), every element widened to double BEFORE it is squared (an exact product, so a finite
  *   fp32 gradient can neither overflow nor underflow the sum: only inf / NaN elements make it non-finite).  Grid of at most 4096 blocks
@@ -378,18 +385,10 @@ int dg_swap_flat(float* a, float* b, size_t n, dg_stream_t s);
  *   pre_scale is the factor the step would have passed as grad_scale (data parallel: 1 / world size behind a SUM all-reduce, so norm
  *   is the norm of the averaged gradient).  max_norm <= 0: no clipping, scale = pre_scale.  The coefficient is
  *   torch.nn.utils.clip_grad_norm_'s; with error_if_nonfinite=False semantics when guard == 0: an infinite norm gives scale 0, a NaN
- *   norm a NaN scale, and the step is taken.  guard != 0: skip = !isfinite(sumsq).
- * dg_adam_advance_c: dg_adam_advance, but state is left untouched when ctl[3] != 0.
- * dg_adam_step_flat_c: dg_adam_step_flat (form 0) / _bf16 (form 1, out = the shadow) / _x3 (form 3, out = plane 0, plane_elems apart)
- *   with grad_scale = (float)ctl[2]; when ctl[3] != 0 every thread returns before its first load: p, m, v, the shadow and the planes
- *   keep their bits.  A step that is taken is bitwise the host-scaled entry point called with grad_scale = (float)ctl[2]. */
+ *   norm a NaN scale, and the step is taken.  guard != 0: skip = !isfinite(sumsq). */
 size_t dg_grad_stats_workspace_bytes(void);
 int dg_grad_sumsq_partial(const float* g, size_t n, double* ws, size_t ws_bytes, int slot0, int* slots_used, dg_stream_t s);
 int dg_grad_clip_finalize(const double* ws, int slots, double pre_scale, double max_norm, int guard, double* ctl, dg_stream_t s);
-int dg_adam_advance_c(double* state, double lr, double beta1, double beta2, const double* ctl, dg_stream_t s);
-int dg_adam_step_flat_c(float* p, const float* g, float* m, float* v, size_t n, const double* state,
-                        float beta1, float beta2, float eps, float weight_decay, const double* ctl,
-                        void* out, int form, size_t plane_elems, dg_stream_t s);
 
 /* nn.BCELoss against a target TENSOR (image_translation.py:157-166 materialises ones / zeros label tensors);
  * same -100 log clamp and 1e-12 backward guard as dg_bce_fwd/_bwd.  p, target: [n]. */
@@ -512,7 +511,7 @@ int dg_image_metrics(const float* x, const float* y, int n, int S, float* out /*
 
 /* ---- bf16 shadow operands for the bf16 matrix path (option "bf16" = 1; BASELINE configs[4]) ---------------------
  * A shadow is a bf16 (RNE) copy of an fp32 tensor with the same logical layout, written by the tensor's PRODUCER so that
- * the conv kernels read half the operand bytes and convert nothing: dg_adam_step_flat_bf16 (weights, +2 B/param),
+ * the conv kernels read half the operand bytes and convert nothing: dg_adam_step_flat form 1 (weights, +2 B/param),
  * dg_bn_act_fwd_bf16 / dg_bn_act_bwd_bf16 (activations / gradients: +2 B/element on passes of 8 / 12 B/element),
  * dg_f32_to_bf16 (initial weight shadow; the first layer's output).  The *_mixed convolutions take either operand as fp32 (flag 0) or bf16 (flag 1)
  * and return the fp32 convolution of the RNE-rounded operands (same summation order per output element whichever operand
@@ -522,9 +521,6 @@ int dg_image_metrics(const float* x, const float* y, int n, int S, float* out /*
  * 2 = the LDS-DMA kernel when both operands are bf16.  A bf16 operand is read in 16-byte granules of 8 elements, which must not
  * straddle a row of its GEMM operand: a bf16 dy (input gradient, weight gradient) needs K % 8 == 0, a bf16 x of the weight gradient
  * C % 8 == 0 -- otherwise that operand flag is refused (pass the fp32 tensor: the kernel rounds it itself, the same values). */
-int dg_adam_step_flat_bf16(float* p, const float* g, float* m, float* v, size_t n, const double* state,
-                           float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                           void* p_bf16, dg_stream_t s);
 int dg_f32_to_bf16(const float* x, void* y_bf16, size_t n, dg_stream_t s);
 int dg_bn_act_fwd_bf16(const float* y, float* z, void* z_bf16, int M, int C, const float* saved, const float* gamma,
                        const float* beta, int act, float slope, dg_stream_t stream);
@@ -547,8 +543,8 @@ int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, int x_bf16, 
  * A plane triple of an fp32 tensor v: hi = bf16(v) (RNE), mid = bf16(v - hi), lo = bf16(v - hi - mid) -- 24 significand
  * bits of v (both subtractions are exact in fp32).  Layout: plane-major, each plane in the tensor's own logical layout;
  * `*_plane` = distance between planes in BYTES (multiple of 16, >= 2 * numel; a weight inside a flat parameter group uses
- * the group's distance), dg_f32_to_bf16x3 / dg_adam_step_flat_x3 take it in ELEMENTS (multiple of 8).  Written by the
- * tensor's producer: dg_adam_step_flat_x3 (weights, +6 B/param), dg_bn_act_fwd_x3 / dg_bn_act_bwd_x3 (activations /
+ * the group's distance), dg_f32_to_bf16x3 / dg_adam_step_flat take it in ELEMENTS (multiple of 8).  Written by the
+ * tensor's producer: dg_adam_step_flat form 3 (weights, +6 B/param), dg_bn_act_fwd_x3 / dg_bn_act_bwd_x3 (activations /
  * gradients), dg_f32_to_bf16x3 (everything else).  The *_x3 convolutions return the fp32 convolution with the same six
  * bf16 MFMAs per product block and the same reduction order as the fp32-pointer entry points under option "bf16" = 2
  * (bit-identical on an unsplit GEMM), without the per-element split in the conv kernel: csrc/igemm_dma_x3.hip, operand
@@ -562,13 +558,10 @@ int dg_conv_wgrad_mixed(const void* dy, int dy_bf16, const void* x, int x_bf16, 
  * ([K][J] images, J = 16 C, at element offsets w_off inside each plane; host arrays, any order; the whole table is checked
  * before the first launch). */
 int dg_f32_to_bf16x3(const float* x, void* y_planes, size_t n, size_t plane_elems, dg_stream_t s);
-int dg_adam_step_flat_x3(float* p, const float* g, float* m, float* v, size_t n, const double* state,
-                         float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                         void* p_planes, size_t plane_elems, dg_stream_t s);
 int dg_x3_transpose_planes(const void* src_planes, void* dst_planes, size_t plane_elems, const int64_t* w_off, const int* w_K,
                            const int* w_J, int n, dg_stream_t s);
 /* One f32x3 Adam step of a whole flat group of `numel` parameters that also writes the transposed weight planes: the bits of
- * dg_adam_step_flat_x3 (ctl == NULL, the host's grad_scale) or dg_adam_step_flat_c form 3 (scale and go / no-go from ctl) followed by
+ * dg_adam_step_flat form 3 (ctl == NULL: the host's grad_scale; otherwise scale and go / no-go from ctl) followed by
  * dg_x3_transpose_planes, without reading the plain planes back (40 instead of 34 + 12 B/param).  The group is given as two host
  * lists, each ascending and disjoint in itself and the two disjoint from each other (an overlap is refused): n_w conv weights ([K][J] images at element offsets w_off; K % 64 == 0, J % 64 == 0,
  * w_off % 8 == 0), stepped by 64 x 128 tiles (64 x 64 where J % 128 != 0) that store p, m, v, the plain planes and the [J][K] planes in pt_planes; and n_r plain

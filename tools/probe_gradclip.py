@@ -55,7 +55,7 @@ def kernel_rates(n, say):
     say(f"(a) n = {n} floats ({n / 1e6:.1f} M), medians of 3 x 10 launches: dg_grad_sumsq_partial + dg_grad_clip_finalize {t_norm:.3f} ms = "
         f"{r_norm:.2f} TB/s (4 B/param); dg_ema_update_flat {t_ema:.3f} ms = {r_ema:.2f} TB/s (12 B/param); ratio of rates "
         f"{r_norm / r_ema:.2f} (target >= 0.90: {'met' if r_norm >= 0.9 * r_ema else 'MISSED'}); dg_adam_step_flat {t_adam:.3f} ms = "
-        f"{28 * n / t_adam / 1e9:.2f} TB/s, dg_adam_step_flat_c {t_adamc:.3f} ms = {28 * n / t_adamc / 1e9:.2f} TB/s (28 B/param)")
+        f"{28 * n / t_adam / 1e9:.2f} TB/s, dg_adam_step_flat with ctl {t_adamc:.3f} ms = {28 * n / t_adamc / 1e9:.2f} TB/s (28 B/param)")
 
 
 def step_times(size, batch, rounds, cycles, say):
