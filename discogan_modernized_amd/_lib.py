@@ -133,6 +133,12 @@ SIGNATURES = {
     "dg_augment_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "dg_pool_draw": (_i, [C.c_uint64, _i, _l, _i, _i, _i, _i, _p, _p]),
     "dg_pool_exchange": (_i, [_p, _p, _p, _i, _i, _z, _p, _p]),
+    "dg_diffaug_draw": (_i, [C.c_uint64, _i, _l, _i, _i, _i, _i, _i, _p, _p]),
+    "dg_diffaug_workspace_bytes": (_z, [_i, _i, _i]),
+    "dg_diffaug_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "dg_diffaug_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "dg_diffaug_fwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "dg_diffaug_bwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _z, _p]),
     "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),

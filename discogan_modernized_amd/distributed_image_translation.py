@@ -6,6 +6,9 @@ LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; the reference hard-code
 xGMI.  Every rank builds identical replicas from ``torch.manual_seed(1234)`` (:372), draws its own
 batch, keeps BatchNorm / feature-matching statistics rank-local, and the stepped side's flat gradient
 buffer is all-reduced (sum, then divided by W inside the Adam kernel).  Rank 0 logs and saves.
+
+``--diffaug POLICY`` (image_translation.py): every rank draws its own transforms of its own discriminator inputs, keyed on
+(seed, rank, iteration, domain, role) -- the replicas see different augmentations of different batches, and the gradients are summed as usual.
 """
 from __future__ import annotations
 

@@ -758,3 +758,43 @@ class FeatureMatchGroupFn(Function):
         need_f = any(ctx.needs_input_grad[1 + g + i] for i in range(g))
         dr, df = ops.fm_bwd_g(list(sv[:g]), list(sv[g:2 * g]), list(sv[2 * g:]), [go.contiguous() for go in gouts], need_r, need_f)
         return (None,) + tuple(dr or [None] * g) + tuple(df or [None] * g) + (None,) * g
+
+
+class DiffAugFn(Function):
+    """Differentiable augmentation of a batch [n,3,S,S] by a record table (diffaug.DiffAugment; include/discogan_hip.h): the op is affine
+    in x, so the backward needs the table and the flags only -- nothing of x is saved.  The table is read again at backward time: it
+    must still hold the forward's records (the trainer draws once per iteration, ahead of the forward)."""
+
+    @_fwd
+    def forward(ctx, x, recs, flags):
+        ctx.recs, ctx.flags = recs, int(flags)
+        ctx.set_materialize_grads(False)
+        return ops.diffaug_fwd(x.contiguous(), ctx.flags, recs)
+
+    @_bwd
+    def backward(ctx, dz):
+        if dz is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.diffaug_bwd(dz.contiguous(), ctx.flags, ctx.recs), None, None
+
+
+class DiffAugGroupFn(Function):
+    """DiffAugFn of ``g`` batches of one shape, each by its own table, in one launch per pass.  args: recs_0.., x_0.."""
+
+    @_fwd
+    def forward(ctx, g, flags, *t):
+        recs, xs = list(t[:g]), [x.contiguous() for x in t[g:2 * g]]
+        ctx.g, ctx.recs, ctx.flags = g, recs, int(flags)
+        ctx.set_materialize_grads(False)
+        return tuple(ops.diffaug_fwd_g(xs, ctx.flags, recs))
+
+    @_bwd
+    def backward(ctx, *dzs):
+        g = ctx.g
+        live = [i for i in range(g) if dzs[i] is not None and ctx.needs_input_grad[2 + g + i]]
+        out = [None] * g
+        if live:
+            dxs = ops.diffaug_bwd_g([dzs[i].contiguous() for i in live], ctx.flags, [ctx.recs[i] for i in live])
+            for i, d in zip(live, dxs):
+                out[i] = d
+        return (None,) * (2 + g) + tuple(out)

@@ -41,6 +41,12 @@ fakes: stored and passed on while the pool fills, afterwards swapped with a rand
 ``ImagePool``).  One fused launch per domain (dg_pool_exchange) on records drawn on the device from (seed, rank, iteration, domain), so graph
 replay and ``--resume`` reproduce the run bitwise; the pools travel in ``train_state_*.pth`` (key ``image_pool``).  A D-step's logged GEN / FM
 values are then computed on the pooled fakes; G-steps, reconstructions, sample grids and evaluation never see a pool.
+Differentiable augmentation: ``--diffaug color,translation,cutout`` (any subset; default "" = off) puts one random transform per sample in
+front of everything a discriminator reads -- reals and fakes, D-steps and G-steps, where the gradient flows back through it into the
+generator (Zhao et al. 2020, DiffAugment; on images in [0, 1]: brightness amplitude halved, padding and cutout fill 0.5).  HIP kernels
+(dg_diffaug_fwd / dg_diffaug_bwd) on records drawn on the device from (seed, rank, iteration, domain, role): graph replay and ``--resume``
+reproduce the run bitwise and nothing is saved.  It goes behind the pool exchange; generators, reconstructions, sample grids, evaluation
+and the EMA never see it.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -61,7 +67,7 @@ from pathlib import Path
 
 import torch
 
-from .trainer import DiscoGANTrainer, check_image_pool
+from .trainer import DiscoGANTrainer, check_diffaug, check_image_pool
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -122,6 +128,9 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--image_pool", type=int, default=0,
                    help="history pool of generated images per domain for the discriminator steps (CycleGAN's ImagePool; 50 is the customary "
                         "size; 0 = off): N * 3 * image_size^2 * 4 bytes of device memory per domain, keyed on (seed, rank, iteration)")
+    p.add_argument("--diffaug", type=str, default="",
+                   help="comma list of 'color', 'translation', 'cutout': differentiable augmentation (DiffAugment) of every discriminator "
+                        "input, reals and fakes, on the device, keyed on (seed, rank, iteration); empty or 'none' = off")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -329,6 +338,7 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
         raise ValueError(f"unknown task_name {args.task_name}; choose from {TASKS}")
     aug = augment_of(args, rank)                          # a mistyped --augment token or a scale below 1 raises before anything is built
     image_pool = check_image_pool(getattr(args, "image_pool", 0))           # likewise: a negative --image_pool
+    diffaug = check_diffaug(getattr(args, "diffaug", ""))                   # likewise: an unknown --diffaug policy
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
     if eval_interval > 0:
         from . import evaluate
@@ -359,6 +369,10 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
             print(f"image pool: {image_pool} images per domain ({image_pool * 3 * args.image_size ** 2 * 4 / 2 ** 20:.1f} MiB each) for the "
                   "discriminator steps; keyed on seed, rank and iteration; generator steps and reconstructions see the newest fakes",
                   flush=True)
+        if diffaug:
+            from .diffaug import policy_names
+            print(f"differentiable augmentation: {policy_names(diffaug)} on every discriminator input (reals and fakes, every step); "
+                  "keyed on seed, rank and iteration; generators, reconstructions, samples and evaluation never see it", flush=True)
     # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
     # saving rank alone loads it, samples and evaluates
     split = None

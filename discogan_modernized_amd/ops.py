@@ -299,6 +299,78 @@ def pool_exchange(x, pool, recs, out=None):
     return out
 
 
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # DG_DIFFAUG_* of include/discogan_hip.h
+DIFFAUG_MAX_BATCH = 4096       # samples per batch of the differentiable-augmentation kernels
+
+
+def check_diffaug_table(recs, n, who):
+    """A record table as the differentiable-augmentation kernels take it: int32 [m, 8] (tx, ty, cx0, cy0, bits(b), bits(s), bits(c), 0)
+    on the device, contiguous, m >= n."""
+    if not (recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.shape[1] == 8 and recs.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who} needs a contiguous int32 HIP record table of shape [n, 8]")
+    if recs.shape[0] < n:
+        raise _lib.DiscoganHipError(f"{who}: the record table has {recs.shape[0]} rows for {n} samples")
+
+
+def diffaug_draw(seed, rank, iteration, domain, role, n, S, flags, out=None, device="cuda"):
+    """The differentiable-augmentation records of one batch: int32 [n, 8] per position, drawn ON THE DEVICE as a pure function of
+    (seed, rank, iteration, domain 0 = A | 1 = B, role 0 = real | 1 = fake, position) -- dg_diffaug_draw; include/discogan_hip.h defines
+    the generator.  ``out``: a table of at least n rows to fill (rows from n on stay as they are)."""
+    if out is None:
+        out = torch.empty((n, 8), device=device, dtype=torch.int32)
+    check_diffaug_table(out, n, "diffaug_draw")
+    _lib.check(_lib.load().dg_diffaug_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank), int(iteration), int(domain), int(role), int(n), int(S),
+                                           int(flags), _ptr(out), _stream()), "dg_diffaug_draw")
+    return out[:n]
+
+
+def _diffaug_g(name, xs, flags, recs, outs):
+    """``len(xs)`` batches [n,3,S,S] of one shape through dg_diffaug_{fwd,bwd}[_g]: one launch per pass for all of them."""
+    g = len(xs)
+    _check_dev(*xs, *(outs or ()))
+    x0 = xs[0]
+    if x0.dim() != 4 or x0.shape[1] != 3 or x0.shape[2] != x0.shape[3]:
+        raise _lib.DiscoganHipError(f"{name} needs [n,3,S,S] batches, got {tuple(x0.shape)}")
+    if len(recs) != g or any(tuple(x.shape) != tuple(x0.shape) or not x.is_contiguous() for x in xs):
+        raise _lib.DiscoganHipError(f"{name}: one record table per batch, and contiguous batches of one shape, expected")
+    n, S = int(x0.shape[0]), int(x0.shape[3])
+    for r in recs:
+        check_diffaug_table(r, n, name)
+    if outs is None:
+        outs = [torch.empty_like(x) for x in xs]
+    elif len(outs) != g or any(tuple(o.shape) != tuple(x0.shape) or not o.is_contiguous() for o in outs):
+        raise _lib.DiscoganHipError(f"{name}: outputs must be contiguous and shaped like the inputs")
+    L = _lib.load()
+    wsl, wsb = _ws_g(L.dg_diffaug_workspace_bytes(n, S, int(flags)), g, x0.device)
+    with _hbm("diffaug", 8.0 * g * x0.numel()):
+        if g == 1:
+            _lib.check(getattr(L, name)(_ptr(xs[0]), _ptr(outs[0]), n, S, int(flags), _ptr(recs[0]), _ptr(wsl[0]), wsb, _stream()), name)
+        else:
+            _lib.check(getattr(L, name + "_g")(g, _tab(xs), _tab(outs), n, S, int(flags), _tab(recs), _tab(wsl), wsb, _stream()), name + "_g")
+    return outs
+
+
+def diffaug_fwd(x, flags, recs, out=None):
+    """The differentiable augmentation of a batch ``x`` [n,3,S,S] by a record table (dg_diffaug_fwd; include/discogan_hip.h defines the
+    transform): a new tensor like x unless ``out`` is given.  x is only read; x and out may not overlap."""
+    return _diffaug_g("dg_diffaug_fwd", [x], flags, [recs], None if out is None else [out])[0]
+
+
+def diffaug_bwd(dz, flags, recs, out=None):
+    """The adjoint of diffaug_fwd's linear part applied to ``dz`` [n,3,S,S] (dg_diffaug_bwd): the gradient of the input."""
+    return _diffaug_g("dg_diffaug_bwd", [dz], flags, [recs], None if out is None else [out])[0]
+
+
+def diffaug_fwd_g(xs, flags, recs, outs=None):
+    """diffaug_fwd of up to MAX_GROUPS batches of one shape, each by its own table, in one launch per pass; bitwise the single calls."""
+    return _diffaug_g("dg_diffaug_fwd", list(xs), flags, list(recs), outs)
+
+
+def diffaug_bwd_g(dzs, flags, recs, outs=None):
+    """diffaug_bwd of up to MAX_GROUPS gradients of one shape, each by its own table, in one launch per pass."""
+    return _diffaug_g("dg_diffaug_bwd", list(dzs), flags, list(recs), outs)
+
+
 def sample_grid(batches, rows, gap=2, bg=255):
     """1..8 float32 NCHW batches [n_c,3,S,S] (n_c >= rows) -> ONE uint8 canvas [rows*(S+gap)+gap, cols*(S+gap)+gap, 3] on the device:
     cell (r, c) = image r of batches[c], pixel = rint(clamp(x, 0, 1) * 255) (half to even, NaN -> 0), every other byte ``bg``

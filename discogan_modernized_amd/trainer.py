@@ -38,13 +38,15 @@ from . import losses as L
 from . import optim
 from .model import Discriminator, Generator
 from .pool import ImagePool
+from .diffaug import DiffAugment, apply_group, parse_policy
 
 LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A", "recon_loss_B",
             "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")
 
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
-                ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0)
+                ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
+                diffaug="")
 
 
 def check_ema_decay(decay):
@@ -71,6 +73,12 @@ def check_image_pool(size):
     return int(size)
 
 
+def check_diffaug(policy):
+    """``diffaug``: "" (or "none") = off, else a comma-separated subset of color, translation, cutout (diffaug.parse_policy).  Returns the
+    DG_DIFFAUG_* flags; raises ValueError on an unknown name."""
+    return parse_policy(policy)
+
+
 def format_grad_suffix(dis, gen):
     """The log suffix of gradient control from the two optimisers' ``grad_stats()``: each side's norm of its last step, then the
     counters of both sides together."""
@@ -82,7 +90,9 @@ class IterationOutputs(SimpleNamespace):
     """What ``forward_losses`` / ``train_iteration`` return: the loss scalars and the tensors of the iteration as attributes, plus
     ``BA_seen`` / ``AB_seen`` = the fake batches the discriminators were given -- ``BA`` / ``AB`` themselves unless a history pool
     exchanged them (``seen``: None, or ``dict(BA=, AB=)`` of a pooled D-step).  The two are properties, not attributes of their own:
-    whatever enumerates the returned tensors (``vars(out)``: bench.py --dump-outputs) finds the same set with and without the feature."""
+    whatever enumerates the returned tensors (``vars(out)``: bench.py --dump-outputs) finds the same set with and without the feature.
+    ``dis_inputs``: None, or with differentiable augmentation ``dict(A=, BA=, B=, AB=)`` = the augmented batches the discriminators read
+    (a dict for the same reason)."""
 
     @property
     def BA_seen(self):
@@ -160,7 +170,7 @@ class DiscoGANTrainer:
             self.optim_dis.enable_grad_control(grad_clip, guard)
         # History pool of generated images (image_pool = P > 0; pool.ImagePool): in a D-step -- and only there -- D_A is trained on
         # pool_BA.exchange(BA) and D_B on pool_AB.exchange(AB), a mix of this iteration's fakes and earlier ones, instead of BA / AB.  The
-        # two record tables are drawn on the device ahead of the iteration's dispatch, outside any capture (_pool_draw), keyed on
+        # two record tables are drawn on the device ahead of the iteration's dispatch, outside any capture (_draw_ahead), keyed on
         # (seed, data-parallel rank, iteration, domain): every rank pools its own fakes, and a resumed run continues the sequence.  Each
         # exchange is ONE launch on the stream of the discriminator pass that consumes it, reading only fixed device addresses, so it is
         # captured like any other kernel.  G-steps, the reconstruction passes and sampling never see a pool.
@@ -171,6 +181,19 @@ class DiscoGANTrainer:
             pseed = 0 if seed is None else seed
             self.pool_BA = ImagePool(P, image_size, pseed, rank, 0, device=self.device)      # domain A: the fakes D_A sees
             self.pool_AB = ImagePool(P, image_size, pseed, rank, 1, device=self.device)      # domain B: the fakes D_B sees
+        # Differentiable augmentation (diffaug = a policy; diffaug.DiffAugment): everything a discriminator reads -- reals and fakes, in
+        # D-steps and G-steps -- goes through one random transform per sample first, behind the pool exchange and on the consumer's
+        # stream; in a G-step the gradient flows back through it into the generator.  Four tables (A real, A fake, B real, B fake), drawn
+        # on the device ahead of EVERY iteration's dispatch, outside any capture (_draw_ahead), keyed on (seed, data-parallel rank,
+        # iteration, domain, role): nothing to checkpoint.  Generators, reconstruction passes, sampling, evaluation and the EMA never
+        # see the transform.
+        self.diffaug_flags = check_diffaug(getattr(self.args, "diffaug", ""))
+        self.aug_A = self.aug_BA = self.aug_B = self.aug_AB = None
+        if self.diffaug_flags:
+            rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+            dseed = 0 if seed is None else seed
+            mk = lambda domain, role: DiffAugment(self.diffaug_flags, image_size, dseed, rank, domain, role, device=self.device)  # noqa: E731
+            self.aug_A, self.aug_BA, self.aug_B, self.aug_AB = mk(0, 0), mk(0, 1), mk(1, 0), mk(1, 1)
         self._graphs = {}
         self._static = None
         # The A-side chain (G_A, D_A) runs on a second HIP stream next to the B-side chain (G_B, D_B):
@@ -360,7 +383,7 @@ class DiscoGANTrainer:
 
         want_recon = need_losses or not (dstep and skip)
         (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
-         seen) = self._two_chain_forward(A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side)
+         seen, dis_inputs) = self._two_chain_forward(A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side)
         assert nfm == len(A_feats_real)
         sl = [lv[i] for i in range(8 + 2 * nfm)]
         terms = {}
@@ -406,7 +429,7 @@ class DiscoGANTrainer:
             fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=recon_loss_A, recon_loss_B=recon_loss_B,
             dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
             A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
-            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv)
+            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, dis_inputs=dis_inputs)
 
     def _two_chain_forward(self, A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side):
         """The symmetric two-chain order: G_A(B) | G_B(A), G_A(AB) | G_B(BA), D_A(A) | D_B(B), D_A(BA) | D_B(AB), each pair in lock step.
@@ -452,8 +475,14 @@ class DiscoGANTrainer:
                 ABA, BAB = pair(self.generator_A.forward_steps(AB), self.generator_B.forward_steps(BA))
         else:
             lv[:2].fill_(float("nan"))
+        A_in, B_in, dis_inputs = A, B, None
+        if self.aug_A is not None:                           # the reals as the discriminators see them (no gradient is wanted of them)
+            with torch.no_grad():
+                with on_side():
+                    A_in = self.aug_A.apply(A)
+                B_in = self.aug_B.apply(B)
         (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = pair(
-            self.discriminator_A.forward_steps(A), self.discriminator_B.forward_steps(B))
+            self.discriminator_A.forward_steps(A_in), self.discriminator_B.forward_steps(B_in))
         # the fakes the discriminators see: in a D-step with a history pool the exchanged batches, each on its consumer's stream (BA was
         # produced on `side`, where D_A runs; AB on `main`, where D_B runs: no new join)
         BA_seen, AB_seen, seen = BA, AB, None
@@ -462,10 +491,16 @@ class DiscoGANTrainer:
                 BA_seen = self.pool_BA.exchange(BA)
             AB_seen = self.pool_AB.exchange(AB)
             seen = dict(BA=BA_seen, AB=AB_seen)
+        BA_in, AB_in = BA_seen, AB_seen
+        if self.aug_A is not None:                           # behind the exchange, each on its consumer's stream; differentiable
+            with on_side():
+                BA_in = self.aug_BA.apply(BA_seen)
+            AB_in = self.aug_AB.apply(AB_seen)
+            dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
         (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = pair(
-            self.discriminator_A.forward_steps(BA_seen), self.discriminator_B.forward_steps(AB_seen))
+            self.discriminator_A.forward_steps(BA_in), self.discriminator_B.forward_steps(AB_in))
         return (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
-                seen)
+                seen, dis_inputs)
 
     def _forward_losses_grouped(self, A, B, iters, need_losses=True):
         """image_translation.py:342-382 with every pair of passes as grouped launches (model.group_generators /
@@ -513,18 +548,29 @@ class DiscoGANTrainer:
         else:
             lv[:2].fill_(float("nan"))
             terms[0], terms[1] = sl[0], sl[1]
-        BA_seen, AB_seen, seen = BA, AB, None
+        BA_seen, AB_seen, seen, dis_inputs = BA, AB, None, None
+        aug = self.aug_A is not None
         with on_side():
             if dstep:
                 if self.pool_BA is not None:                 # the history pool: both exchanges on the discriminators' stream
                     BA_seen, AB_seen = self.pool_BA.exchange(BA), self.pool_AB.exchange(AB)
                     seen = dict(BA=BA_seen, AB=AB_seen)
+                A_in, BA_in, B_in, AB_in = A, BA_seen, B, AB_seen
+                if aug:                                      # the four inputs of the group of four: one launch per pass
+                    A_in, BA_in, B_in, AB_in = apply_group([self.aug_A, self.aug_BA, self.aug_B, self.aug_AB], [A, BA_seen, B, AB_seen])
                 (A_dis_real, A_feats_real), (A_dis_fake, A_feats_fake), (B_dis_real, B_feats_real), (B_dis_fake, B_feats_fake) = \
-                    group_discriminators([dA, dA, dB, dB], [A, BA_seen, B, AB_seen])
+                    group_discriminators([dA, dA, dB, dB], [A_in, BA_in, B_in, AB_in])
             else:
+                A_in, BA_in, B_in, AB_in = A, BA, B, AB
                 with torch.no_grad():
-                    (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = group_discriminators([dA, dB], [A, B])
-                (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = group_discriminators([dA, dB], [BA, AB])
+                    if aug:
+                        A_in, B_in = apply_group([self.aug_A, self.aug_B], [A, B])
+                    (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = group_discriminators([dA, dB], [A_in, B_in])
+                if aug:                                      # the gradient of the fakes flows back through the transform
+                    BA_in, AB_in = apply_group([self.aug_BA, self.aug_AB], [BA, AB])
+                (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = group_discriminators([dA, dB], [BA_in, AB_in])
+            if aug:
+                dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
             # GAN terms (image_translation.py:157-166): slots 2 / 5 bce(real, 1), 4 / 7 bce(fake, 1), 3 / 6 bce(fake, 0)
             terms[2], terms[4], terms[5], terms[7] = F_.BCELossGroupFn.apply(
                 4, (1.0, 1.0, 1.0, 1.0), A_dis_real, A_dis_fake, B_dis_real, B_dis_fake, sl[2], sl[4], sl[5], sl[7])
@@ -544,7 +590,7 @@ class DiscoGANTrainer:
             fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=terms[0], recon_loss_B=terms[1],
             dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
             A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
-            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, backward_cut=cut)
+            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, backward_cut=cut, dis_inputs=dis_inputs)
 
     # ---- the iteration as a sequence of graphs with gaps (overlap_comm="graph") --------------------------------------------------
     def _cut(self, name):
@@ -691,13 +737,19 @@ class DiscoGANTrainer:
         opt.fill_unwritten_grads()
         return self._all_reduce(opt.flat_g, kind)
 
-    def _pool_draw(self, A, B, iters):
-        """With a history pool, ahead of a D-step's dispatch and outside any capture: the record tables of this iteration's two
-        exchanges (BA = G_A(B) has B's batch size, AB = G_B(A) has A's).  Eager launches on the current stream, which everything the
+    def _draw_ahead(self, A, B, iters):
+        """The device draws ahead of an iteration's dispatch, outside any capture.  With a history pool, in a D-step: the record tables
+        of this iteration's two exchanges (BA = G_A(B) has B's batch size, AB = G_B(A) has A's).  With differentiable augmentation, in
+        EVERY iteration: the four tables of the discriminators' inputs.  Eager launches on the current stream, which everything the
         iteration issues -- eagerly or by graph replay -- is ordered behind."""
         if self.pool_BA is not None and self.is_dis_step(iters):
             self.pool_BA.draw(iters, B.shape[0])
             self.pool_AB.draw(iters, A.shape[0])
+        if self.aug_A is not None:
+            self.aug_A.draw(iters, A.shape[0])
+            self.aug_BA.draw(iters, B.shape[0])
+            self.aug_B.draw(iters, B.shape[0])
+            self.aug_AB.draw(iters, A.shape[0])
 
     def train_iteration(self, A, B, iters, do_step=True, need_losses=True):
         """One full iteration; returns the namespace of (device) loss scalars.  need_losses=False tells the
@@ -710,7 +762,7 @@ class DiscoGANTrainer:
         RECON always comes from the unpooled ``AB`` / ``BA``."""
         dstep = self.is_dis_step(iters)
         opt = self.optim_dis if dstep else self.optim_gen
-        self._pool_draw(A, B, iters)
+        self._draw_ahead(A, B, iters)
         if self.graph_overlap:
             return self._train_iteration_graph_overlap(A, B, iters, do_step, need_losses)
         bucketed = self._buckets is not None and not dstep and do_step and self.xg is not None and not self.grad_control

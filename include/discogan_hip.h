@@ -490,6 +490,58 @@ int dg_augment_f32(const float* src, float* dst, int N, int S, int L, const int3
 int dg_pool_draw(uint64_t seed, int rank, int64_t iteration, int domain, int n, int P, int filled,
                  int32_t* recs /* device [n][4]: src, slot, st_src, 0 */, dg_stream_t s);
 int dg_pool_exchange(const float* x, float* pool, float* out, int n, int P, size_t elems, const int32_t* recs, dg_stream_t s);
+/* ---- differentiable augmentation of the discriminators' inputs (Zhao et al., NeurIPS 2020, "DiffAugment") ----------------------
+ * One random, differentiable transform per sample on everything a discriminator sees.  The published policy color,translation,cutout is
+ * defined on x' = 2x - 1 in [-1, 1]; images here live in [0, 1], so it is implemented CONJUGATED by x = (x' + 1) / 2: the brightness
+ * amplitude is halved, and translation padding and cutout fill with 0.5 instead of 0.  x, z: float [n][3][S][S] (NCHW).
+ *
+ * With T = floor(S / 8 + 0.5) and cs = floor(S / 2 + 0.5), the record of a sample is eight int32
+ *   (tx, ty, cx0, cy0, bits(b), bits(s), bits(c), 0);        a table is device int32 [n][8], 16-byte aligned.
+ * Stages, in this order; a stage outside `flags` is not evaluated at all (its record fields are not read), so a geometry-only policy is
+ * a pure copy of bit patterns:
+ *   DG_DIFFAUG_COLOR, fp32:  brightness v = x + b;  saturation m1 = (v0 + v1 + v2) / 3 per pixel, v = (v - m1) s + m1;
+ *                            contrast m2 = mean of v over the sample's 3 S S values, v = (v - m2) c + m2.
+ *                            (Saturation keeps each pixel's channel mean and brightness shifts it by b: m2 = mean(x) + b.)
+ *   DG_DIFFAUG_TRANSLATION, DG_DIFFAUG_CUTOUT:
+ *                            z(ch, y, x) = v(ch, y + ty, x + tx) where (y + ty, x + tx) lies inside the image and (y, x) is not in the
+ *                            cut square [cy0, cy0 + cs) x [cx0, cx0 + cs) (clipped by the image; cx0, cy0 may be negative), else 0.5.
+ * Backward = the adjoint of the linear part (the op is affine in x: nothing of x is saved), a gather, no float atomics:
+ *   g(ch, y', x') = dz(ch, y' - ty, x' - tx) where that position is inside the image and not in the cut square, else 0;
+ *   with COLOR  dx = s c g + (1 - s) c chanmean(g) + (1 - c) G,  G = the sample's mean of g;  without, dx = g.
+ *
+ * dg_diffaug_draw fills a table: record j is a pure function of (seed, rank, iteration, domain 0 = A | 1 = B, role 0 = real batch |
+ * 1 = fake batch, j).  The key chain of dg_augment_draw (mix, G as above) with one more link:
+ *   k = mix(seed + G); k = mix(k ^ (uint64(uint32(rank)) << 32 | uint32(domain))); k = mix(k ^ uint64(iteration));
+ *   k = mix(k ^ (0x6469666600000000 | role));        q_i = mix(k + G (4j + i)), i = 1..4;
+ *   unit(w) = float(w >> 8) 2^-24;  range(w, lo, count) = lo + ((uint64(w) count) >> 32);  hi / lo = the high / low 32 bits;
+ *   b = (unit(hi q_1) - 0.5) 0.5;  s = 2 unit(lo q_1);  c = unit(hi q_2) + 0.5   (fp32 arithmetic);
+ *   tx = range(lo q_2, -T, 2T + 1);  ty = range(hi q_3, -T, 2T + 1);
+ *   cx0 = range(lo q_3, 0, S + 1 - cs % 2) - cs / 2;  cy0 likewise from hi q_4   (the published offset, uniform over S + 1 - cs % 2 values).
+ * Fields of stages outside `flags` hold their neutral values (0, 0, 0, 0, 0.0f, 1.0f, 1.0f).  Rows past n are left untouched.
+ *
+ * The record VALUES need no trust: any int32 in tx / ty / cx0 / cy0 (INT_MIN and INT_MAX included) is memory-safe -- coordinates are
+ * computed in 64 bits --, and any float bits are allowed as factors; a NaN factor or pixel poisons its own sample only.
+ *
+ * Launches: one gather pass; with COLOR a statistics pass in front of it, which leaves parts(S) = min(64, ceil(3 S S / 8192)) fp64 partial
+ * sums per sample in the workspace (forward: of x; backward: of g) -- a fixed partition of the sample, fixed summation order inside a
+ * block and over the partials, no atomics: bitwise repeatable, independent of stream, of the batch and of the grouping.  The workspace is
+ * dg_diffaug_workspace_bytes(n, S, flags) = n parts(S) 8 bytes per problem (0 without COLOR), 8-byte aligned.  16 bytes per lane where
+ * every base is 16-byte aligned and S % 4 == 0 (a sample whose tx is no multiple of 4 reads its shifted rows in 4-byte pieces and still
+ * stores 16), else 4.  1 <= n <= 4096, 2 <= S <= 32768; no output may overlap an input or another output of the launch.
+ * The *_g forms run `groups` (1..DG_MAX_GROUPS) problems of one (n, S, flags) in ONE launch per pass, bitwise the single calls. */
+#define DG_DIFFAUG_COLOR 1
+#define DG_DIFFAUG_TRANSLATION 2
+#define DG_DIFFAUG_CUTOUT 4
+#define DG_DIFFAUG_ALL 7
+int dg_diffaug_draw(uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S, int flags,
+                    int32_t* recs /* device [n][8] */, dg_stream_t s);
+size_t dg_diffaug_workspace_bytes(int n, int S, int flags);
+int dg_diffaug_fwd(const float* x, float* z, int n, int S, int flags, const int32_t* recs, void* ws, size_t ws_bytes, dg_stream_t s);
+int dg_diffaug_bwd(const float* dz, float* dx, int n, int S, int flags, const int32_t* recs, void* ws, size_t ws_bytes, dg_stream_t s);
+int dg_diffaug_fwd_g(int groups, const float* const* x, float* const* z, int n, int S, int flags, const int32_t* const* recs,
+                     void* const* ws, size_t ws_bytes, dg_stream_t s);
+int dg_diffaug_bwd_g(int groups, const float* const* dz, float* const* dx, int n, int S, int flags, const int32_t* const* recs,
+                     void* const* ws, size_t ws_bytes, dg_stream_t s);
 /* ---- sample grids (image_translation.py:170-209): the inverse of the ingest, tiled -------------------------
    src: HOST table of `cols` device pointers, each a float batch [n_c][3][S][S] (NCHW, n_c >= rows).
    canvas: device uint8 [Hc][Wc][3], Hc = rows*(S+gap)+gap, Wc = cols*(S+gap)+gap.
