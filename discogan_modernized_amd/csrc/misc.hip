@@ -63,12 +63,15 @@ extern "C" int dg_device_cu_count(void) {
     return n;
 }
 
-// 32x32 tile transpose through LDS between the [C] and [H*W] axes of one image
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ x, float* __restrict__ y, int R, int Cn) {
+// 32x32 tile transpose through LDS between the [C] and [H*W] axes of one image.  The tiles of one image are numbered along grid.x,
+// column tile fastest (tiles_c = ceil(Cn / 32)): grid.y and grid.z stop at 65536, and R = H*W of a single-channel plane of
+// 1449 x 1449 pixels already has 65613 row tiles.
+__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ x, float* __restrict__ y, int R, int Cn, int tiles_c) {
     // x: [B][R][Cn] -> y: [B][Cn][R]
     __shared__ float tile[32][33];
     const long boff = (long)blockIdx.z * R * Cn;
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+    const int tr = blockIdx.x / tiles_c;
+    const int c0 = (blockIdx.x - tr * tiles_c) * 32, r0 = tr * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int j = ty; j < 32; j += 8) {
         const int r = r0 + j, c = c0 + tx;
@@ -80,19 +83,25 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
         if (r < R && c < Cn) y[boff + (long)c * R + r] = tile[tx][j];
     }
 }
-static int launch_transpose(const float* x, float* y, int B, int R, int Cn, hipStream_t st) {
-    dim3 grid((Cn + 31) / 32, (R + 31) / 32, B);
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, st, x, y, R, Cn);
+#define TRANSPOSE_MAX_TILES 16777215L   // grid.x * 256 threads must stay below 2^32
+static int launch_transpose(const char* who, const float* x, float* y, int B, long R, long Cn, hipStream_t st) {
+    DG_CHECK_ARG(R <= 2147483647L && Cn <= 2147483647L && R * Cn <= 2147483647L, "%s: C*H*W of one image must not exceed 2^31 - 1", who);
+    const long tiles_c = (Cn + 31) / 32, tiles_r = (R + 31) / 32;
+    DG_CHECK_ARG(tiles_c * tiles_r <= TRANSPOSE_MAX_TILES,
+                 "%s: one image takes ceil(C/32) * ceil(H*W/32) = %ld tiles of 32 x 32, more than %ld (grid.x of 256-thread blocks)", who,
+                 tiles_c * tiles_r, TRANSPOSE_MAX_TILES);
+    dim3 grid((unsigned)(tiles_c * tiles_r), 1, B);
+    hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, st, x, y, (int)R, (int)Cn, (int)tiles_c);
     DG_CHECK_LAUNCH("transpose");
     return DG_OK;
 }
 extern "C" int dg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, dg_stream_t s) {
     DG_CHECK_ARG(x && y && N > 0 && C > 0 && H > 0 && W > 0 && N < 65536, "dg_nchw_to_nhwc: bad argument");
-    return launch_transpose(x, y, N, C, H * W, (hipStream_t)s);  // [N][C][HW] -> [N][HW][C]
+    return launch_transpose("dg_nchw_to_nhwc", x, y, N, C, (long)H * W, (hipStream_t)s);  // [N][C][HW] -> [N][HW][C]
 }
 extern "C" int dg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, dg_stream_t s) {
     DG_CHECK_ARG(x && y && N > 0 && C > 0 && H > 0 && W > 0 && N < 65536, "dg_nhwc_to_nchw: bad argument");
-    return launch_transpose(x, y, N, H * W, C, (hipStream_t)s);  // [N][HW][C] -> [N][C][HW]
+    return launch_transpose("dg_nhwc_to_nchw", x, y, N, (long)H * W, C, (hipStream_t)s);  // [N][HW][C] -> [N][C][HW]
 }
 
 // ---- image ingest (dataset.py:62-66): uint8 [N][H][W][3] (decoded image rows) -> float [N][3][H][W] in [0,1] ----

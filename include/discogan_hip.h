@@ -686,7 +686,9 @@ int dg_fm_fwd_t(const void* real, const void* fake, int io_bf16, int N, size_t J
                 size_t ws_bytes, dg_stream_t stream);
 int dg_fm_bwd_t(const float* diff, int N, size_t J, const float* gout, void* dreal, void* dfake, int io_bf16, dg_stream_t stream);
 
-/* ---- layout helpers --------------------------------------------------------------------------- */
+/* ---- layout helpers ---------------------------------------------------------------------------
+ * fp32, N < 65536, C*H*W of one image <= 2^31 - 1 and ceil(C/32) * ceil(H*W/32) <= 16777215 (one image's 32 x 32 tiles lie along
+ * grid.x); anything else is refused before a launch. */
 int dg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, dg_stream_t s);
 int dg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, dg_stream_t s);
 
