@@ -142,6 +142,16 @@ SIGNATURES = {
     "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
+    "dg_swd_max_row": (_i, []),
+    "dg_swd_levels": (_i, [_i]),
+    "dg_lap_pyramid_elems": (_z, [_i, _i]),
+    "dg_lap_pyramid": (_i, [_p, _i, _i, _p, _p]),
+    "dg_swd_draw": (_i, [C.c_uint64, _i, _i, _i, _i, _p, _p]),
+    "dg_swd_descriptors_workspace_bytes": (_z, [_i]),
+    "dg_swd_descriptors": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "dg_swd_project": (_i, [_p, _p, _i, _p, _i, _p, _p]),
+    "dg_swd_sort_rows": (_i, [_p, _i, _i, _p]),
+    "dg_swd_row_distance": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "dg_f32_to_bf16": (_i, [_p, _p, _z, _p]),
     "dg_bn_act_fwd_bf16": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _p]),
     "dg_bn_act_bwd_bf16": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _p, _p, _i, _p, _z, _p]),

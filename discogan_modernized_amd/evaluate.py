@@ -10,6 +10,10 @@ What is scored:
   trans_AB, trans_BA    paired splits only (``edges2shoes`` / ``edges2handbags``: image i of A and image i of B are the two halves of
                         one file): the translation ``A->B`` against ``B`` and ``B->A`` against ``A``, over the first min(n_A, n_B) images
 
+  swd_AB, swd_BA        with ``--eval_swd`` / ``--swd``, paired or not: the sliced Wasserstein distance (``SWD`` below) between the
+                        translations ``A->B`` and ``test_B``, and between ``B->A`` and ``test_A`` -- the only score an unpaired split has
+                        for the translations themselves
+
 Two ways to run it, which score different things:
   ``--eval_interval N`` of the training CLIs   scores the images of the sample grid: ``DiscoGANTrainer.sample``, generators in TRAINING
                         mode (BatchNorm normalises with the statistics of the whole split, one batch per pass; every event moves the
@@ -31,6 +35,7 @@ import torch
 
 PAIRED_TASKS = ("edges2shoes", "edges2handbags")        # dataset.py:52-60: both domains are cut from the same files
 MIN_SIZE = 11                                             # the SSIM window
+SWD_MIN_SIZE = 16                                         # the coarsest pyramid level of the sliced Wasserstein distance
 
 
 def paired_default(args, data_kind):
@@ -49,8 +54,96 @@ def summarise(rows):
     return dict(n=int(r.shape[0]), mse=float(mse.mean()), mae=float(r[:, 1].mean()), ssim=float(r[:, 2].mean()), psnr=float(psnr.mean()))
 
 
-def evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, paired):
-    """The metric launches of one evaluation event on the six device batches of a sampling event -> dict of ``summarise`` dicts."""
+class SWD:
+    """Sliced Wasserstein distance between a fixed REAL set and generated sets, on Laplacian-pyramid patches (Karras et al., ICLR 2018,
+    section 5; include/discogan_hip.h, "sliced Wasserstein distance", is the definition).  Per level: ``P`` 7 x 7 x 3 patches per image at
+    keyed positions, each channel normalised over the set, ``dirs`` unit directions, both sets' projections sorted,
+    ``SWD_l = 1000 mean_d mean_i |a_(i) - b_(i)|``; ``mean`` is the mean over the levels.  Deviations from the publication: a channel of
+    standard deviation exactly 0 becomes zeros (the publication divides by zero); positions and directions are keyed on ``seed`` alone, so
+    every event and every checkpoint is scored on the same patches and directions; no network, no host arithmetic but the last means.
+
+    ``n`` images of both sets are used: ``P = min(patches, DG_SWD_MAX_ROW // n)`` patches per image, so that a row of ``M = n P`` projected
+    values fits the LDS of the one workgroup that sorts it (n = 200: P = 128, M = 25600).
+
+    Memory.  ``set_reference`` keeps the real set's sorted projections, ``D M 4`` bytes per level: 52 MB per level at n = 200, so 0.31 GB
+    for the six levels of 512 px and about 0.6 GB for the two objects (one per domain) of an evaluation.  The descriptor table (M x 147) and the
+    projection table (D x M) are allocated once, here; the few KB of statistics partials and each event's pyramid (4 n S^2 floats) come
+    from torch's caching allocator."""
+
+    def __init__(self, n, image_size, device, seed=0, patches=128, dirs=512):
+        from . import ops
+        self.n, self.size, self.seed, self.device = int(n), int(image_size), int(seed), torch.device(device)
+        self.sizes = ops.swd_levels(image_size)
+        if not self.sizes:
+            raise ValueError(f"the sliced Wasserstein distance needs --image_size >= {SWD_MIN_SIZE}, got {image_size}")
+        if not 1 <= self.n <= ops.swd_max_row():
+            raise ValueError(f"the sliced Wasserstein distance takes 1 to {ops.swd_max_row()} images per set, got {n}")
+        self.patches = ops.swd_patches(self.n, patches)
+        self.M, self.D = self.n * self.patches, int(dirs)
+        self.dirs = make_swd_directions(self.seed, self.D).to(self.device)
+        self.recs = [ops.swd_draw(self.seed, l, self.n, R, self.patches, device=self.device) for l, R in enumerate(self.sizes)]
+        self.desc = torch.empty((self.M, ops.SWD_DESC), device=self.device, dtype=torch.float32)
+        self.stats = torch.empty((3, 2), device=self.device, dtype=torch.float64)
+        self.proj = torch.empty((self.D, self.M), device=self.device, dtype=torch.float32)
+        self.dist = torch.empty((len(self.sizes), self.D), device=self.device, dtype=torch.float64)
+        self.ref = None
+
+    def _project(self, l, level, out):
+        from . import ops
+        ops.swd_descriptors(level, self.recs[l], desc=self.desc, stats=self.stats)
+        return ops.swd_project(self.desc, self.stats, self.dirs, out=out)
+
+    def _levels(self, x):
+        from . import ops
+        if x.dim() != 4 or x.shape[0] < self.n or tuple(x.shape[1:]) != (3, self.size, self.size):
+            raise ValueError(f"SWD was built for at least {self.n} images [3,{self.size},{self.size}], got {tuple(x.shape)}")
+        return ops.lap_pyramid(x[:self.n])
+
+    def set_reference(self, real):
+        """Builds and keeps the sorted projections of the first n images of ``real`` for every level (once per run)."""
+        from . import ops
+        self.ref = []
+        for l, level in enumerate(self._levels(real)):
+            ref = torch.empty((self.D, self.M), device=self.device, dtype=torch.float32)
+            self.ref.append(ops.swd_sort_rows(self._project(l, level, ref)))
+        return self
+
+    def score(self, fake):
+        """The first n images of ``fake`` against the reference -> dict(levels=[SWD_l], mean, n, patches); one D2H copy of [L][D] doubles."""
+        from . import ops
+        if self.ref is None:
+            raise RuntimeError("SWD.score before SWD.set_reference")
+        for l, level in enumerate(self._levels(fake)):
+            ops.swd_row_distance(self._project(l, level, self.proj), self.ref[l], out=self.dist[l])
+        levels = [1000.0 * float(v) for v in self.dist.cpu().mean(dim=1)]
+        return dict(levels=levels, mean=sum(levels) / len(levels), n=self.n, patches=self.patches)
+
+
+def make_swd_directions(seed, dirs=512):
+    """float32 [dirs,147]: standard-normal vectors from ``torch.Generator().manual_seed(seed)``, scaled to unit length in float64 and
+    rounded once."""
+    g = torch.Generator().manual_seed(int(seed))
+    v = torch.randn((int(dirs), 147), generator=g, dtype=torch.float64)
+    return (v / v.norm(dim=1, keepdim=True)).float()
+
+
+def make_swd_pair(test_A, test_B, image_size, seed=0):
+    """The two ``SWD`` objects of an evaluation, references built: ``(against test_B, against test_A)`` over the first
+    min(n_A, n_B) images -- what ``evaluate_outputs(..., swd=...)`` takes.  Also returns SWD(test_A, test_B), the gap between the domains."""
+    n = min(len(test_A), len(test_B))
+    to_B = SWD(n, image_size, test_B.device, seed=seed).set_reference(test_B)
+    to_A = SWD(n, image_size, test_A.device, seed=seed).set_reference(test_A)
+    return (to_B, to_A), to_B.score(test_A)
+
+
+def format_swd(r):
+    return "/".join(f"{v:.3f}" for v in r["levels"]) + f"={r['mean']:.3f}"
+
+
+def evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, paired, swd=None):
+    """The metric launches of one evaluation event on the six device batches of a sampling event -> dict of ``summarise`` dicts.
+    ``swd``: two ``SWD`` objects with their references set, ``(against test_B, against test_A)``: the result also holds ``swd_AB`` and
+    ``swd_BA`` (dicts of ``SWD.score``), for paired and unpaired splits alike."""
     from . import ops
     pairs = [("recon_A", test_A, ABA), ("recon_B", test_B, BAB)]
     if paired:
@@ -62,6 +155,9 @@ def evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, paired):
     for (name, _, _), r in zip(pairs, rows):
         res[name] = summarise(host[at:at + len(r)])
         at += len(r)
+    if swd is not None:
+        res["swd_AB"] = swd[0].score(AB)
+        res["swd_BA"] = swd[1].score(BA)
     return res
 
 
@@ -73,21 +169,25 @@ def format_eval(iters, res):
     if "trans_AB" in res:
         s += (f", TRANS_PSNR: {pair('psnr', 'trans_AB', 'trans_BA', '.3f')}, TRANS_SSIM: {pair('ssim', 'trans_AB', 'trans_BA', '.4f')}, "
               f"TRANS_MAE: {pair('mae', 'trans_AB', 'trans_BA', '.5f')}")
+    if "swd_AB" in res:
+        s += f", SWD_AB: {format_swd(res['swd_AB'])}, SWD_BA: {format_swd(res['swd_BA'])}"
     return s + f" (n={res['recon_A']['n']}/{res['recon_B']['n']})"
 
 
-def evaluate_split(trainer, split, paired, outs=None):
+def evaluate_split(trainer, split, paired, outs=None, swd=None):
     """One evaluation event of a training run: the four passes of ``trainer.sample`` (unless the sampling event of the same iteration
-    already ran them: ``outs``), then the metrics.  Returns ``(res, outs)``."""
+    already ran them: ``outs``), then the metrics (``swd``: see ``evaluate_outputs``).  Returns ``(res, outs)``."""
     test_A, test_B = split
     if outs is None:
         outs = trainer.sample(test_A, test_B)
-    return evaluate_outputs(test_A, test_B, *outs, paired), outs
+    return evaluate_outputs(test_A, test_B, *outs, paired, swd=swd), outs
 
 
-def check_size(image_size):
+def check_size(image_size, swd=False):
     if image_size < MIN_SIZE:
         raise ValueError(f"evaluation needs --image_size >= {MIN_SIZE} (the 11 x 11 SSIM window), got {image_size}")
+    if swd and image_size < SWD_MIN_SIZE:
+        raise ValueError(f"the sliced Wasserstein distance needs --image_size >= {SWD_MIN_SIZE} (its coarsest pyramid level), got {image_size}")
 
 
 def parse_args(argv=None):
@@ -102,13 +202,17 @@ def parse_args(argv=None):
     p.add_argument("--use_extra_layers", action="store_true")
     p.add_argument("--no_fold", action="store_true", help="run the training modules in eval() mode instead of the folded form")
     p.add_argument("--use_ema", action="store_true", help="score gen_A_ema_final.pth / gen_B_ema_final.pth (a run with --ema_decay)")
+    p.add_argument("--swd", action="store_true",
+                   help="also score the sliced Wasserstein distance of the translations against the other domain's test images "
+                        "(swd_AB, swd_BA) and of the two test sets against each other (swd_domains); works on unpaired splits")
+    p.add_argument("--swd_seed", type=int, default=0, help="key of the patch positions and directions of --swd")
     p.add_argument("--output", type=str, default="eval.json")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    check_size(args.image_size)
+    check_size(args.image_size, swd=args.swd)
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible: this implementation has no CPU path")
     from . import inference, samples
@@ -127,7 +231,11 @@ def main(argv=None):
     with torch.no_grad():
         AB, BA = g_ab(test_A), g_ba(test_B)
         ABA, BAB = g_ba(AB), g_ab(BA)
-    res = evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, args.paired)
+    swd, domains = make_swd_pair(test_A, test_B, args.image_size, args.swd_seed) if args.swd else (None, None)
+    res = evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, args.paired, swd=swd)
+    if args.swd:
+        res["swd_domains"] = domains
+        print(f"SWD_DOMAINS: {format_swd(domains)} (n={domains['n']}, {domains['patches']} patches per image)", flush=True)
     print(format_eval("final", res), flush=True)
     with open(args.output, "w") as f:
         json.dump(res, f, indent=1)

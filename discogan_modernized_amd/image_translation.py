@@ -23,6 +23,9 @@ reference these passes move the generators' BatchNorm running statistics.
 Held-out evaluation (evaluate.py): every ``--eval_interval`` iterations (0 = never, the default) the same split is scored -- PSNR, SSIM
 and MAE of the reconstructions, and of the translations when the split is paired (``--eval_paired``) -- and one line goes to
 ``results/.../eval_log.txt``.  An iteration that also writes a sample grid runs the four passes once for both.
+``--eval_swd`` appends the sliced Wasserstein distance (``evaluate.SWD``: Laplacian-pyramid patches, no pairing needed) between the
+translations and the other domain's held-out images to every such line, from the same passes; the held-out sets are projected and sorted
+once at start, where ``SWD_DOMAINS:`` prints the distance between the two held-out sets themselves.
 
 Weight EMA (optim.EMA): ``--ema_decay D`` (0 = off) keeps ``ema = D * ema + (1 - D) * w`` of both generators' weights, updated behind every
 generator step from ``--ema_start_iter`` on; every model save also writes ``gen_A_ema_{tag}.pth`` / ``gen_B_ema_{tag}.pth`` (EMA weights, live
@@ -109,6 +112,11 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--eval_paired", type=str, default="auto", choices=["auto", "on", "off"],
                    help="image i of test A and of test B show the same thing, so the translations are scored too; auto: the files "
                         "source of edges2shoes / edges2handbags")
+    p.add_argument("--eval_swd", action="store_true",
+                   help="with --eval_interval: also score the sliced Wasserstein distance on Laplacian-pyramid patches between the "
+                        "translations and the other domain's held-out images (SWD_AB, SWD_BA; needs no pairing); keeps "
+                        "512 * n * P * 4 bytes per pyramid level and domain on the device (evaluate.SWD)")
+    p.add_argument("--eval_swd_seed", type=int, default=0, help="key of the patch positions and directions of --eval_swd")
     p.add_argument("--ema_decay", type=float, default=0.0,
                    help="keep an exponential moving average of both generators' weights with this decay (e.g. 0.999; 0 = off) and "
                         "save it as gen_A_ema_*.pth / gen_B_ema_*.pth next to the live checkpoints")
@@ -333,6 +341,14 @@ def batches_per_epoch(args, data_size, world_size):
     return data_size // args.batch_size
 
 
+def check_eval_swd(args):
+    """--eval_swd scores at the evaluation events, so it needs --eval_interval."""
+    on = bool(getattr(args, "eval_swd", False))
+    if on and int(getattr(args, "eval_interval", 0) or 0) <= 0:
+        raise ValueError("--eval_swd scores at the evaluation events: it needs --eval_interval > 0")
+    return on
+
+
 def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=None):
     if args.task_name not in TASKS:
         raise ValueError(f"unknown task_name {args.task_name}; choose from {TASKS}")
@@ -340,9 +356,10 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     image_pool = check_image_pool(getattr(args, "image_pool", 0))           # likewise: a negative --image_pool
     diffaug = check_diffaug(getattr(args, "diffaug", ""))                   # likewise: an unknown --diffaug policy
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
+    eval_swd = check_eval_swd(args)                                        # likewise: --eval_swd without --eval_interval
     if eval_interval > 0:
         from . import evaluate
-        evaluate.check_size(args.image_size)
+        evaluate.check_size(args.image_size, swd=eval_swd)
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible: this implementation has no CPU path (use the reference for CPU runs)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -380,6 +397,11 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
         from . import samples
         split = samples.load_split(args, data_kind, device, world_size)
     eval_paired = eval_interval > 0 and evaluate.paired_default(args, data_kind)
+    swd = None
+    if eval_swd and split is not None:
+        # the real sets' sorted projections, once; SWD(test_A, test_B) is the gap a translation has to close, the same all run long
+        swd, domains = evaluate.make_swd_pair(*split, args.image_size, int(getattr(args, "eval_swd_seed", 0)))
+        print(f"SWD_DOMAINS: {evaluate.format_swd(domains)} (n={domains['n']}, {domains['patches']} patches per image)", flush=True)
     n_batches = batches_per_epoch(args, data_size, world_size)
     if n_batches < 1:
         raise ValueError(f"batch_size {args.batch_size} leaves no full batch in {data_size} images on {world_size} rank(s)")
@@ -434,7 +456,7 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                 if sampling:
                     samples.save_samples(trainer, split, result_path / "samples", iters, outs=outs)
                 if evaluating:
-                    res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs)
+                    res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs, swd=swd)
                     msg = evaluate.format_eval(iters, res) + (" [ema]" if on_ema else "")
                     print(msg, flush=True)
                     with open(result_path / "eval_log.txt", "a") as f:

@@ -422,6 +422,140 @@ def image_metrics(x, y):
     return out
 
 
+# ---- sliced Wasserstein distance on Laplacian-pyramid patches (include/discogan_hip.h defines every stage) -----------------------
+SWD_DESC = 147                 # floats per descriptor: 3 x 7 x 7, [channel][dy][dx]
+SWD_PATCH = 7
+
+
+def swd_max_row():
+    """DG_SWD_MAX_ROW of the loaded library: the longest row (descriptors per set and level) one workgroup sorts in LDS."""
+    return int(_lib.load().dg_swd_max_row())
+
+
+def swd_levels(S):
+    """The pyramid's resolutions for images of S pixels: [S, S/2, ...] while the size is even and its half is at least 16; [] for S < 16."""
+    L = int(_lib.load().dg_swd_levels(int(S)))
+    return [int(S) >> l for l in range(L)]
+
+
+def swd_patches(n, patches=128):
+    """Patches per image for a set of n images: min(patches, DG_SWD_MAX_ROW // n), so that a row of n P values fits one workgroup."""
+    return min(int(patches), swd_max_row() // max(int(n), 1))
+
+
+def _swd_fail(msg):
+    raise _lib.DiscoganHipError(msg)
+
+
+def _swd_buf(t, shape, dtype, who, what):
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        _swd_fail(f"{who} needs {what} as a contiguous {dtype} HIP tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def lap_pyramid(x):
+    """float32 NCHW batch [n,3,S,S] (S >= 16) -> the list of its Laplacian-pyramid levels [n,3,R_l,R_l], views of one buffer
+    (dg_lap_pyramid: [1 4 6 4 1] / 16, mirror border; the last level is the Gaussian level itself)."""
+    _check_dev(x)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        _swd_fail(f"lap_pyramid needs a [n,3,S,S] batch, got {tuple(x.shape)}")
+    n, S = int(x.shape[0]), int(x.shape[3])
+    Rs = swd_levels(S)
+    if n < 1 or not Rs:
+        _swd_fail(f"lap_pyramid needs n >= 1 images of S >= 16 pixels, got n={n}, S={S}")
+    xc = x.contiguous()
+    L = _lib.load()
+    out = torch.empty(int(L.dg_lap_pyramid_elems(n, S)), device=x.device, dtype=torch.float32)
+    _lib.check(L.dg_lap_pyramid(_ptr(xc), n, S, _ptr(out), _stream()), "dg_lap_pyramid")
+    levels, at = [], 0
+    for R in Rs:
+        levels.append(out[at:at + n * 3 * R * R].view(n, 3, R, R))
+        at += n * 3 * R * R
+    return levels
+
+
+def swd_draw(seed, level, n, R, P, out=None, device="cuda"):
+    """The patch positions of one level: int32 [n, P, 2] = (oy, ox) in [0, R - 7], drawn on the device as a pure function of
+    (seed, level, image, patch) -- dg_swd_draw.  ``out``: a table of at least n images to fill (rows from n on stay as they are)."""
+    if out is None:
+        out = torch.empty((int(n), int(P), 2), device=device, dtype=torch.int32)
+    if not (out.is_cuda and out.dtype == torch.int32 and out.dim() == 3 and out.shape[1] == P and out.shape[2] == 2 and out.is_contiguous()
+            and out.shape[0] >= n):
+        _swd_fail(f"swd_draw needs a contiguous int32 HIP record table of shape [>= {n}, {P}, 2]")
+    _lib.check(_lib.load().dg_swd_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(level), int(n), int(R), int(P), _ptr(out), _stream()), "dg_swd_draw")
+    return out[:n]
+
+
+def swd_descriptors(level, recs, desc=None, stats=None):
+    """One pyramid level [n,3,R,R] and its record table int32 [n,P,2] -> (desc float32 [n P, 147], stats float64 [3, 2] = per channel mean
+    and population standard deviation of the descriptor values) -- dg_swd_descriptors.  Offsets are clamped into the image."""
+    _check_dev(level)
+    if level.dim() != 4 or level.shape[1] != 3 or level.shape[2] != level.shape[3] or not level.is_contiguous():
+        _swd_fail(f"swd_descriptors needs a contiguous [n,3,R,R] level, got {tuple(level.shape)}")
+    n, R = int(level.shape[0]), int(level.shape[3])
+    if not (recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 3 and recs.shape[0] == n and recs.shape[2] == 2 and recs.is_contiguous()):
+        _swd_fail(f"swd_descriptors needs a contiguous int32 HIP record table of shape [{n}, P, 2]")
+    P = int(recs.shape[1])
+    M = n * P
+    if n < 1 or P < 1 or M > swd_max_row() or R < SWD_PATCH:
+        _swd_fail(f"swd_descriptors needs 1 <= n P <= {swd_max_row()} and R >= {SWD_PATCH}, got n={n}, P={P}, R={R}")
+    desc = torch.empty((M, SWD_DESC), device=level.device, dtype=torch.float32) if desc is None else \
+        _swd_buf(desc, (M, SWD_DESC), torch.float32, "swd_descriptors", "desc")
+    stats = torch.empty((3, 2), device=level.device, dtype=torch.float64) if stats is None else \
+        _swd_buf(stats, (3, 2), torch.float64, "swd_descriptors", "stats")
+    L = _lib.load()
+    nbytes = int(L.dg_swd_descriptors_workspace_bytes(M))
+    ws = torch.empty(nbytes // 8, device=level.device, dtype=torch.float64)
+    _lib.check(L.dg_swd_descriptors(_ptr(level), n, R, P, _ptr(recs), _ptr(desc), _ptr(stats), _ptr(ws), nbytes, _stream()), "dg_swd_descriptors")
+    return desc, stats
+
+
+def swd_project(desc, stats, dirs, out=None):
+    """desc float32 [M,147], stats float64 [3,2], dirs float32 [D,147] -> proj float32 [D,M]: the normalised descriptors on every
+    direction (dg_swd_project: fp32 fma chain, a channel of standard deviation 0 contributes zeros)."""
+    _check_dev(desc, dirs)
+    if desc.dim() != 2 or desc.shape[1] != SWD_DESC or dirs.dim() != 2 or dirs.shape[1] != SWD_DESC or not desc.is_contiguous() \
+            or not dirs.is_contiguous():
+        _swd_fail(f"swd_project needs contiguous desc [M,{SWD_DESC}] and dirs [D,{SWD_DESC}], got {tuple(desc.shape)} and {tuple(dirs.shape)}")
+    _swd_buf(stats, (3, 2), torch.float64, "swd_project", "stats")
+    M, D = int(desc.shape[0]), int(dirs.shape[0])
+    if M < 1 or D < 1 or M > swd_max_row():
+        _swd_fail(f"swd_project needs 1 <= M <= {swd_max_row()} and D >= 1, got M={M}, D={D}")
+    out = torch.empty((D, M), device=desc.device, dtype=torch.float32) if out is None else _swd_buf(out, (D, M), torch.float32, "swd_project", "out")
+    _lib.check(_lib.load().dg_swd_project(_ptr(desc), _ptr(stats), M, _ptr(dirs), D, _ptr(out), _stream()), "dg_swd_project")
+    return out
+
+
+def _swd_rows(proj, who):
+    _check_dev(proj)
+    if proj.dim() != 2 or not proj.is_contiguous():
+        _swd_fail(f"{who} needs a contiguous [D,M] tensor, got {tuple(proj.shape)}")
+    D, M = int(proj.shape[0]), int(proj.shape[1])
+    if D < 1 or M < 1 or M > swd_max_row():
+        _swd_fail(f"{who} needs D >= 1 rows of 1 <= M <= {swd_max_row()} values (one workgroup sorts a row in LDS), got D={D}, M={M}")
+    return D, M
+
+
+def swd_sort_rows(proj):
+    """Sorts every row of float32 [D,M] ascending IN PLACE (dg_swd_sort_rows; total order on the bits: -inf first, +inf last, NaNs beyond)."""
+    D, M = _swd_rows(proj, "swd_sort_rows")
+    _lib.check(_lib.load().dg_swd_sort_rows(_ptr(proj), D, M, _stream()), "dg_swd_sort_rows")
+    return proj
+
+
+def swd_row_distance(proj, ref_sorted, out=None, sorted_out=None):
+    """float32 [D,M] and sorted rows [D,M] -> float64 [D]: out[d] = mean_i |sort(proj[d])_i - ref_sorted[d][i]| (dg_swd_row_distance).
+    ``proj`` is only read; its sorted rows are written to ``sorted_out`` when given."""
+    D, M = _swd_rows(proj, "swd_row_distance")
+    _check_dev(ref_sorted, sorted_out)
+    _swd_buf(ref_sorted, (D, M), torch.float32, "swd_row_distance", "ref_sorted")
+    if sorted_out is not None:
+        _swd_buf(sorted_out, (D, M), torch.float32, "swd_row_distance", "sorted_out")
+    out = torch.empty(D, device=proj.device, dtype=torch.float64) if out is None else _swd_buf(out, (D,), torch.float64, "swd_row_distance", "out")
+    _lib.check(_lib.load().dg_swd_row_distance(_ptr(proj), _ptr(ref_sorted), D, M, _ptr(out), _ptr(sorted_out), _stream()), "dg_swd_row_distance")
+    return out
+
+
 def krsc_param(w_logical):
     """[K,C,4,4] contiguous -> same logical tensor whose memory is [K,4,4,C] (dim 1 innermost)."""
     return w_logical.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)

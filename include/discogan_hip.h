@@ -560,6 +560,51 @@ int dg_sample_grid_u8(const float* const* src, int cols, int rows, int S, int ga
    the other pairs (a NaN / inf in pair i reaches row i only). */
 size_t dg_image_metrics_workspace_bytes(int n, int S);
 int dg_image_metrics(const float* x, const float* y, int n, int S, float* out /* [n][3] */, void* ws, size_t ws_bytes, dg_stream_t s);
+/* ---- sliced Wasserstein distance on Laplacian-pyramid patches (evaluate.py; Karras et al., ICLR 2018, "Progressive Growing of GANs",
+ * section 5): a score for UNPAIRED sets, no network.  x, y: float [n][3][S][S] (NCHW), values as they are (no clamp), S >= 16.
+ *
+ * Levels.  R_0 = S; level l + 1 exists while R_l is even and R_l / 2 >= 16, with R_{l+1} = R_l / 2; L = dg_swd_levels(S) levels
+ * (16 -> 1, 32 -> 2, 34 -> 2 (34, 17), 48 -> 2, 64 -> 3, 96 -> 3, 512 -> 6; 0 for S < 16).  An odd R occurs only at the last level.
+ * Pyramid.  w = [1 4 6 4 1] / 16, separable; MIRROR border (index -1 -> 1, R -> R - 2: no edge repeat; scipy.ndimage mode='mirror', not
+ * 'reflect').  down(a) = filter, then every second row and column from 0.  up(a) = a at the even positions of a zero image of twice the
+ * size, filtered with 4 w (x) w.  G_0 = x, G_{l+1} = down(G_l); level l < L - 1 is G_l - up(G_{l+1}), level L - 1 is G_{L-1}.
+ *   dg_lap_pyramid writes all levels into `out`, level l as [n][3][R_l][R_l] at float offset 3 n (R_0^2 + ... + R_{l-1}^2);
+ *   dg_lap_pyramid_elems(n, S) floats in all.  x and out do not overlap; any 4-byte alignment (16-byte lanes where alignment and R % 4
+ *   allow, the same bits either way).  fp32.
+ * Patches.  P patches of 7 x 7 x 3 per image and level, top-left (oy, ox) uniform in [0, R - 7]^2, a pure function of (seed, level,
+ * image j, patch p): the key chain of dg_augment_draw (mix, G as above) with a link of its own --
+ *   k = mix(seed + G); k = mix(k ^ (0x7377640000000000 | level)); q = mix(k + G (j P + p + 1));
+ *   oy = (uint64(high 32 bits of q) (R - 6)) >> 32; ox likewise from the low 32 bits.
+ * No rank, no iteration: every event scores the same patches, and one table serves both sets.  dg_swd_draw fills device int32
+ * [n][P][2] = (oy, ox), 8-byte aligned; rows past n are untouched.  R >= 7.
+ * Descriptors.  dg_swd_descriptors gathers desc [n P][147], a descriptor ordered [channel][dy][dx], as a bit copy of `level`
+ * ([n][3][R][R]); the record VALUES need no trust: offsets are clamped to [0, R - 7].  stats: device double [3][2] = per channel the
+ * mean and the population standard deviation (ddof 0) of its n P 49 descriptor values, fp64, two passes, fixed partition and order.
+ * ws: dg_swd_descriptors_workspace_bytes(n P) bytes, 8-byte aligned.
+ * Projection.  dg_swd_project: xhat = (v - mean_c) / std_c (all zeros for a channel whose std is exactly 0 -- the publication divides by
+ * zero there), proj[d][i] = sum_k xhat[i][k] dirs[d][k]: float [D][M], M = n P, fp32 fma chain in ascending k (no bf16 rounding).
+ * dirs: float [D][147], unit vectors made by the caller (evaluate.py: standard normal from torch.Generator().manual_seed(seed), scaled
+ * to unit length in float64, rounded once).
+ * Distance.  dg_swd_sort_rows sorts every row of [D][M] ascending in place; dg_swd_row_distance sorts a copy of each row of `proj` and
+ * writes out[d] = mean_i |a_(i) - ref_sorted[d][i]| (double [D]; fp32 terms, fp64 from the wave sum on, fixed order, no atomics: the
+ * same input gives the same bits, and exchanging the two sets gives the same bits); the sorted row goes to sorted_out[d] unless that is
+ * NULL.  SWD_l = 1000 mean_d out[d] is the caller's.  One workgroup sorts one row in LDS, so 1 <= M <= DG_SWD_MAX_ROW (32768 floats =
+ * 128 KiB of the CU's 160 KiB), D >= 1.  The order is total on the bit patterns: -inf first, +inf last, NaNs beyond them; a NaN anywhere
+ * in a row makes that row's distance NaN and no other's. */
+#define DG_SWD_MAX_ROW 32768
+int dg_swd_max_row(void);
+int dg_swd_levels(int S);
+size_t dg_lap_pyramid_elems(int n, int S);
+int dg_lap_pyramid(const float* x, int n, int S, float* out, dg_stream_t s);
+int dg_swd_draw(uint64_t seed, int level, int n, int R, int P, int32_t* recs /* device [n][P][2]: oy, ox */, dg_stream_t s);
+size_t dg_swd_descriptors_workspace_bytes(int M);
+int dg_swd_descriptors(const float* level, int n, int R, int P, const int32_t* recs, float* desc /* [n P][147] */, double* stats /* [3][2] */,
+                       void* ws, size_t ws_bytes, dg_stream_t s);
+int dg_swd_project(const float* desc, const double* stats, int M, const float* dirs /* [D][147] */, int D, float* proj /* [D][M] */,
+                   dg_stream_t s);
+int dg_swd_sort_rows(float* proj /* [D][M] */, int D, int M, dg_stream_t s);
+int dg_swd_row_distance(const float* proj, const float* ref_sorted, int D, int M, double* out /* [D] */, float* sorted_out /* or NULL */,
+                        dg_stream_t s);
 
 /* ---- bf16 shadow operands for the bf16 matrix path (option "bf16" = 1; BASELINE configs[4]) ---------------------
  * A shadow is a bf16 (RNE) copy of an fp32 tensor with the same logical layout, written by the tensor's PRODUCER so that
