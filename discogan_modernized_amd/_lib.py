@@ -142,6 +142,11 @@ SIGNATURES = {
     "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
+    "dg_recon_loss_workspace_bytes": (_z, [_i, _i]),
+    "dg_recon_loss_fwd": (_i, [_p, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "dg_recon_loss_bwd": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
+    "dg_recon_loss_fwd_g": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "dg_recon_loss_bwd_g": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p]),
     "dg_swd_max_row": (_i, []),
     "dg_swd_levels": (_i, [_i]),
     "dg_lap_pyramid_elems": (_z, [_i, _i]),

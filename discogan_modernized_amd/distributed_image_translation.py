@@ -9,6 +9,8 @@ buffer is all-reduced (sum, then divided by W inside the Adam kernel).  Rank 0 l
 
 ``--diffaug POLICY`` (image_translation.py): every rank draws its own transforms of its own discriminator inputs, keyed on
 (seed, rank, iteration, domain, role) -- the replicas see different augmentations of different batches, and the gradients are summed as usual.
+``--recon_loss KIND`` (image_translation.py): every rank measures the reconstruction terms of its own batch with the criterion; it has no
+state, so there is nothing to exchange beside the gradients.
 """
 from __future__ import annotations
 

@@ -381,6 +381,25 @@ class MSELossFn(Function):
         return dx, dt, None
 
 
+class ReconLossFn(Function):
+    """``w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ssim (1 - mean SSIM)`` of an image batch against data (ops.recon_loss_fwd);
+    ``w = (w_mse, w_l1, w_ssim)``; the gradient is taken with respect to ``x`` only."""
+
+    @_fwd
+    def forward(ctx, x, t, w, out=None):
+        xd, td = x.contiguous(), t.contiguous()
+        loss = ops.recon_loss_fwd(xd, td, w, out)
+        ctx.save_for_backward(xd, td)
+        ctx.w = tuple(w)
+        return loss
+
+    @_bwd
+    def backward(ctx, gout):
+        xd, td = ctx.saved_tensors
+        dx = ops.recon_loss_bwd(xd, td, ctx.w, gout.contiguous()) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None
+
+
 class BCELossFn(Function):
     """nn.BCELoss against a constant label tensor (image_translation.py:157-166)."""
 
@@ -707,6 +726,28 @@ class MSELossGroupFn(Function):
         sv = ctx.saved_tensors
         dxs = ops.mse_bwd_g(list(sv[:g]), list(sv[g:]), [go.contiguous() for go in gouts])
         return (None,) + tuple(dxs) + (None,) * (2 * g)
+
+
+class ReconLossGroupFn(Function):
+    """ReconLossFn of ``g`` (x, target) pairs under one weight triple; the losses land in ``outs``.  args: x_0.., t_0.., out_0.."""
+
+    @_fwd
+    def forward(ctx, g, w, *t):
+        xs, ts, outs = [v.contiguous() for v in t[:g]], [v.contiguous() for v in t[g:2 * g]], list(t[2 * g:3 * g])
+        ops.recon_loss_fwd_g(xs, ts, w, outs)
+        ctx.g, ctx.w = g, tuple(w)
+        ctx.save_for_backward(*xs, *ts)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @_bwd
+    def backward(ctx, *gouts):
+        g = ctx.g
+        if not _all_or_none(gouts, "ReconLossGroupFn"):
+            return (None,) * (2 + 3 * g)
+        sv = ctx.saved_tensors
+        dxs = ops.recon_loss_bwd_g(list(sv[:g]), list(sv[g:]), ctx.w, [go.contiguous() for go in gouts])
+        return (None, None) + tuple(dxs) + (None,) * (2 * g)
 
 
 class BCELossGroupFn(Function):

@@ -50,6 +50,12 @@ generator (Zhao et al. 2020, DiffAugment; on images in [0, 1]: brightness amplit
 (dg_diffaug_fwd / dg_diffaug_bwd) on records drawn on the device from (seed, rank, iteration, domain, role): graph replay and ``--resume``
 reproduce the run bitwise and nothing is saved.  It goes behind the pool exchange; generators, reconstructions, sample grids, evaluation
 and the EMA never see it.
+Reconstruction criterion: ``--recon_loss {mse,l1,ssim,l1_ssim}`` (default ``mse``, the reference's) chooses what the two cycle terms
+ABA against A and BAB against B are measured with: ``l1`` = mean |x - t| (CycleGAN), ``ssim`` = 1 - SSIM (the 11 x 11 Gaussian window,
+sigma 1.5, valid windows, that ``SSIM_ABA`` of the evaluation reports; needs ``--image_size >= 11``), ``l1_ssim`` = (1 - alpha) L1 +
+alpha (1 - SSIM) with ``--recon_ssim_alpha`` (default 0.84, Zhao et al. 2017).  One fused forward and one backward kernel per term
+(dg_recon_loss_fwd / dg_recon_loss_bwd) in the place of the MSE kernels: captured, replayed and resumed like them, nothing is saved, and
+the ``RECON:`` field of the log line prints the criterion's value.  With ``mse`` nothing changes.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -70,7 +76,7 @@ from pathlib import Path
 
 import torch
 
-from .trainer import DiscoGANTrainer, check_diffaug, check_image_pool
+from .trainer import DiscoGANTrainer, check_diffaug, check_image_pool, check_recon_loss
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -139,6 +145,12 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--diffaug", type=str, default="",
                    help="comma list of 'color', 'translation', 'cutout': differentiable augmentation (DiffAugment) of every discriminator "
                         "input, reals and fakes, on the device, keyed on (seed, rank, iteration); empty or 'none' = off")
+    p.add_argument("--recon_loss", type=str, default="mse", choices=["mse", "l1", "ssim", "l1_ssim"],
+                   help="criterion of the two reconstruction (cycle) terms: mse (the reference's nn.MSELoss), l1 (CycleGAN's), ssim "
+                        "(1 - SSIM, the 11 x 11 Gaussian window of the evaluation) or l1_ssim ((1 - alpha) L1 + alpha (1 - SSIM)); the "
+                        "SSIM kinds need --image_size >= 11")
+    p.add_argument("--recon_ssim_alpha", type=float, default=0.84,
+                   help="with --recon_loss l1_ssim: the weight alpha of the SSIM term, in (0, 1) (Zhao et al. 2017: 0.84)")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -355,8 +367,10 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     aug = augment_of(args, rank)                          # a mistyped --augment token or a scale below 1 raises before anything is built
     image_pool = check_image_pool(getattr(args, "image_pool", 0))           # likewise: a negative --image_pool
     diffaug = check_diffaug(getattr(args, "diffaug", ""))                   # likewise: an unknown --diffaug policy
+    recon_loss = getattr(args, "recon_loss", "mse")                         # likewise: an SSIM criterion on images under 11 pixels
+    recon_w = check_recon_loss(recon_loss, getattr(args, "recon_ssim_alpha", 0.84), args.image_size)
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
-    eval_swd = check_eval_swd(args)                                        # likewise: --eval_swd without --eval_interval
+    eval_swd = check_eval_swd(args)                                       # likewise: --eval_swd without --eval_interval
     if eval_interval > 0:
         from . import evaluate
         evaluate.check_size(args.image_size, swd=eval_swd)
@@ -390,6 +404,9 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
             from .diffaug import policy_names
             print(f"differentiable augmentation: {policy_names(diffaug)} on every discriminator input (reals and fakes, every step); "
                   "keyed on seed, rank and iteration; generators, reconstructions, samples and evaluation never see it", flush=True)
+        if recon_loss != "mse":
+            print(f"reconstruction loss: {recon_loss} = {recon_w[0]:g} MSE + {recon_w[1]:g} L1 + {recon_w[2]:g} (1 - SSIM) on both cycle "
+                  "terms (RECON: prints its value)", flush=True)
     # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
     # saving rank alone loads it, samples and evaluates
     split = None

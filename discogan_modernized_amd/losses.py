@@ -20,6 +20,54 @@ class MSELoss(nn.Module):
         return F.MSELossFn.apply(input, target)
 
 
+RECON_KINDS = ("mse", "l1", "ssim", "l1_ssim")
+
+
+def recon_weights(kind, alpha=0.84):
+    """The weights ``(w_mse, w_l1, w_ssim)`` of a reconstruction criterion (``dg_recon_loss_fwd``): ``mse`` -> (1, 0, 0), ``l1`` ->
+    (0, 1, 0), ``ssim`` -> (0, 0, 1) (the loss is 1 - SSIM), ``l1_ssim`` -> (0, 1 - alpha, alpha) (Zhao et al. 2017: alpha = 0.84)."""
+    if kind == "mse":
+        return (1.0, 0.0, 0.0)
+    if kind == "l1":
+        return (0.0, 1.0, 0.0)
+    if kind == "ssim":
+        return (0.0, 0.0, 1.0)
+    if kind == "l1_ssim":
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"recon_ssim_alpha must be in (0, 1), got {alpha}")
+        return (0.0, 1.0 - alpha, alpha)
+    raise ValueError(f"unknown reconstruction loss {kind!r} (one of {', '.join(RECON_KINDS)})")
+
+
+class ReconLoss(nn.Module):
+    """``w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ssim (1 - mean SSIM)`` of an image batch ``input`` [n,3,S,S] against the data
+    ``target`` (no gradient flows into it), weights by ``recon_weights(kind, alpha)``.  SSIM: 11 x 11 Gaussian window of sigma 1.5,
+    valid windows, data range 1 -- the quantity ``ops.image_metrics`` reports."""
+
+    def __init__(self, kind="l1_ssim", alpha=0.84):
+        super().__init__()
+        self.kind = kind
+        self.weights = recon_weights(kind, alpha)
+
+    def forward(self, input, target):
+        return F.ReconLossFn.apply(input, target, self.weights)
+
+
+class L1Loss(ReconLoss):
+    """nn.L1Loss() (mean reduction) of an image batch against data."""
+
+    def __init__(self):
+        super().__init__("l1")
+
+
+class SSIMLoss(ReconLoss):
+    """1 - mean SSIM of an image batch against data."""
+
+    def __init__(self):
+        super().__init__("ssim")
+
+
 class BCELoss(nn.Module):
     """nn.BCELoss() (mean reduction, log clamped at -100).  ``target`` is a tensor of the input's size, as in the
     reference (image_translation.py:157-166), or a Python scalar label (1.0 / 0.0), which skips materialising it."""

@@ -1397,6 +1397,53 @@ def mse_bwd(x, t, gout):
     return dx
 
 
+# Reconstruction criterion (dg_recon_loss_*): w = (w_mse, w_l1, w_ssim) host floats; x the reconstruction, t the real image (data)
+def _recon_args(who, xs, ts, w):
+    """The argument checks of the recon_loss_* wrappers.  Returns (n, S, the weights as a C float[3])."""
+    import ctypes as C
+    import math
+    w = tuple(float(v) for v in w)
+    if len(w) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in w) or not any(v > 0.0 for v in w):
+        raise _lib.DiscoganHipError(f"{who}: the weights (w_mse, w_l1, w_ssim) must be three finite numbers >= 0, not all 0, got {w}")
+    _check_dev(*xs, *ts)
+    x0 = xs[0]
+    for x, t in zip(xs, ts):
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise _lib.DiscoganHipError(f"{who} needs [n,3,S,S] image batches, got {tuple(x.shape)}")
+        if tuple(t.shape) != tuple(x.shape) or tuple(x.shape) != tuple(x0.shape) or t.device != x0.device or x.device != x0.device:
+            raise _lib.DiscoganHipError(f"{who}: input and target must have one shape on one device, got {tuple(x.shape)} and {tuple(t.shape)}")
+        if not (x.is_contiguous() and t.is_contiguous()):
+            raise _lib.DiscoganHipError(f"{who} needs contiguous NCHW batches")
+        if t.requires_grad:
+            raise _lib.DiscoganHipError(f"{who}: the target is data -- no gradient with respect to it exists; detach it")
+    n, S = int(x0.shape[0]), int(x0.shape[3])
+    if n < 1 or S < 1:
+        raise _lib.DiscoganHipError(f"{who}: empty batch {tuple(x0.shape)}")
+    if w[2] > 0.0 and S < 11:
+        raise _lib.DiscoganHipError(f"{who}: the SSIM term needs S >= 11 pixels (the 11 x 11 window), got S={S}")
+    return n, S, (C.c_float * 3)(*w)
+
+
+def recon_loss_fwd(x, t, w, out=None):
+    """loss = w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ssim (1 - mean SSIM) of two float32 NCHW batches [n,3,S,S], a device scalar
+    (``out``: the slot to write it into)."""
+    n, S, cw = _recon_args("recon_loss_fwd", [x], [t], w)
+    loss = out if out is not None else torch.empty((), device=x.device, dtype=torch.float32)
+    L = _lib.load()
+    ws, wsb = _ws(L.dg_recon_loss_workspace_bytes(n, S), x.device)
+    _lib.check(L.dg_recon_loss_fwd(_ptr(x), _ptr(t), n, S, cw, _ptr(loss), _ptr(ws), wsb, _stream()), "dg_recon_loss_fwd")
+    return loss
+
+
+def recon_loss_bwd(x, t, w, gout):
+    """d loss / d x times the device scalar ``gout`` (one pass, overwriting)."""
+    n, S, cw = _recon_args("recon_loss_bwd", [x], [t], w)
+    _check_dev(gout)
+    dx = torch.empty_like(x)
+    _lib.check(_lib.load().dg_recon_loss_bwd(_ptr(x), _ptr(t), n, S, cw, _ptr(gout), _ptr(dx), _stream()), "dg_recon_loss_bwd")
+    return dx
+
+
 def bce_fwd(p, label, out=None):
     _check_dev(p)
     p = p.contiguous()
@@ -1800,6 +1847,22 @@ def mse_fwd_g(xs, ts, outs):
 def mse_bwd_g(xs, ts, gouts):
     dxs = [_dense_like(x) for x in xs]
     _lib.check(_lib.load().dg_mse_bwd_g(len(xs), _tab(xs), _tab(ts), xs[0].numel(), _tab(gouts), _tab(dxs), _stream()), "dg_mse_bwd_g")
+    return dxs
+
+
+def recon_loss_fwd_g(xs, ts, w, outs):
+    n, S, cw = _recon_args("recon_loss_fwd_g", xs, ts, w)
+    L = _lib.load()
+    wsl, wsb = _ws_g(L.dg_recon_loss_workspace_bytes(n, S), len(xs), xs[0].device)
+    _lib.check(L.dg_recon_loss_fwd_g(len(xs), _tab(xs), _tab(ts), n, S, cw, _tab(outs), _tab(wsl), wsb, _stream()), "dg_recon_loss_fwd_g")
+    return outs
+
+
+def recon_loss_bwd_g(xs, ts, w, gouts):
+    n, S, cw = _recon_args("recon_loss_bwd_g", xs, ts, w)
+    _check_dev(*gouts)
+    dxs = [torch.empty_like(x) for x in xs]
+    _lib.check(_lib.load().dg_recon_loss_bwd_g(len(xs), _tab(xs), _tab(ts), n, S, cw, _tab(gouts), _tab(dxs), _stream()), "dg_recon_loss_bwd_g")
     return dxs
 
 

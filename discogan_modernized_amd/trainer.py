@@ -46,7 +46,7 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
                 ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
-                diffaug="")
+                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84)
 
 
 def check_ema_decay(decay):
@@ -77,6 +77,16 @@ def check_diffaug(policy):
     """``diffaug``: "" (or "none") = off, else a comma-separated subset of color, translation, cutout (diffaug.parse_policy).  Returns the
     DG_DIFFAUG_* flags; raises ValueError on an unknown name."""
     return parse_policy(policy)
+
+
+def check_recon_loss(kind, alpha, image_size):
+    """``recon_loss``: the criterion of the two reconstruction (cycle) terms -- "mse" (the reference's nn.MSELoss), "l1", "ssim" (1 - SSIM)
+    or "l1_ssim" ((1 - alpha) L1 + alpha (1 - SSIM), ``recon_ssim_alpha`` in (0, 1), read by that kind only).  The SSIM kinds need images
+    of at least 11 pixels (the 11 x 11 window).  Returns the weights (w_mse, w_l1, w_ssim) (losses.recon_weights)."""
+    w = L.recon_weights(kind, alpha)
+    if w[2] > 0.0 and image_size < 11:
+        raise ValueError(f"recon_loss {kind!r} needs image_size >= 11 (the 11 x 11 SSIM window), got {image_size}")
+    return w
 
 
 def format_grad_suffix(dis, gen):
@@ -119,6 +129,8 @@ class DiscoGANTrainer:
                 setattr(self.args, k, v)
         ema_decay = check_ema_decay(self.args.ema_decay)
         grad_clip = check_grad_clip(getattr(self.args, "grad_clip", 0.0))
+        self.recon_loss = self.args.recon_loss
+        self.recon_w = check_recon_loss(self.recon_loss, self.args.recon_ssim_alpha, image_size)
         guard, log_norm = bool(getattr(self.args, "nonfinite_guard", False)), bool(getattr(self.args, "log_grad_norm", False))
         self.device = torch.device(device)
         self.image_size = image_size
@@ -144,7 +156,10 @@ class DiscoGANTrainer:
         self.discriminator_B = Discriminator(image_size=image_size).to(self.device)
         self.nets = dict(gen_A=self.generator_A, gen_B=self.generator_B,
                          dis_A=self.discriminator_A, dis_B=self.discriminator_B)
-        self.recon_criterion = L.MSELoss()
+        # The criterion of the two reconstruction terms (slots 0 and 1 of the loss vector).  "mse": the reference's, through MSELossFn /
+        # MSELossGroupFn as ever.  Any other kind: one fused kernel pair per term (functional.ReconLossFn / ReconLossGroupFn,
+        # csrc/recon.hip) in the same places on the same streams, capturable, stateless -- nothing to checkpoint or to exchange.
+        self.recon_criterion = L.MSELoss() if self.recon_loss == "mse" else L.ReconLoss(self.recon_loss, self.args.recon_ssim_alpha)
         self.gan_criterion = L.BCELoss()
         self.feat_criterion = L.HingeEmbeddingLoss()
         a = self.args
@@ -394,7 +409,7 @@ class DiscoGANTrainer:
         with on_side():
             if want_recon:
                 with gen_ctx():
-                    terms[0] = F_.MSELossFn.apply(ABA, A, sl[0])
+                    terms[0] = self._recon_term(ABA, A, sl[0])
             else:
                 terms[0] = sl[0]
             bce(A_dis_real, 1.0, 2); bce(A_dis_fake, 0.0, 3); bce(A_dis_fake, 1.0, 4)
@@ -402,7 +417,7 @@ class DiscoGANTrainer:
                 terms[8 + l] = F_.FeatureMatchFn.apply(r, f, sl[8 + l])
         if want_recon:
             with gen_ctx():
-                terms[1] = F_.MSELossFn.apply(BAB, B, sl[1])
+                terms[1] = self._recon_term(BAB, B, sl[1])
         else:
             terms[1] = sl[1]
         bce(B_dis_real, 1.0, 5); bce(B_dis_fake, 0.0, 6); bce(B_dis_fake, 1.0, 7)
@@ -430,6 +445,12 @@ class DiscoGANTrainer:
             dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
             A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
             A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, dis_inputs=dis_inputs)
+
+    def _recon_term(self, x, t, slot):
+        """One reconstruction term into its slot of the loss vector: the reference's MSE, or the criterion of ``recon_loss``."""
+        if self.recon_loss == "mse":
+            return F_.MSELossFn.apply(x, t, slot)
+        return F_.ReconLossFn.apply(x, t, self.recon_w, slot)
 
     def _two_chain_forward(self, A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side):
         """The symmetric two-chain order: G_A(B) | G_B(A), G_A(AB) | G_B(BA), D_A(A) | D_B(B), D_A(BA) | D_B(AB), each pair in lock step.
@@ -544,7 +565,10 @@ class DiscoGANTrainer:
         if want_recon:
             with gen_ctx():
                 ABA, BAB = group_generators([gA, gB], [AB, BA])
-                terms[0], terms[1] = F_.MSELossGroupFn.apply(2, ABA, BAB, A, B, sl[0], sl[1])
+                if self.recon_loss == "mse":
+                    terms[0], terms[1] = F_.MSELossGroupFn.apply(2, ABA, BAB, A, B, sl[0], sl[1])
+                else:
+                    terms[0], terms[1] = F_.ReconLossGroupFn.apply(2, self.recon_w, ABA, BAB, A, B, sl[0], sl[1])
         else:
             lv[:2].fill_(float("nan"))
             terms[0], terms[1] = sl[0], sl[1]

@@ -560,6 +560,34 @@ int dg_sample_grid_u8(const float* const* src, int cols, int rows, int S, int ga
    the other pairs (a NaN / inf in pair i reaches row i only). */
 size_t dg_image_metrics_workspace_bytes(int n, int S);
 int dg_image_metrics(const float* x, const float* y, int n, int S, float* out /* [n][3] */, void* ws, size_t ws_bytes, dg_stream_t s);
+/* ---- reconstruction loss (trainer.py --recon_loss; csrc/recon.hip): the trainable form of the numbers above.  x (the reconstruction)
+   and t (the real image): float [n][3][S][S] (NCHW, any 4-byte alignment); w: three HOST floats (w_mse, w_l1, w_ssim), finite, >= 0,
+   not all 0.
+     loss = w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ssim (1 - mean over the n 3 (S - 10)^2 valid windows of SSIM)
+   SSIM is exactly the quantity of dg_image_metrics (same window, constants, data range 1); the mean over all windows equals the mean of
+   the per-image values.  S >= 11 when w_ssim > 0; a term of weight 0 is not evaluated (w_ssim == 0: a plain streaming pass, any S >= 1).
+   loss: one device float per problem, written once (fp32 inside a thread, fp64 from the wave sum on, fixed order: bitwise repeatable).
+   ws: dg_recon_loss_workspace_bytes(n, S) bytes per problem, 8-byte aligned.
+   bwd: the gradient with respect to x only (t is data), gout a device scalar:
+     dx = gout ( w_mse 2 (x - t) / N + w_l1 sign(x - t) / N - w_ssim d(mean SSIM) / dx ),  N = 3 n S^2,  sign(0) = 0
+   in one pass that overwrites dx; the combination is formed in double and rounded once.  With A1 = 2 mx my + C1, A2 = 2 sxy + C2,
+   B1 = mx^2 + my^2 + C1, B2 = sx2 + sy2 + C2 per window p:
+     dmu = 2 my A2 / (B1 B2) - 2 mx A1 A2 / (B1^2 B2),  dsig = -A1 A2 / (B1 B2^2),  dc = 2 A1 / (B1 B2)
+     a = dmu - 2 mx dsig - my dc,  b = 2 dsig,  c = dc
+     d(mean SSIM) / dx(q) = [ (w * a)(q) + x(q) (w * b)(q) + t(q) (w * c)(q) ] / (3 n (S - 10)^2)
+   where (w * f)(q) sums w(q - p) f(p) over the valid windows p that contain pixel q.  The maps a, b, c are recomputed by the backward
+   (nothing is saved by the forward); each output pixel gathers its windows: no atomics, two calls give the same bits, and a NaN / inf in
+   one image stays in that image's rows of dx.  16-byte loads when S % 4 == 0 and every pointer is 16-byte aligned, scalar loads
+   otherwise.  No host synchronisation, no allocation: capturable.  The *_g forms run `groups` (1..DG_MAX_GROUPS) problems of one (n, S, w)
+   in one launch per kernel, bitwise the single calls. */
+size_t dg_recon_loss_workspace_bytes(int n, int S);
+int dg_recon_loss_fwd(const float* x, const float* t, int n, int S, const float* w /* host [3] */, float* loss, void* ws, size_t ws_bytes,
+                      dg_stream_t s);
+int dg_recon_loss_bwd(const float* x, const float* t, int n, int S, const float* w /* host [3] */, const float* gout, float* dx, dg_stream_t s);
+int dg_recon_loss_fwd_g(int groups, const float* const* x, const float* const* t, int n, int S, const float* w /* host [3] */,
+                        float* const* loss, void* const* ws, size_t ws_bytes, dg_stream_t s);
+int dg_recon_loss_bwd_g(int groups, const float* const* x, const float* const* t, int n, int S, const float* w /* host [3] */,
+                        const float* const* gout, float* const* dx, dg_stream_t s);
 /* ---- sliced Wasserstein distance on Laplacian-pyramid patches (evaluate.py; Karras et al., ICLR 2018, "Progressive Growing of GANs",
  * section 5): a score for UNPAIRED sets, no network.  x, y: float [n][3][S][S] (NCHW), values as they are (no clamp), S >= 16.
  *
