@@ -35,8 +35,9 @@ import torch
 from . import dp
 from . import functional as F_
 from . import losses as L
+from . import ops
 from . import optim
-from .model import Discriminator, Generator
+from .model import Discriminator, Generator, group_discriminators, group_generators
 from .pool import ImagePool
 from .diffaug import DiffAugment, apply_group, parse_policy
 
@@ -47,6 +48,30 @@ DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
                 ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
                 diffaug="", recon_loss="mse", recon_ssim_alpha=0.84)
+
+# The loss vector every term of an iteration is written into and dg_loss_mix_fwd / _bwd read (the layout is defined by the comment
+# above dg_loss_mix_fwd in include/discogan_hip.h): the two reconstruction terms, per discriminator BCE(real, 1), BCE(fake, 0),
+# BCE(fake, 1), then the nfm feature-matching layers of D_A from FM0 and those of D_B from FM0 + nfm.
+RECON_A, RECON_B = 0, 1
+A_REAL1, A_FAKE0, A_FAKE1, B_REAL1, B_FAKE0, B_FAKE1 = 2, 3, 4, 5, 6, 7
+FM0 = 8
+MIX_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")     # its out8
+WHICH_GEN, WHICH_DIS = 6, 7                # dg_loss_mix_bwd's ``which``: backward of gen_loss (out8[6]) / of dis_loss (out8[7])
+ARCH_CODES = {"discogan": 0, "recongan": 1, "gan": 2}
+PREC_OF = {"f32": ops.PREC_F32, "bf16": ops.PREC_BF16, "f32x3": ops.PREC_F32X3}
+
+
+def loss_slots(model_arch, dstep, nfm):
+    """``(arch_code, which, idx)`` of a D-step / G-step: the library's code of ``model_arch``, which mixed loss is differentiated, and the
+    slots of the loss vector that carry gradient then (image_translation.py:374-382): discogan both sides; recongan D_B | recon_A +
+    G_B's GAN and feature-matching terms; gan D_B | G_B's.  Raises ValueError for an unknown ``model_arch``."""
+    arch = ARCH_CODES.get(model_arch)
+    if arch is None:
+        raise ValueError(f"unknown model_arch {model_arch}")
+    if dstep:
+        return arch, WHICH_DIS, ((A_REAL1, A_FAKE0, B_REAL1, B_FAKE0) if arch == 0 else (B_REAL1, B_FAKE0))
+    fmA, fmB = tuple(range(FM0, FM0 + nfm)), tuple(range(FM0 + nfm, FM0 + 2 * nfm))
+    return arch, WHICH_GEN, ((RECON_A, RECON_B, A_FAKE1, B_FAKE1) + fmA + fmB, (RECON_A, B_FAKE1) + fmB, (B_FAKE1,) + fmB)[arch]
 
 
 def check_ema_decay(decay):
@@ -128,14 +153,17 @@ class DiscoGANTrainer:
             if not hasattr(self.args, k):
                 setattr(self.args, k, v)
         ema_decay = check_ema_decay(self.args.ema_decay)
-        grad_clip = check_grad_clip(getattr(self.args, "grad_clip", 0.0))
+        grad_clip = check_grad_clip(self.args.grad_clip)
         self.recon_loss = self.args.recon_loss
         self.recon_w = check_recon_loss(self.recon_loss, self.args.recon_ssim_alpha, image_size)
-        guard, log_norm = bool(getattr(self.args, "nonfinite_guard", False)), bool(getattr(self.args, "log_grad_norm", False))
+        guard, log_norm = bool(self.args.nonfinite_guard), bool(self.args.log_grad_norm)
+        loss_slots(self.args.model_arch, True, 0)        # an unknown model_arch is refused here, before anything is allocated
         self.device = torch.device(device)
         self.image_size = image_size
         self.pg = process_group
         self.world_size = torch.distributed.get_world_size(process_group) if process_group is not None else 1
+        rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+        stream_seed = 0 if seed is None else seed         # with the rank: the key of the pool's and DiffAugment's device-side draws
         # exchange transport (dp.ExchangeGroup): "capi" = the library's own RCCL communicator (collectives on the
         # caller's stream), "c10d" = torch.distributed, "auto" = capi under backend nccl.  comm="capi" may be forced at
         # world size 1 (tests: the whole exchange path runs against a 1-rank RCCL communicator).
@@ -189,25 +217,21 @@ class DiscoGANTrainer:
         # (seed, data-parallel rank, iteration, domain): every rank pools its own fakes, and a resumed run continues the sequence.  Each
         # exchange is ONE launch on the stream of the discriminator pass that consumes it, reading only fixed device addresses, so it is
         # captured like any other kernel.  G-steps, the reconstruction passes and sampling never see a pool.
-        P = check_image_pool(getattr(self.args, "image_pool", 0))
+        P = check_image_pool(self.args.image_pool)
         self.pool_BA = self.pool_AB = None
         if P > 0:
-            rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
-            pseed = 0 if seed is None else seed
-            self.pool_BA = ImagePool(P, image_size, pseed, rank, 0, device=self.device)      # domain A: the fakes D_A sees
-            self.pool_AB = ImagePool(P, image_size, pseed, rank, 1, device=self.device)      # domain B: the fakes D_B sees
+            self.pool_BA = ImagePool(P, image_size, stream_seed, rank, 0, device=self.device)      # domain A: the fakes D_A sees
+            self.pool_AB = ImagePool(P, image_size, stream_seed, rank, 1, device=self.device)      # domain B: the fakes D_B sees
         # Differentiable augmentation (diffaug = a policy; diffaug.DiffAugment): everything a discriminator reads -- reals and fakes, in
         # D-steps and G-steps -- goes through one random transform per sample first, behind the pool exchange and on the consumer's
         # stream; in a G-step the gradient flows back through it into the generator.  Four tables (A real, A fake, B real, B fake), drawn
         # on the device ahead of EVERY iteration's dispatch, outside any capture (_draw_ahead), keyed on (seed, data-parallel rank,
         # iteration, domain, role): nothing to checkpoint.  Generators, reconstruction passes, sampling, evaluation and the EMA never
         # see the transform.
-        self.diffaug_flags = check_diffaug(getattr(self.args, "diffaug", ""))
+        self.diffaug_flags = check_diffaug(self.args.diffaug)
         self.aug_A = self.aug_BA = self.aug_B = self.aug_AB = None
         if self.diffaug_flags:
-            rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
-            dseed = 0 if seed is None else seed
-            mk = lambda domain, role: DiffAugment(self.diffaug_flags, image_size, dseed, rank, domain, role, device=self.device)  # noqa: E731
+            mk = lambda domain, role: DiffAugment(self.diffaug_flags, image_size, stream_seed, rank, domain, role, device=self.device)  # noqa: E731
             self.aug_A, self.aug_BA, self.aug_B, self.aug_AB = mk(0, 0), mk(0, 1), mk(1, 0), mk(1, 1)
         self._graphs = {}
         self._static = None
@@ -256,9 +280,8 @@ class DiscoGANTrainer:
         # The arithmetic and operand forms of THIS trainer's calls: an ops.Context handed to every op with the call (the conv
         # arithmetic is an argument of the C ABI: DG_PREC_*), never a process-wide switch -- two trainers with different arithmetic
         # can be interleaved call by call (tests/test_group_gpu.py::test_interleaved_trainers_with_different_arithmetic).
-        from . import ops as _ops
-        self.ctx = _ops.Context(prec={"f32": _ops.PREC_F32, "bf16": _ops.PREC_BF16, "f32x3": _ops.PREC_F32X3}[mfma_dtype],
-                                shadow=self.bf16_shadow, act16=self.act_dtype == "bf16", x3=self.x3_planes, group_plan=group_plan)
+        self.ctx = ops.Context(group_plan=group_plan)
+        self._refresh_ctx()
         # Grouped launches (round 4): the A-side / B-side pass of every pair of the iteration (image_translation.py:342-346,353-361)
         # goes out as ONE launch per kernel, and in a D-step each discriminator layer's real and fake pass of both sides as one
         # launch over four problems (same weights fetched once per launch; BatchNorm statistics / feature maps per pass).  Bitwise
@@ -356,20 +379,14 @@ class DiscoGANTrainer:
 
     def forward_losses(self, A, B, iters, need_losses=True):
         """image_translation.py:342-382.  need_losses=False (D-steps only): the reconstruction passes ABA / BAB and their
-        MSE terms feed nothing but the log line in a D-step, so they are not computed (recon_loss_* read NaN)."""
+        terms feed nothing but the log line in a D-step, so they are not computed (recon_loss_* read NaN)."""
         if self.group_launch and (not self._group_auto or A.shape[0] * A.shape[2] * A.shape[3] <= self.group_max_pixels):
             return self._forward_losses_grouped(A, B, iters, need_losses)
-        a = self.args
         dstep = self.is_dis_step(iters)
-        skip = self.skip_dead_work
-        gen_ctx = torch.no_grad if (skip and dstep) else torch.enable_grad
-        main = torch.cuda.current_stream(self.device)
-        side = self.side_stream if self.two_streams else main
-        on_side = (lambda: torch.cuda.stream(side)) if self.two_streams else contextlib.nullcontext
-        # loss vector (layout: dg_loss_mix_fwd): allocated BEFORE the fork so that the side stream's writes are
-        # ordered after whatever used this block on the main stream
-        nfm = self.discriminator_A.n_stages - 1
-        lv = torch.empty(8 + 2 * nfm, device=self.device, dtype=torch.float32)
+        gen_ctx = torch.no_grad if (self.skip_dead_work and dstep) else torch.enable_grad
+        main, side, on_side = self._streams()
+        # allocated BEFORE the fork so that the side stream's writes are ordered after whatever used this block on the main stream
+        nfm, lv, sl, terms = self._loss_vector()
         if self.two_streams:
             side.wait_stream(main)
             # tensors that cross streams tell the caching allocator (a block is otherwise reusable on its
@@ -396,68 +413,12 @@ class DiscoGANTrainer:
                         rb = e.value
             return ra, rb
 
-        want_recon = need_losses or not (dstep and skip)
-        (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
-         seen, dis_inputs) = self._two_chain_forward(A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side)
-        assert nfm == len(A_feats_real)
-        sl = [lv[i] for i in range(8 + 2 * nfm)]
-        terms = {}
-
-        def bce(p, label, k):
-            terms[k] = F_.BCELossFn.apply(p.reshape(p.size(0), -1), label, sl[k])
-
-        with on_side():
-            if want_recon:
-                with gen_ctx():
-                    terms[0] = self._recon_term(ABA, A, sl[0])
-            else:
-                terms[0] = sl[0]
-            bce(A_dis_real, 1.0, 2); bce(A_dis_fake, 0.0, 3); bce(A_dis_fake, 1.0, 4)
-            for l, (r, f) in enumerate(zip(A_feats_real, A_feats_fake)):
-                terms[8 + l] = F_.FeatureMatchFn.apply(r, f, sl[8 + l])
-        if want_recon:
-            with gen_ctx():
-                terms[1] = self._recon_term(BAB, B, sl[1])
-        else:
-            terms[1] = sl[1]
-        bce(B_dis_real, 1.0, 5); bce(B_dis_fake, 0.0, 6); bce(B_dis_fake, 1.0, 7)
-        for l, (r, f) in enumerate(zip(B_feats_real, B_feats_fake)):
-            terms[8 + nfm + l] = F_.FeatureMatchFn.apply(r, f, sl[8 + nfm + l])
-        if self.two_streams:
-            main.wait_stream(side)
-        rate = self.rate(iters)
-        arch = {"discogan": 0, "recongan": 1, "gan": 2}.get(a.model_arch)
-        if arch is None:
-            raise ValueError(f"unknown model_arch {a.model_arch}")
-        fmA, fmB = list(range(8, 8 + nfm)), list(range(8 + nfm, 8 + 2 * nfm))
-        if dstep:
-            which, idx = 7, ([2, 3, 5, 6] if arch == 0 else [5, 6])
-        else:
-            which = 6
-            idx = ([0, 1, 4, 7] + fmA + fmB) if arch == 0 else (([0, 7] if arch == 1 else [7]) + fmB)
-        idx = tuple(idx)
-        (gen_loss_A, gen_loss_B, fm_loss_A, fm_loss_B, dis_loss_A, dis_loss_B, gen_loss, dis_loss) = \
-            F_.LossMixFn.apply(lv, nfm, rate, arch, which, idx, *[terms[i] for i in idx])
-        recon_loss_A, recon_loss_B = terms[0], terms[1]
-        return IterationOutputs(
-            gen_loss=gen_loss, dis_loss=dis_loss, gen_loss_A=gen_loss_A, gen_loss_B=gen_loss_B,
-            fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=recon_loss_A, recon_loss_B=recon_loss_B,
-            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
-            A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
-            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, dis_inputs=dis_inputs)
-
-    def _recon_term(self, x, t, slot):
-        """One reconstruction term into its slot of the loss vector: the reference's MSE, or the criterion of ``recon_loss``."""
-        if self.recon_loss == "mse":
-            return F_.MSELossFn.apply(x, t, slot)
-        return F_.ReconLossFn.apply(x, t, self.recon_w, slot)
-
-    def _two_chain_forward(self, A, B, lv, pair, gen_ctx, main, side, want_recon, dstep, on_side):
-        """The symmetric two-chain order: G_A(B) | G_B(A), G_A(AB) | G_B(BA), D_A(A) | D_B(B), D_A(BA) | D_B(AB), each pair in lock step.
-        (Round 4 tried a DEPHASED order -- side: D_A(A), G_A(B), G_A(AB), D_A(BA); main: G_B(A), D_B(B), G_B(BA), D_B(AB) -- so that one
-        chain's HBM-bound BatchNorm kernels would meet the other chain's conv kernels instead of its BatchNorm kernels: bitwise
-        neutral, and no faster: 295.0 / 293.9 -> 294.5 / 294.8 images/s (f32x3), 1014.9 -> 1002.8 (bf16), 194.2 -> 192.9 (f32) at
-        512 px / batch 32, same box, alternating, profiles/r04_ab_dephased_chain_order.txt.  Removed.)"""
+        want_recon = need_losses or not (dstep and self.skip_dead_work)
+        # The symmetric two-chain order: G_A(B) | G_B(A), G_A(AB) | G_B(BA), D_A(A) | D_B(B), D_A(BA) | D_B(AB), each pair in lock step.
+        # (Round 4 tried a DEPHASED order -- side: D_A(A), G_A(B), G_A(AB), D_A(BA); main: G_B(A), D_B(B), G_B(BA), D_B(AB) -- so that one
+        # chain's HBM-bound BatchNorm kernels would meet the other chain's conv kernels instead of its BatchNorm kernels: bitwise
+        # neutral, and no faster: 295.0 / 293.9 -> 294.5 / 294.8 images/s (f32x3), 1014.9 -> 1002.8 (bf16), 194.2 -> 192.9 (f32) at
+        # 512 px / batch 32, same box, alternating, profiles/r04_ab_dephased_chain_order.txt.  Removed.)
         # stage 1: the two first-stage translations are independent.  Their backward passes are the LAST ones to
         # touch each generator's parameters (autograd replays in reverse), which the bucketed exchange keys on.
         F_.FINAL_PASS = True
@@ -483,11 +444,7 @@ class DiscoGANTrainer:
             ev_ba.record(side)
             side.wait_event(ev_ab)                           # G_A(AB) needs AB
             main.wait_event(ev_ba)                           # G_B(BA) needs BA
-        if self._ev_dis_ready is not None:                   # D parameters updated on the comm stream
-            main.wait_event(self._ev_dis_ready)
-            if self.two_streams:
-                side.wait_event(self._ev_dis_ready)
-            self._ev_dis_ready = None
+        self._wait_dis_ready(*((main, side) if self.two_streams else (main,)))       # D parameters updated on the comm stream
         # stage 2 + discriminators.  Every loss term is written into its slot of one device vector (layout:
         # dg_loss_mix_fwd); the mix and its gradient seeds are one launch each instead of ~45 scalar kernels.
         ABA = BAB = None
@@ -495,7 +452,7 @@ class DiscoGANTrainer:
             with gen_ctx():
                 ABA, BAB = pair(self.generator_A.forward_steps(AB), self.generator_B.forward_steps(BA))
         else:
-            lv[:2].fill_(float("nan"))
+            self._no_recon(lv, sl, terms)
         A_in, B_in, dis_inputs = A, B, None
         if self.aug_A is not None:                           # the reals as the discriminators see them (no gradient is wanted of them)
             with torch.no_grad():
@@ -506,12 +463,7 @@ class DiscoGANTrainer:
             self.discriminator_A.forward_steps(A_in), self.discriminator_B.forward_steps(B_in))
         # the fakes the discriminators see: in a D-step with a history pool the exchanged batches, each on its consumer's stream (BA was
         # produced on `side`, where D_A runs; AB on `main`, where D_B runs: no new join)
-        BA_seen, AB_seen, seen = BA, AB, None
-        if dstep and self.pool_BA is not None:
-            with on_side():
-                BA_seen = self.pool_BA.exchange(BA)
-            AB_seen = self.pool_AB.exchange(AB)
-            seen = dict(BA=BA_seen, AB=AB_seen)
+        BA_seen, AB_seen, seen = self._pooled_fakes(dstep, BA, AB, on_side)
         BA_in, AB_in = BA_seen, AB_seen
         if self.aug_A is not None:                           # behind the exchange, each on its consumer's stream; differentiable
             with on_side():
@@ -520,26 +472,112 @@ class DiscoGANTrainer:
             dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
         (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = pair(
             self.discriminator_A.forward_steps(BA_in), self.discriminator_B.forward_steps(AB_in))
-        return (BA, AB, ABA, BAB, A_dis_real, A_feats_real, B_dis_real, B_feats_real, A_dis_fake, A_feats_fake, B_dis_fake, B_feats_fake,
-                seen, dis_inputs)
+        assert nfm == len(A_feats_real)
+
+        def bce(p, label, k):
+            terms[k] = F_.BCELossFn.apply(p.reshape(p.size(0), -1), label, sl[k])
+
+        with on_side():
+            if want_recon:
+                with gen_ctx():
+                    terms[RECON_A], = self._recon_terms([ABA], [A], [sl[RECON_A]])
+            bce(A_dis_real, 1.0, A_REAL1); bce(A_dis_fake, 0.0, A_FAKE0); bce(A_dis_fake, 1.0, A_FAKE1)
+            for l, (r, f) in enumerate(zip(A_feats_real, A_feats_fake)):
+                terms[FM0 + l] = F_.FeatureMatchFn.apply(r, f, sl[FM0 + l])
+        if want_recon:
+            with gen_ctx():
+                terms[RECON_B], = self._recon_terms([BAB], [B], [sl[RECON_B]])
+        bce(B_dis_real, 1.0, B_REAL1); bce(B_dis_fake, 0.0, B_FAKE0); bce(B_dis_fake, 1.0, B_FAKE1)
+        for l, (r, f) in enumerate(zip(B_feats_real, B_feats_fake)):
+            terms[FM0 + nfm + l] = F_.FeatureMatchFn.apply(r, f, sl[FM0 + nfm + l])
+        if self.two_streams:
+            main.wait_stream(side)
+        return self._mix(lv, terms, iters, dstep, nfm, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
+                         A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
+                         A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, dis_inputs=dis_inputs)
+
+    # ---- what the two schedules (two-chain above, grouped below) share: everything but the order of dispatch ----------------------
+    def _streams(self):
+        """(main, side, on_side): the current stream, the A-side chain's stream (two_streams=False: main) and the context that issues on it."""
+        main = torch.cuda.current_stream(self.device)
+        if not self.two_streams:
+            return main, main, contextlib.nullcontext
+        return main, self.side_stream, lambda: torch.cuda.stream(self.side_stream)
+
+    def _wait_dis_ready(self, *streams, keep=False):
+        """The discriminators' all-reduce + Adam of the last D-step may still run on the communication stream (``_ev_dis_ready``): the
+        given streams wait for it, and the event is dropped unless ``keep`` (a later reader on another stream has to wait as well)."""
+        if self._ev_dis_ready is not None:
+            for s in streams:
+                s.wait_event(self._ev_dis_ready)
+            if not keep:
+                self._ev_dis_ready = None
+
+    @contextlib.contextmanager
+    def _on_comm_behind(self, stream):
+        """Hand-over to the communication stream: what is issued inside runs there, behind everything queued on ``stream`` so far."""
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self.comm_stream.wait_event(ev)
+        with torch.cuda.stream(self.comm_stream):
+            yield
+
+    def _refresh_ctx(self):
+        """``self.ctx`` from the trainer's CURRENT arithmetic attributes (they may have been switched between iterations: tests run one
+        trainer in several arithmetics), with no derived operand form of an earlier pass left in it."""
+        self.ctx.prec = PREC_OF[self.mfma_dtype]
+        self.ctx.shadow, self.ctx.act16, self.ctx.x3 = bool(self.bf16_shadow), self.act_dtype == "bf16", bool(self.x3_planes)
+        self.ctx.clear()
+
+    def _loss_vector(self):
+        """(nfm, lv, sl, terms): the feature-matching layers per discriminator, the iteration's loss vector, a view of each of its slots
+        (where the loss kernels write), and the dict slot -> autograd term that the schedule fills and ``_mix`` reads."""
+        nfm = self.discriminator_A.n_stages - 1
+        lv = torch.empty(FM0 + 2 * nfm, device=self.device, dtype=torch.float32)
+        return nfm, lv, [lv[i] for i in range(FM0 + 2 * nfm)], {}
+
+    def _no_recon(self, lv, sl, terms):
+        """A D-step whose losses are not read runs no reconstruction pass: both terms read NaN, and are the bare slots."""
+        lv[RECON_A:RECON_B + 1].fill_(float("nan"))
+        terms[RECON_A], terms[RECON_B] = sl[RECON_A], sl[RECON_B]
+
+    def _recon_terms(self, xs, ts, slots):
+        """The reconstruction terms of ``xs`` against ``ts`` into their slots of the loss vector -- the reference's MSE, or the criterion
+        of ``recon_loss``: one pass on its own stream (two-chain schedule), or both as one grouped launch."""
+        mse = self.recon_loss == "mse"
+        if len(xs) == 1:
+            return (F_.MSELossFn.apply(xs[0], ts[0], slots[0]) if mse else F_.ReconLossFn.apply(xs[0], ts[0], self.recon_w, slots[0]),)
+        if mse:
+            return F_.MSELossGroupFn.apply(len(xs), *xs, *ts, *slots)
+        return F_.ReconLossGroupFn.apply(len(xs), self.recon_w, *xs, *ts, *slots)
+
+    def _pooled_fakes(self, dstep, BA, AB, ctx_for_BA=contextlib.nullcontext):
+        """(BA_seen, AB_seen, seen): the fakes the discriminators see -- in a D-step with a history pool the exchanged batches (BA's
+        exchange is issued under ``ctx_for_BA()``, AB's on the current stream), otherwise BA / AB themselves and seen = None."""
+        if not dstep or self.pool_BA is None:
+            return BA, AB, None
+        with ctx_for_BA():
+            BA_seen = self.pool_BA.exchange(BA)
+        AB_seen = self.pool_AB.exchange(AB)
+        return BA_seen, AB_seen, dict(BA=BA_seen, AB=AB_seen)
+
+    def _mix(self, lv, terms, iters, dstep, nfm, **tensors):
+        """The tail of both schedules: the curriculum mix of the loss vector (one launch; its backward seeds the gradient of every term
+        in ``loss_slots``) and the iteration's namespace: the ten loss scalars, ``lossvec`` and the schedule's ``tensors``."""
+        arch, which, idx = loss_slots(self.args.model_arch, dstep, nfm)
+        mixed = F_.LossMixFn.apply(lv, nfm, self.rate(iters), arch, which, idx, *[terms[i] for i in idx])
+        return IterationOutputs(**dict(zip(MIX_KEYS, mixed)), recon_loss_A=terms[RECON_A], recon_loss_B=terms[RECON_B], lossvec=lv, **tensors)
 
     def _forward_losses_grouped(self, A, B, iters, need_losses=True):
         """image_translation.py:342-382 with every pair of passes as grouped launches (model.group_generators /
         group_discriminators).  Main stream: G_A(B) | G_B(A), then G_A(AB) | G_B(BA) + the two reconstruction terms; side stream
         (from the hand-over of AB / BA on): the discriminator passes + GAN / feature-matching terms -- D-step: D_A(A) | D_A(BA) |
         D_B(B) | D_B(AB) as ONE group of four, G-step: the real pair without an autograd graph, then the fake pair."""
-        from .model import group_discriminators, group_generators
-        a = self.args
         dstep = self.is_dis_step(iters)
         gen_ctx = torch.no_grad if dstep else torch.enable_grad
-        main = torch.cuda.current_stream(self.device)
-        side = self.side_stream if self.two_streams else main
-        on_side = (lambda: torch.cuda.stream(side)) if self.two_streams else contextlib.nullcontext
+        main, side, on_side = self._streams()
         gA, gB, dA, dB = self.generator_A, self.generator_B, self.discriminator_A, self.discriminator_B
-        nfm = dA.n_stages - 1
-        lv = torch.empty(8 + 2 * nfm, device=self.device, dtype=torch.float32)
-        sl = [lv[i] for i in range(8 + 2 * nfm)]
-        terms = {}
+        nfm, lv, sl, terms = self._loss_vector()
         F_.FINAL_PASS = True        # the backward of these two passes is the last to touch each generator's parameters
         try:
             cut = None
@@ -553,9 +591,8 @@ class DiscoGANTrainer:
             F_.FINAL_PASS = False
         if self.graph_overlap:
             self._cut("dis_ready")                           # (a gap between two captured graphs: the wait happens at replay)
-        elif self._ev_dis_ready is not None:                 # D parameters updated on the communication stream
-            main.wait_event(self._ev_dis_ready)
-            self._ev_dis_ready = None
+        else:
+            self._wait_dis_ready(main)                       # D parameters updated on the communication stream
         if self.two_streams:
             side.wait_stream(main)
             for t_ in (A, B, lv, AB, BA):
@@ -565,20 +602,14 @@ class DiscoGANTrainer:
         if want_recon:
             with gen_ctx():
                 ABA, BAB = group_generators([gA, gB], [AB, BA])
-                if self.recon_loss == "mse":
-                    terms[0], terms[1] = F_.MSELossGroupFn.apply(2, ABA, BAB, A, B, sl[0], sl[1])
-                else:
-                    terms[0], terms[1] = F_.ReconLossGroupFn.apply(2, self.recon_w, ABA, BAB, A, B, sl[0], sl[1])
+                terms[RECON_A], terms[RECON_B] = self._recon_terms([ABA, BAB], [A, B], [sl[RECON_A], sl[RECON_B]])
         else:
-            lv[:2].fill_(float("nan"))
-            terms[0], terms[1] = sl[0], sl[1]
-        BA_seen, AB_seen, seen, dis_inputs = BA, AB, None, None
+            self._no_recon(lv, sl, terms)
+        dis_inputs = None
         aug = self.aug_A is not None
         with on_side():
+            BA_seen, AB_seen, seen = self._pooled_fakes(dstep, BA, AB)     # the history pool: both exchanges on the discriminators' stream
             if dstep:
-                if self.pool_BA is not None:                 # the history pool: both exchanges on the discriminators' stream
-                    BA_seen, AB_seen = self.pool_BA.exchange(BA), self.pool_AB.exchange(AB)
-                    seen = dict(BA=BA_seen, AB=AB_seen)
                 A_in, BA_in, B_in, AB_in = A, BA_seen, B, AB_seen
                 if aug:                                      # the four inputs of the group of four: one launch per pass
                     A_in, BA_in, B_in, AB_in = apply_group([self.aug_A, self.aug_BA, self.aug_B, self.aug_AB], [A, BA_seen, B, AB_seen])
@@ -595,26 +626,19 @@ class DiscoGANTrainer:
                 (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = group_discriminators([dA, dB], [BA_in, AB_in])
             if aug:
                 dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
-            # GAN terms (image_translation.py:157-166): slots 2 / 5 bce(real, 1), 4 / 7 bce(fake, 1), 3 / 6 bce(fake, 0)
-            terms[2], terms[4], terms[5], terms[7] = F_.BCELossGroupFn.apply(
-                4, (1.0, 1.0, 1.0, 1.0), A_dis_real, A_dis_fake, B_dis_real, B_dis_fake, sl[2], sl[4], sl[5], sl[7])
-            terms[3], terms[6] = F_.BCELossGroupFn.apply(2, (0.0, 0.0), A_dis_fake, B_dis_fake, sl[3], sl[6])
+            # GAN terms (image_translation.py:157-166): bce(real, 1) and bce(fake, 1) of both sides in one launch, bce(fake, 0) in another
+            terms[A_REAL1], terms[A_FAKE1], terms[B_REAL1], terms[B_FAKE1] = F_.BCELossGroupFn.apply(
+                4, (1.0, 1.0, 1.0, 1.0), A_dis_real, A_dis_fake, B_dis_real, B_dis_fake,
+                sl[A_REAL1], sl[A_FAKE1], sl[B_REAL1], sl[B_FAKE1])
+            terms[A_FAKE0], terms[B_FAKE0] = F_.BCELossGroupFn.apply(2, (0.0, 0.0), A_dis_fake, B_dis_fake, sl[A_FAKE0], sl[B_FAKE0])
             for l in range(nfm):
-                terms[8 + l], terms[8 + nfm + l] = F_.FeatureMatchGroupFn.apply(
-                    2, A_feats_real[l], B_feats_real[l], A_feats_fake[l], B_feats_fake[l], sl[8 + l], sl[8 + nfm + l])
+                terms[FM0 + l], terms[FM0 + nfm + l] = F_.FeatureMatchGroupFn.apply(
+                    2, A_feats_real[l], B_feats_real[l], A_feats_fake[l], B_feats_fake[l], sl[FM0 + l], sl[FM0 + nfm + l])
         if self.two_streams:
             main.wait_stream(side)
-        rate = self.rate(iters)
-        fmA, fmB = list(range(8, 8 + nfm)), list(range(8 + nfm, 8 + 2 * nfm))
-        which, idx = (7, (2, 3, 5, 6)) if dstep else (6, tuple([0, 1, 4, 7] + fmA + fmB))
-        (gen_loss_A, gen_loss_B, fm_loss_A, fm_loss_B, dis_loss_A, dis_loss_B, gen_loss, dis_loss) = \
-            F_.LossMixFn.apply(lv, nfm, rate, 0, which, idx, *[terms[i] for i in idx])
-        return IterationOutputs(
-            gen_loss=gen_loss, dis_loss=dis_loss, gen_loss_A=gen_loss_A, gen_loss_B=gen_loss_B,
-            fm_loss_A=fm_loss_A, fm_loss_B=fm_loss_B, recon_loss_A=terms[0], recon_loss_B=terms[1],
-            dis_loss_A=dis_loss_A, dis_loss_B=dis_loss_B, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
-            A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
-            A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, lossvec=lv, backward_cut=cut, dis_inputs=dis_inputs)
+        return self._mix(lv, terms, iters, dstep, nfm, AB=AB, BA=BA, ABA=ABA, BAB=BAB, seen=seen,
+                         A_dis_real=A_dis_real, A_dis_fake=A_dis_fake, B_dis_real=B_dis_real, B_dis_fake=B_dis_fake,
+                         A_feats_real=A_feats_real, B_feats_fake=B_feats_fake, backward_cut=cut, dis_inputs=dis_inputs)
 
     # ---- the iteration as a sequence of graphs with gaps (overlap_comm="graph") --------------------------------------------------
     def _cut(self, name):
@@ -628,18 +652,12 @@ class DiscoGANTrainer:
     def _gap(self, name):
         main = torch.cuda.current_stream(self.device)
         if name == "dis_ready":
-            if self._ev_dis_ready is not None:               # the discriminators' all-reduce + Adam of the last D-step (communication stream)
-                main.wait_event(self._ev_dis_ready)
-                self._ev_dis_ready = None
+            self._wait_dis_ready(main)
         elif name == "dec_bucket":
             # every gradient of both decoders is final: their exchange + Adam slices leave while the encoders' backward replays
-            opt = self.optim_gen
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self.comm_stream.wait_event(ev)
-            with torch.cuda.stream(self.comm_stream):
-                opt.begin_step()
-                self._exchange_and_step_ranges(opt, self._gen_ranges()[1], "G")
+            with self._on_comm_behind(main):
+                self.optim_gen.begin_step()
+                self._exchange_and_step_ranges(self.optim_gen, self._gen_ranges()[1], "G")
             self._dec_done = True
         else:
             raise ValueError(name)
@@ -664,21 +682,17 @@ class DiscoGANTrainer:
         self._set_requires_grad(dstep)
         if self.skip_dead_work:
             # only the stepped side's gradients are written this iteration; the other flat buffer is
-            # left alone (it may still be in flight on the communication stream)
-            if dstep and self._ev_dis_ready is not None and self._cap is None:
-                torch.cuda.current_stream(self.device).wait_event(self._ev_dis_ready)
+            # left alone (it may still be in flight on the communication stream; the event stays for the forward's own streams)
+            if dstep and self._cap is None:
+                self._wait_dis_ready(torch.cuda.current_stream(self.device), keep=True)
             # lazy: no fill -- the first weight-gradient kernel of every parameter overwrites (optim.Adam.zero_grad)
             (self.optim_dis if dstep else self.optim_gen).zero_grad(lazy=True)
         else:
             self.optim_gen.zero_grad(lazy=not dstep)     # image_translation.py:336-339 (the side that is not stepped: a plain fill)
             self.optim_dis.zero_grad(lazy=dstep)
-        from . import ops as _ops
-        # (the attributes may have been switched between iterations: tests run one trainer in several arithmetics)
-        self.ctx.prec = {"f32": _ops.PREC_F32, "bf16": _ops.PREC_BF16, "f32x3": _ops.PREC_F32X3}[self.mfma_dtype]
-        self.ctx.shadow, self.ctx.act16, self.ctx.x3 = bool(self.bf16_shadow), self.act_dtype == "bf16", bool(self.x3_planes)
-        self.ctx.clear()
+        self._refresh_ctx()
         try:
-            with _ops.use(self.ctx):           # this trainer's arithmetic / operand forms ride with every call
+            with ops.use(self.ctx):            # this trainer's arithmetic / operand forms ride with every call
                 out = self.forward_losses(A, B, iters, need_losses)
                 cut = getattr(out, "backward_cut", None)
                 if cut is not None:
@@ -821,11 +835,7 @@ class DiscoGANTrainer:
         dstep = self.is_dis_step(iters)
         opt = self.optim_dis if dstep else self.optim_gen
         if dstep and (self.overlap_comm or self.graph_overlap):
-            main = torch.cuda.current_stream(self.device)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self.comm_stream.wait_event(ev)
-            with torch.cuda.stream(self.comm_stream):
+            with self._on_comm_behind(torch.cuda.current_stream(self.device)):
                 scale = self._exchange(opt, "D")
                 opt.step(grad_scale=scale, active=self.active_ranges(dstep))
                 self._ev_dis_ready = torch.cuda.Event()
@@ -849,9 +859,8 @@ class DiscoGANTrainer:
         main = torch.cuda.current_stream(self.device)
         if self.time_comm:
             self.comm_steps["D" if dstep else "G"] += 1
-        if dstep and self._ev_dis_ready is not None:          # (a D-step right behind a D-step: update_interval 1)
-            main.wait_event(self._ev_dis_ready)
-            self._ev_dis_ready = None
+        if dstep:                                             # (a D-step right behind a D-step: update_interval 1)
+            self._wait_dis_ready(main)
         self._split_backward, self._dec_done = bool(do_step) and not self.grad_control, False
         if self.use_graph and iters >= self._eager_until and do_step:
             out = self._fwd_bwd_graphed(A, B, iters, need_losses)
@@ -865,10 +874,7 @@ class DiscoGANTrainer:
             # is needed by the very next kernel -- main stream
             self.apply_step(iters)
             return out
-        ev = torch.cuda.Event()
-        ev.record(main)
-        self.comm_stream.wait_event(ev)
-        with torch.cuda.stream(self.comm_stream):
+        with self._on_comm_behind(main):
             self._exchange_and_step_ranges(opt, self._gen_ranges()[0], "G")      # the encoders: the exposed part
         main.wait_stream(self.comm_stream)                # the next iteration's first kernels read the generators' weights
         self._ema_update(iters)                           # ... and so does the EMA: decoders' and encoders' slices are both in
@@ -886,8 +892,7 @@ class DiscoGANTrainer:
 
     def finish(self):
         """Join the communication stream (call before reading parameters / saving / timing)."""
-        if self._ev_dis_ready is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._ev_dis_ready)
+        self._wait_dis_ready(torch.cuda.current_stream(self.device), keep=True)     # (kept: the next forward's streams wait on their own)
 
     def sample(self, test_A, test_B):
         """The four generator passes of a sampling event on the held-out split (image_translation.py:170-184):
@@ -901,12 +906,9 @@ class DiscoGANTrainer:
             raise ValueError("sample() needs two batches [n,3,S,S] with n >= 2 (train-mode BatchNorm needs more than one value per "
                              f"channel at the bottleneck), got {tuple(test_A.shape)} and {tuple(test_B.shape)}")
         self.finish()
-        from . import ops as _ops
-        self.ctx.prec = {"f32": _ops.PREC_F32, "bf16": _ops.PREC_BF16, "f32x3": _ops.PREC_F32X3}[self.mfma_dtype]
-        self.ctx.shadow, self.ctx.act16, self.ctx.x3 = bool(self.bf16_shadow), self.act_dtype == "bf16", bool(self.x3_planes)
-        self.ctx.clear()
+        self._refresh_ctx()
         try:
-            with torch.no_grad(), _ops.use(self.ctx):
+            with torch.no_grad(), ops.use(self.ctx):
                 AB = self.generator_B(test_A)
                 BA = self.generator_A(test_B)
                 ABA = self.generator_A(AB)
@@ -1139,10 +1141,7 @@ class _GradBuckets:
     def _launch(self, b, producer_stream, early, active=None):
         tr, opt = self.tr, self.opt
         b["done"] = True
-        ev = torch.cuda.Event()
-        ev.record(producer_stream)
-        tr.comm_stream.wait_event(ev)
-        with torch.cuda.stream(tr.comm_stream):
+        with tr._on_comm_behind(producer_stream):
             scale = tr._all_reduce(opt.flat_g[b["begin"]:b["end"]], "G")
             if active is None or any(lo <= b["begin"] and b["end"] <= hi for lo, hi in active):
                 opt.step_ranges([(b["begin"], b["end"])], scale)    # (with the slice's bf16 shadow / f32x3 plane triples)

@@ -309,6 +309,30 @@ def test_grouped_step_with_launch_plans_tracks_the_ungrouped_step():
             assert abs(a[k] - b[k]) <= tol * abs(a[k]) + 1e-7, f"iteration {it} {k}: {a[k]} vs {b[k]}"
 
 
+OUTPUT_NAMES = {"gen_loss", "dis_loss", "gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A", "recon_loss_B",
+                "dis_loss_A", "dis_loss_B", "AB", "BA", "ABA", "BAB", "seen", "A_dis_real", "A_dis_fake", "B_dis_real", "B_dis_fake",
+                "A_feats_real", "B_feats_fake", "lossvec", "dis_inputs"}
+
+
+@pytest.mark.parametrize("kw,names", [(dict(group_launch=False), OUTPUT_NAMES),
+                                      (dict(group_launch=True, group_plan="single"), OUTPUT_NAMES | {"backward_cut"})],
+                         ids=["two_chain", "grouped"])
+def test_attributes_of_the_returned_namespace(kw, names):
+    """What ``vars(out)`` of a D-step and of a G-step holds on either schedule (bench.py --dump-outputs enumerates it): the sets are
+    those the trainer returned before its two forwards shared one tail, recorded by running that commit.  Without a history pool the
+    fakes the discriminators saw are BA / AB themselves."""
+    A, B = synthetic_batch(4, 16, 5, DEV)
+    tr = DiscoGANTrainer(default_args(), device=DEV, image_size=16, seed=1234, **kw)
+    for it in (0, 1):
+        out = tr.train_iteration(A, B, it)
+        assert set(vars(out)) == names, (it, set(vars(out)) ^ names)
+        assert out.BA_seen is out.BA and out.AB_seen is out.AB
+        assert out.seen is None and out.dis_inputs is None
+        if kw["group_launch"]:
+            assert out.backward_cut is None
+    torch.cuda.synchronize()
+
+
 def test_grouping_defaults():
     assert DiscoGANTrainer(default_args(), device=DEV, image_size=64, seed=1).group_launch
     assert DiscoGANTrainer(default_args(), device=DEV, image_size=64, seed=1, mfma_dtype="f32x3").group_launch
