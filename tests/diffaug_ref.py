@@ -80,6 +80,32 @@ def draw(seed, rank, iteration, domain, role, n, S, flags):
     return out
 
 
+# ---- the host's launch arithmetic (csrc/diffaug.hip), restated for the tests past the grid caps -----------------------------------------
+DA_MAX_PARTS, DA_PART_ELEMS = 64, 8192    # csrc/diffaug.hip
+DA_APPLY_BLOCKS = 4096                    # da_run: the apply kernel launches at most 4096 / (groups n) blocks per sample, at least 1
+DA_THREADS = 256
+# (groups, n, S): scalar form 5 blocks wanted of 3; 16-byte form 4 of 2; grouped 4 of 3; 4096 / 4098 = 0 -> one block, two trips
+APPLY_PAST_CAP = ((1, 1025, 34), (1, 1366, 64), (4, 300, 64), (2, 2049, 40))
+APPLY_CHUNK = 256                         # samples per launch that does not stride at any of these sizes
+# (n, S): 4 parts; 6; exactly 64 that tile E; scalar form, 64 with a short last chunk; 65 wanted, capped; the workload's 96 -> 64
+STATS_PARTITIONS = ((2, 100), (2, 128), (2, 416), (2, 418), (2, 420), (1, 512))
+
+
+def stats_partition(S):
+    """(parts, chunk) of da_parts / da_chunk: E = 3 S S values in ``parts`` chunks of ``chunk`` values, a multiple of 4."""
+    E = 3 * S * S
+    parts = min(-(-E // DA_PART_ELEMS), DA_MAX_PARTS)
+    return parts, (-(-E // parts) + 3) // 4 * 4
+
+
+def apply_grid(groups, n, S, vec=None):
+    """(blocks wanted, blocks launched) per sample of the apply kernel; vec: 16-byte units (default: S % 4 == 0)."""
+    vec = S % 4 == 0 if vec is None else vec
+    units = S * (S // 4) if vec else S * S
+    want = -(-units // DA_THREADS)
+    return want, min(want, max(1, DA_APPLY_BLOCKS // (groups * n)))
+
+
 def _geometry(S, rec, flags):
     """(src_y, src_x, keep): output pixel (y, x) reads v(src_y[y], src_x[x]) where keep[y, x]; Python integers, so any int32 is safe."""
     tx, ty = (int(rec[0]), int(rec[1])) if flags & TRANSLATION else (0, 0)

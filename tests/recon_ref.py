@@ -89,3 +89,58 @@ def grad_bound(x, t, w, gout, r64=None):
     r64 = grad_ref(x, t, w, gout) if r64 is None else r64
     e32 = float((grad_ref(x, t, w, gout, torch.float32).double() - r64).abs().max())
     return MR.SSIM_M * e32 + 2.0 ** -20 * float(r64.abs().max()), r64, e32
+
+
+# ---- shapes past the grid caps (tests/test_recon_cpu.py states the arithmetic, tests/test_recon_gpu.py runs them) ----------------------
+RC_MAX_BLOCKS = 8192        # csrc/recon.hip: both tile kernels launch at most this many blocks per problem and stride over the items
+RC_STREAM_BLOCKS = 1024     # csrc/recon.hip: the forward stream kernel's cap; the backward's is twice that
+TILE = 32                   # RT
+FINAL_THREADS = 256         # recon_final_kernel: thread t sums the partials t, t + 256, ...
+TILE_PAST_CAP = ((5470, 11), (690, 43), (690, 44))      # three trips at one tile per plane; four tiles per plane, scalar and 16-byte loads
+FINAL_PAST_256 = ((30, 43, "triple"), (2, 256, "l1"))   # the final kernel's second trip alone: 360 tile partials, 384 stream partials
+STREAM_PAST_CAP = ((11, 256), (125, 75))                # 16-byte loads; scalar loads with a three-element tail
+
+
+def tile_items(n, S):
+    """(items, P): work items of the tile kernels (dg_recon_loss_fwd_g: items = n P, P = 3 T^2, T = ceil(S / 32))."""
+    T = (S + TILE - 1) // TILE
+    return n * 3 * T * T, 3 * T * T
+
+
+def stream_blocks(n, S):
+    """(blocks wanted, quads, tail elements) of the stream kernels: g = (count / 4 + 255) / 256 before the cap."""
+    count = n * 3 * S * S
+    return max(1, (count // 4 + 255) // 256), count // 4, count % 4
+
+
+def planted_images(n, S):
+    """Image 0, the images that hold the items either side of every multiple of the grid cap (and the image after), the last image."""
+    items, P = tile_items(n, S)
+    at = {0, n - 1}
+    for k in range(1, (items - 1) // RC_MAX_BLOCKS + 1):
+        at |= {(k * RC_MAX_BLOCKS - 1) // P, (k * RC_MAX_BLOCKS) // P, (k * RC_MAX_BLOCKS) // P + 1}
+    return sorted(i for i in at if i < n)
+
+
+def planted_pair(n, S, seed):
+    """x = t everywhere but in the planted images, where x and t are independent: there one item's share of the loss is far above the
+    forward bound, so a dropped or misdecoded item at a trip boundary cannot hide (test_recon_cpu states the margin)."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.rand(n, 3, S, S, generator=g)
+    x = t.clone()
+    at = planted_images(n, S)
+    px, pt = MR.make_pair("indep", len(at), S, seed + 1)
+    x[at], t[at] = px, pt
+    return x, t, at
+
+
+def fwd_bound(x, t, w):
+    """The forward criterion: each part within its own bound -- MSE and L1 gamma(K_CHAIN) of their values, the SSIM part
+    ``metrics_ref.ssim_bound`` -- weighted, plus one rounding of the sum to fp32.  Returns (bound, loss64)."""
+    parts = parts_ref(x, t)
+    mse, l1, _ = (float(v) for v in parts)
+    loss = float(sum(float(wi) * p for wi, p in zip(w, parts) if wi > 0))       # loss_ref's sum, the parts evaluated once
+    fb = w[0] * MR.gamma(MR.K_CHAIN) * mse + w[1] * MR.gamma(MR.K_CHAIN) * l1 + MR.U32 * abs(loss)
+    if w[2] > 0:
+        fb += w[2] * MR.ssim_bound(x, t)[0]
+    return fb, loss

@@ -104,6 +104,38 @@ def pyramid_bound(x):
     return out + [gamma((len(Rs) - 1) * K_DOWN) * m[-1]]
 
 
+# ---- the host's launch arithmetic (csrc/swd.hip), restated for the tests past the grid caps ----------------------------------------------
+PYR_MAX_BLOCKS, PYR_THREADS = 16384, 256       # SWD_PYR_MAX_BLOCKS; one item per thread and trip
+DESC_PER_BLOCK, SUM_THREADS = 32, 256          # SWD_DESC_PER_BLOCK; swd_sum_parts: thread t adds the partials t, t + 256, ...
+# (n, S): swd_lap_kernel<4> at level 0; swd_lap_kernel<1> and swd_down_kernel<1>; swd_down_kernel<4> (and four trips of swd_lap_kernel<4>)
+PYRAMID_PAST_CAP = ((1366, 64), (4840, 34), (5462, 64))
+PYRAMID_CHUNK = 512                            # images per launch that does not stride at these sizes
+STATS_PAST_256 = ((257, 32), (256, 128))       # (n, P) at R = 16: 257 and 1024 block partials
+
+
+def pyramid_launches(n, S):
+    """dg_lap_pyramid's launches for 16-byte aligned buffers: [(kernel, V, level, items, items per image)] in launch order."""
+    out = []
+    for l, R in enumerate(levels(S)[:-1]):
+        Ro = R // 2
+        v = 4 if Ro % 4 == 0 else 1
+        out.append(("down", v, l, n * 3 * Ro * (Ro // v), 3 * Ro * (Ro // v)))
+        v = 4 if R % 4 == 0 else 1
+        out.append(("lap", v, l, n * 3 * R * (R // v), 3 * R * (R // v)))
+    return out
+
+
+def pyramid_boundary_images(n, S):
+    """The first and last image and, for every launch that strides, the images that hold the items either side of each trip boundary
+    (with their neighbours)."""
+    cap = PYR_MAX_BLOCKS * PYR_THREADS
+    at = {0, 1, 2, n // 2, n - 3, n - 2, n - 1}
+    for _, _, _, items, per in pyramid_launches(n, S):
+        for k in range(1, (items - 1) // cap + 1):
+            at |= {(k * cap - 1) // per - 1, (k * cap - 1) // per, (k * cap) // per, (k * cap) // per + 1}
+    return sorted(i for i in at if 0 <= i < n)
+
+
 # ---- descriptors, statistics, projection ----------------------------------------------------------------------------------------------------
 def gather(level, recs):
     """[n,3,R,R], int [n,P,2] -> [n P, 147] ordered [channel][dy][dx]; offsets clamped to [0, R - 7] as the kernel does"""

@@ -1,6 +1,8 @@
 """Differentiable augmentation without a GPU: the policy parser and the trainer's check, the CLI flag, the numpy reference against the
 published function and against its own adjoint, the statistics of the draw with a few pinned rows, and the launchers' argument checks."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -39,6 +41,29 @@ def test_parsers_gain_diffaug_off_by_default():
 def test_an_unknown_policy_is_refused_before_the_device_check():
     with pytest.raises(ValueError, match="unknown policy 'blur'"):
         it.train(it.parse_args(["--task_name", "edges2shoes", "--diffaug", "color,blur"]))
+
+
+def test_shapes_past_the_grid_caps_reach_every_stride_loop():
+    """The launch arithmetic of da_run / da_parts / da_chunk (csrc/diffaug.hip) at the shapes the GPU tests run past the caps, and the
+    constants diffaug_ref copies against the source."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "discogan_modernized_amd", "csrc", "diffaug.hip")).read()
+    assert int(re.search(r"#define DA_MAX_PARTS (\d+)", src).group(1)) == DR.DA_MAX_PARTS
+    assert int(re.search(r"#define DA_PART_ELEMS (\d+)", src).group(1)) == DR.DA_PART_ELEMS
+    assert f"cap = {DR.DA_APPLY_BLOCKS} / ((long)groups * n)" in src and "gx = (a.units + 255) / 256" in src
+    assert [DR.apply_grid(g, n, S) for g, n, S in DR.APPLY_PAST_CAP] == [(5, 3), (4, 2), (4, 3), (2, 1)]
+    assert [S % 4 == 0 for _, _, S in DR.APPLY_PAST_CAP] == [False, True, True, True]
+    assert DR.DA_APPLY_BLOCKS // (2 * 2049) == 0                                            # the floor of one block per sample
+    for g, n, S in DR.APPLY_PAST_CAP:                                                      # the chunks compared against do not stride,
+        for vec in (S % 4 == 0, False):                                                    # nor in the scalar form
+            want, got = DR.apply_grid(1, DR.APPLY_CHUNK, S, vec)
+            assert want == got
+    assert [DR.stats_partition(S) for _, S in DR.STATS_PARTITIONS] == [(4, 7500), (6, 8192), (64, 8112), (64, 8192), (64, 8272), (64, 12288)]
+    assert [-(-3 * S * S // DR.DA_PART_ELEMS) for _, S in DR.STATS_PARTITIONS] == [4, 6, 64, 64, 65, 96]
+    for S in SIZES + (16, 34, 40):                                                         # what the older tests reach
+        assert DR.stats_partition(S)[0] <= 2 and DR.apply_grid(4, 5, S, vec=False) == (-(-S * S // 256),) * 2
+    for S in (2, 9, 64, 100, 418, 420, 512, 4097):                                         # the partition covers the sample, in whole quads
+        parts, chunk = DR.stats_partition(S)
+        assert chunk % 4 == 0 and (parts - 1) * chunk < 3 * S * S <= parts * chunk and 1 <= parts <= DR.DA_MAX_PARTS
 
 
 @pytest.mark.parametrize("S", SIZES)

@@ -47,13 +47,13 @@ class _Banded:
         return self.buf[self.lo:self.lo + self.size].cpu().numpy().view(dtype).reshape(self.shape)
 
     def bands_intact(self):
-        host = self.buf.cpu().numpy()
-        return bool((host[:self.lo] == SENTINEL).all() and (host[self.lo + self.size:] == SENTINEL).all())
+        return bool((self.buf[:self.lo] == SENTINEL).all() and (self.buf[self.lo + self.size:] == SENTINEL).all())
 
 
-def _run_op(op, x_np, recs_np, flags, shift=0):
-    """One dg_diffaug_fwd / _bwd on banded buffers: the output as int32 patterns; the input unwritten, every band intact."""
-    x, out = _Banded(x_np, shift), _Banded(np.full(x_np.shape, 7, dtype=np.int32), shift)
+def _run_op(op, x_np, recs_np, flags, shift=0, fill=7):
+    """One dg_diffaug_fwd / _bwd on banded buffers (the output starts as ``fill``): the output as int32 patterns; the input unwritten,
+    every band intact."""
+    x, out = _Banded(x_np, shift), _Banded(np.full(x_np.shape, fill, dtype=np.int32), shift)
     recs = torch.from_numpy(np.ascontiguousarray(recs_np)).to(DEV)
     got = op(x.view(), flags, recs, out=out.view())
     assert got.data_ptr() == out.view().data_ptr()
@@ -211,6 +211,102 @@ def test_grouped_forms_are_bitwise_the_single_calls(S, flags):
         assert torch.equal(on_side.view(torch.int32), want[1].view(torch.int32))
         assert torch.equal(pair[0].view(torch.int32), want[2].view(torch.int32)) and torch.equal(pair[1].view(torch.int32), want[3].view(torch.int32))
         assert len({int(t.view(torch.int32).sum()) for t in want}) == g                   # four different problems
+
+
+# ---- 4b. past the grid caps ------------------------------------------------------------------------------------------------------------------
+UNWRITTEN = 0x7FC0DEAD                     # a NaN pattern no kernel produces: what the outputs of the tests below start as
+
+
+def _past_cap_records(n, S, flags, dom):
+    """A drawn table with the hand-made records cycled through every fourth row (their geometry; the drawn factors stay)."""
+    recs = ops.diffaug_draw(4321, 0, 9, dom & 1, dom >> 1, n, S, flags, device=DEV).cpu().numpy().copy()
+    hand = _hand_records(S)
+    rows = np.arange(1, n, 4)
+    recs[rows, :4] = hand[np.arange(len(rows)) % len(hand), :4]
+    return recs, len(hand)
+
+
+@pytest.mark.parametrize("flags", [6, 7])
+@pytest.mark.parametrize("groups,n,S", DR.APPLY_PAST_CAP)
+def test_apply_kernel_past_its_per_sample_cap(groups, n, S, flags):
+    """More 256-unit blocks wanted per sample than 4096 / (groups n) allows: every block of diffaug_apply_kernel strides.  Forward and
+    backward, outputs that start as NaN between sentinel bands.  The launch equals, bit for bit, launches of at most 256 samples (which
+    do not stride) with the same rows of the record table; and chosen samples -- the first and last of every group, records that shift
+    by a multiple of 4 and by another amount -- pass the file's reference check: bitwise without colour, the float64 criterion with."""
+    want, launched = DR.apply_grid(groups, n, S)
+    assert want > launched and launched == max(1, 4096 // (groups * n)), (want, launched)
+    assert DR.apply_grid(1, DR.APPLY_CHUNK, S)[0] == DR.apply_grid(1, DR.APPLY_CHUNK, S)[1] == want    # the chunks do not stride
+    rng = np.random.default_rng(7 * n + S + flags)
+    if flags & DR.COLOR:
+        data = [(rng.random((n, 3, S, S), dtype=np.float32), rng.standard_normal((n, 3, S, S)).astype(np.float32)) for _ in range(groups)]
+    else:
+        data = [(_patterns((n, 3, S, S), 10 * n + S + g),) * 2 for g in range(groups)]
+    tabs = [_past_cap_records(n, S, flags, g) for g in range(groups)]
+    recs_np, n_hand = [t[0] for t in tabs], tabs[0][1]
+    recs = [torch.from_numpy(r).to(DEV) for r in recs_np]
+    sel = sorted({0, 1, 2, 3, n - 3, n - 2, n - 1} | {4 * h + 1 for h in range(n_hand - 5, n_hand)})      # the last five hand rows shift by 4, -8, 3, -5, 8
+    assert len(sel) >= 8 and sel[-1] == n - 1
+    tx = recs_np[0][sel, 0]
+    assert ((tx % 4 == 0) & (tx != 0) & (abs(tx) < S)).any() and ((tx % 4 != 0) & (abs(tx) < S)).any()
+    for k, (single, grouped, ref) in enumerate(((ops.diffaug_fwd, ops.diffaug_fwd_g, DR.forward), (ops.diffaug_bwd, ops.diffaug_bwd_g, DR.backward))):
+        ins = [_Banded(d[k]) for d in data]
+        outs = [_Banded(np.full((n, 3, S, S), UNWRITTEN, dtype=np.int32)) for _ in range(groups)]
+        assert all(b.view().data_ptr() % 16 == 0 for b in ins + outs)
+        kept = [b.buf.clone() for b in ins]
+        if groups > 1:
+            grouped([b.view() for b in ins], flags, recs, outs=[b.view() for b in outs])
+        else:
+            single(ins[0].view(), flags, recs[0], out=outs[0].view())
+        for g in range(groups):
+            assert torch.equal(ins[g].buf, kept[g]), "the input was written"
+            assert ins[g].bands_intact() and outs[g].bands_intact()
+            got_dev = outs[g].view().view(torch.int32)
+            for lo in range(0, n, DR.APPLY_CHUNK):
+                part = single(ins[g].view()[lo:lo + DR.APPLY_CHUNK], flags, recs[g][lo:lo + DR.APPLY_CHUNK])
+                assert torch.equal(part.view(torch.int32), got_dev[lo:lo + DR.APPLY_CHUNK]), (ref.__name__, g, lo)
+            got = got_dev[sel].cpu().numpy()
+            inp = data[g][k][sel]
+            if not flags & DR.COLOR:
+                assert np.array_equal(got, ref(inp, recs_np[g][sel], flags)), (ref.__name__, g)
+                continue
+            wanted = ref(inp.astype(np.float64), recs_np[g][sel], flags)
+            bound, e_ref = _bound(ref(inp, recs_np[g][sel], flags, np.float32), wanted)
+            err = float(np.abs(got.view(np.float32).astype(np.float64) - wanted).max())
+            print(f"groups {groups} n {n} S {S} {ref.__name__} group {g}: err {err:.3e} e_ref {e_ref:.3e} bound {bound:.3e}")
+            assert err <= bound, (ref.__name__, g, err, bound)
+
+
+@pytest.mark.parametrize("n,S", DR.STATS_PARTITIONS)
+def test_statistics_partition_at_and_past_its_cap(n, S):
+    """diffaug_stats_kernel with 4, 6, exactly 64, and more than 64 chunks wanted per sample (capped: a thread then takes more trips over
+    its chunk), in the 16-byte and the scalar form; the apply kernel's tree over up to 64 partials.  Colour alone and the whole policy,
+    forward and backward, against float64.  The records shift and cut at the ends of their ranges, so the backward's "sum of g over
+    its sources" mask changes inside chunks and across their boundaries."""
+    parts, chunk = DR.stats_partition(S)
+    E, T, cs = 3 * S * S, DR.T_of(S), DR.cs_of(S)
+    assert (parts, chunk) == {100: (4, 7500), 128: (6, 8192), 416: (64, 8112), 418: (64, 8192), 420: (64, 8272), 512: (64, 12288)}[S]
+    assert (parts - 1) * chunk < E <= parts * chunk and (S % 4 == 0) != (S == 418)
+    assert (-(-E // DR.DA_PART_ELEMS) > 64) == (S in (420, 512)) and (S != 416 or (-(-E // DR.DA_PART_ELEMS) == 64 and 64 * chunk == E))
+    assert S != 418 or E - 63 * chunk == 8076
+    lo, hi = -(cs // 2), S - cs % 2 - cs // 2                     # the ends of the cut square's range (dg_diffaug_draw)
+    recs = np.stack([DR.make_record(T, -T, lo, hi, 0.25, 2.0, 1.5), DR.make_record(-T, T, hi, lo, -0.25, 0.0, 0.5)])[:n]
+    rng = np.random.default_rng(1000 + 10 * n + S)
+    x_np = rng.random((n, 3, S, S), dtype=np.float32)
+    dz_np = rng.standard_normal((n, 3, S, S)).astype(np.float32)
+    for flags in (DR.COLOR, DR.ALL):
+        for op, ref, inp in ((ops.diffaug_fwd, DR.forward, x_np), (ops.diffaug_bwd, DR.backward, dz_np)):
+            want = ref(inp.astype(np.float64), recs, flags)
+            bound, e_ref = _bound(ref(inp, recs, flags, np.float32), want)
+            for shift in (0, 1):
+                got = _run_op(op, inp, recs, flags, shift, fill=UNWRITTEN).view(np.float32)
+                err = float(np.abs(got.astype(np.float64) - want).max())
+                print(f"S {S} n {n} parts {parts} chunk {chunk} flags {flags} {ref.__name__} shift {shift}: err {err:.3e} e_ref {e_ref:.3e} "
+                      f"bound {bound:.3e}")
+                assert err <= bound, (flags, ref.__name__, shift, err, bound)
+                if shift == 0:
+                    first = got
+                else:                                        # the statistics do not depend on the alignment class
+                    assert np.array_equal(got.view(np.int32), first.view(np.int32))
 
 
 def test_ops_wrappers_refuse_what_the_kernels_cannot_take():

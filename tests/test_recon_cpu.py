@@ -56,6 +56,51 @@ def test_gradient_is_the_central_finite_difference():
         assert rel <= 1e-6, (w, rel)                  # the difference quotient's own error: h^2 f''' / 6 + rounding / h
 
 
+def test_shapes_past_the_grid_caps_reach_every_stride_loop():
+    """The host's grid arithmetic (csrc/recon.hip, dg_recon_loss_fwd_g / dg_recon_loss_bwd_g) at the shapes the GPU tests run past the
+    caps, and the constants they copy against the source."""
+    src = open(os.path.join(ROOT, "discogan_modernized_amd", "csrc", "recon.hip")).read()
+    assert int(re.search(r"#define RC_MAX_BLOCKS (\d+)", src).group(1)) == RR.RC_MAX_BLOCKS
+    assert int(re.search(r"#define RC_STREAM_BLOCKS (\d+)", src).group(1)) == RR.RC_STREAM_BLOCKS
+    assert int(re.search(r"#define RT (\d+)", src).group(1)) == RR.TILE
+    assert "i += 256" in src.split("void recon_final_kernel")[1].split("__global__")[0] and RR.FINAL_THREADS == 256
+    assert "g > 2 * RC_STREAM_BLOCKS ? 2 * RC_STREAM_BLOCKS" in src                          # the backward stream kernel's cap
+    assert [RR.tile_items(n, S) for n, S in RR.TILE_PAST_CAP] == [(16410, 3), (8280, 12), (8280, 12)]
+    assert RR.planted_images(5470, 11) == [0, 2730, 2731, 5461, 5462, 5469] and RR.planted_images(690, 43) == [0, 682, 683, 689]
+    for n, S in RR.TILE_PAST_CAP:
+        items, P = RR.tile_items(n, S)
+        assert items > RR.RC_MAX_BLOCKS and -(-items // RR.RC_MAX_BLOCKS) == (3 if S == 11 else 2)
+        at = RR.planted_images(n, S)
+        for k in range(1, (items - 1) // RR.RC_MAX_BLOCKS + 1):                              # the items either side of every trip boundary
+            assert (k * RR.RC_MAX_BLOCKS - 1) // P in at and (k * RR.RC_MAX_BLOCKS) // P in at
+    assert [S % 4 for _, S in RR.TILE_PAST_CAP] == [3, 3, 0]
+    assert RR.tile_items(30, 43)[0] == 360 and RR.stream_blocks(2, 256) == (384, 98304, 0)  # FINAL_PAST_256: one grid, two trips of the final kernel
+    assert RR.stream_blocks(11, 256) == (2112, 540672, 0) and RR.stream_blocks(125, 75) == (2060, 527343, 3)
+    for n, S in RR.STREAM_PAST_CAP:
+        assert RR.stream_blocks(n, S)[0] > 2 * RR.RC_STREAM_BLOCKS
+    for n, S in SHAPES:                                                                      # what the older tests reach: one trip everywhere
+        assert RR.tile_items(n, S)[0] <= RR.FINAL_THREADS and RR.stream_blocks(n, S)[0] <= RR.FINAL_THREADS
+
+
+@pytest.mark.parametrize("n,S", RR.TILE_PAST_CAP)
+def test_a_planted_channel_moves_the_loss_by_four_forward_bounds(n, S):
+    """On ``planted_pair`` data, making x = t in any one channel of any one planted image (what a dropped or misplaced item would
+    amount to) moves the float64 loss by more than 4 x the forward bound.  The loss is a mean over images of per-image terms, so the
+    move of the whole batch's loss is the move of that image's own loss / n."""
+    x, t, at = RR.planted_pair(n, S, 100 * S + n)
+    assert all(torch.equal(x[i], t[i]) == (i not in at) for i in range(n))
+    bound, loss = RR.fwd_bound(x, t, TRIPLE)
+    least = float("inf")
+    for i in at:
+        own = float(RR.loss_ref(x[i:i + 1], t[i:i + 1], TRIPLE))
+        for ch in range(3):
+            xi = x[i:i + 1].clone()
+            xi[0, ch] = t[i, ch]
+            least = min(least, abs(own - float(RR.loss_ref(xi, t[i:i + 1], TRIPLE))) / n)
+    print(f"n {n} S {S}: loss {loss:.6e} forward bound {bound:.3e} smallest move {least:.3e} = {least / bound:.1f} bounds")
+    assert least > 4 * bound, (least, bound)
+
+
 def test_recon_weights_table():
     assert losses.recon_weights("mse") == (1.0, 0.0, 0.0)
     assert losses.recon_weights("l1") == (0.0, 1.0, 0.0)

@@ -43,15 +43,25 @@ def _case(n, S, kind, wname):
     key = (n, S, kind, wname)
     if key not in _REF:
         w = WEIGHTS[wname]
-        x, t = MR.make_pair(kind, n, S, 100 * S + n)
-        mse, l1, ssim = (float(v) for v in RR.parts_ref(x, t))
-        loss = float(RR.loss_ref(x, t, w))
-        fb = w[0] * MR.gamma(MR.K_CHAIN) * mse + w[1] * MR.gamma(MR.K_CHAIN) * l1 + MR.U32 * abs(loss)
-        if w[2] > 0:
-            fb += w[2] * MR.ssim_bound(x, t)[0]
-        gb, g64, e32 = RR.grad_bound(x, t, w, GOUT)
-        _REF[key] = dict(x=x, t=t, w=w, loss=loss, fbound=fb, grad=g64, gbound=gb, e32=e32)
+        sel = None
+        if kind == "planted":                                  # x = t but in the images at the trip boundaries (recon_ref.planted_pair)
+            x, t, at = RR.planted_pair(n, S, 100 * S + n)
+            if _halves(n, S):                                  # dx is held to its halves' launches bit for bit: float64 for chosen images
+                sel = sorted({j for i in at + [n // 2] for j in (i - 1, i, i + 1) if 0 <= j < n})
+        else:
+            x, t = MR.make_pair(kind, n, S, 100 * S + n)
+        fb, loss = RR.fwd_bound(x, t, w)
+        if sel is None:
+            gb, g64, e32 = RR.grad_bound(x, t, w, GOUT)
+        else:       # the loss is a mean over images of per-image terms: rows ``sel`` of the whole batch's gradient are the sub-batch's x m / n
+            gb, g64, e32 = RR.grad_bound(x[sel], t[sel], w, GOUT * len(sel) / n)
+        _REF[key] = dict(x=x, t=t, w=w, loss=loss, fbound=fb, grad=g64, gbound=gb, e32=e32, sel=sel)
     return _REF[key]
+
+
+def _halves(n, S):
+    """The batch splits into two launches that do not stride."""
+    return n % 2 == 0 and RR.tile_items(n // 2, S)[0] <= RR.RC_MAX_BLOCKS
 
 
 def _gpu(c):
@@ -79,16 +89,42 @@ def test_mse_and_l1_parts_alone_are_one_rounding_from_their_formulas(n, S):
     """Weights (1, 0, 0) and (0, 1, 0): the streaming kernels, any S.  Forward within gamma(K_CHAIN); dx within one fp32 rounding of
     gout 2 (x - t) / N and gout sign(x - t) / N, sign(0) = 0."""
     x, t = MR.make_pair("noisy", n, S, 5 * S + n)
+    _stream_check(x, t)
+
+
+def _stream_check(x, t, share=None):
+    """The criteria of the stream kernels on one pair; loss slot and dx start as NaN.  share(values [N] float64) -> the smallest
+    share of the sum that one block's trip (or the tail) holds: it must exceed the forward bound, or a dropped trip could hide."""
     x[0, 1, 2, 3] = t[0, 1, 2, 3]                           # a zero difference
     x64, t64, N = x.double(), t.double(), x.numel()
     xg, tg = x.to(DEV), t.to(DEV)
-    for w, val, ref in (((1.0, 0.0, 0.0), float(((x64 - t64) ** 2).mean()), GOUT * 2.0 * (x64 - t64) / N),
-                        ((0.0, 1.0, 0.0), float((x64 - t64).abs().mean()), GOUT * torch.sign(x64 - t64) / N)):
-        loss = float(ops.recon_loss_fwd(xg, tg, w))
+    for w, terms, ref in (((1.0, 0.0, 0.0), (x64 - t64) ** 2, GOUT * 2.0 * (x64 - t64) / N),
+                          ((0.0, 1.0, 0.0), (x64 - t64).abs(), GOUT * torch.sign(x64 - t64) / N)):
+        val = float(terms.mean())
+        if share is not None:
+            least = share(terms.reshape(-1)) / N
+            print(f"w {w}: value {val:.6e} bound {MR.gamma(MR.K_CHAIN) * val:.3e} smallest trip's share {least:.3e}")
+            assert least > MR.gamma(MR.K_CHAIN) * val, (w, least)
+        loss = float(_fwd_nan(xg, tg, w))
         assert abs(loss - val) <= MR.gamma(MR.K_CHAIN) * val, (w, loss, val)
-        dx = ops.recon_loss_bwd(xg, tg, w, _gout()).cpu().double()
+        dx = _bwd_nan(xg, tg, w).cpu().double()
         assert bool(((dx - ref).abs() <= MR.U32 * (1 + 2.0 ** -20) * ref.abs()).all()), w
         assert float(dx[0, 1, 2, 3]) == 0.0
+
+
+def _fwd_nan(x, t, w):
+    """ops.recon_loss_fwd into a slot that starts as NaN."""
+    return ops.recon_loss_fwd(x, t, w, out=torch.full((), float("nan"), device=DEV))
+
+
+def _bwd_nan(x, t, w, gout=GOUT):
+    """dg_recon_loss_bwd into a dx that starts as NaN: a value no trip wrote is not "equal"."""
+    assert x.is_contiguous() and t.is_contiguous() and x.shape == t.shape
+    dx = torch.full_like(x, float("nan"))
+    g = torch.tensor(gout, device=DEV, dtype=torch.float32)
+    _lib.check(_lib.load().dg_recon_loss_bwd(x.data_ptr(), t.data_ptr(), x.shape[0], x.shape[-1], (ctypes.c_float * 3)(*w), g.data_ptr(), dx.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream), "dg_recon_loss_bwd")
+    return dx
 
 
 @pytest.mark.parametrize("n,S", SHAPES)
@@ -163,6 +199,81 @@ def test_a_nan_stays_in_its_own_image(S):
             got = ops.recon_loss_bwd(bad, t, c["w"], _gout())
             assert torch.equal(_bits(got[0]), _bits(clean[0])) and torch.equal(_bits(got[2]), _bits(clean[2])), (wname, where)
             assert bool(torch.isnan(got[1][where[1:]])) and bool(torch.isnan(ops.recon_loss_fwd(bad, t, c["w"])))
+
+
+# ---- 2b. past the grid caps: the stride loops of the tile, stream and final kernels ---------------------------------------------------
+@pytest.mark.parametrize("n,S", RR.TILE_PAST_CAP)
+def test_tile_kernels_past_the_grid_cap(n, S):
+    """More items than RC_MAX_BLOCKS: every block of both tile kernels takes a second (at S = 11 some a third) item, and the final
+    kernel many trips.  Data: recon_ref.planted_pair, whose sensitivity test_recon_cpu states.  The forward against float64 of the whole
+    batch under the bound of ``_case``.  The gradient, n = 690: dx equals, bit for bit, the launches of the two halves (which do not
+    stride) with gout / 2 -- gout / 2 is exact and both normalisers of half the batch are exactly twice the whole batch's, so the three
+    factors gout w / N are the same doubles -- and the planted images, the last of the first and the first of the second half and
+    their neighbours are held to float64 under the bound of ``_case`` taken on those images.  n = 5470 has no power-of-two split into
+    sub-cap chunks, and another ratio changes the factors' roundings: float64 of the whole batch there, which is cheap at 11 px."""
+    items, P = RR.tile_items(n, S)
+    assert items > RR.RC_MAX_BLOCKS and items > RR.FINAL_THREADS                    # a second trip in the tile and the final kernels
+    if S == 11:
+        assert P == 3 and 0 < items - 2 * RR.RC_MAX_BLOCKS < RR.RC_MAX_BLOCKS      # some blocks take three items, the rest two
+    else:
+        assert P == 12 and RR.RC_MAX_BLOCKS % P != 0                               # four tiles per plane; the second trip starts inside an image
+    assert (S % 4 == 0) == (S == 44)                                                # 16-byte loads at 44 alone
+    c = _case(n, S, "planted", "triple")
+    x, t = c["x"].to(DEV), c["t"].to(DEV)
+    assert x.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0
+    loss, dx = _fwd_nan(x, t, c["w"]), _bwd_nan(x, t, c["w"])
+    ferr = abs(float(loss) - c["loss"])
+    gerr = float(((dx if c["sel"] is None else dx[c["sel"]]).cpu().double() - c["grad"]).abs().max())
+    print(f"n {n} S {S} planted: loss {c['loss']:.6f} err {ferr:.3e} bound {c['fbound']:.3e} | grad max {float(c['grad'].abs().max()):.3e} "
+          f"err {gerr:.3e} e32 {c['e32']:.3e} bound {c['gbound']:.3e}")
+    assert ferr <= c["fbound"], (ferr, c["fbound"])
+    assert gerr <= c["gbound"], (gerr, c["gbound"])
+    if _halves(n, S):
+        h = n // 2
+        assert len(c["sel"]) >= 8 and {0, h - 1, h, n - 1} <= set(c["sel"])
+        for lo in (0, h):
+            half = _bwd_nan(x[lo:lo + h], t[lo:lo + h], c["w"], gout=GOUT / 2)
+            assert torch.equal(_bits(half), _bits(dx[lo:lo + h])), lo
+    else:
+        assert (n, S) == (5470, 11) and c["sel"] is None
+
+
+@pytest.mark.parametrize("n,S,wname", RR.FINAL_PAST_256)
+def test_final_kernel_second_trip(n, S, wname):
+    """More partials than the final kernel has threads, fewer than any grid cap: its stride loop alone."""
+    if WEIGHTS[wname][2] > 0:
+        parts = RR.tile_items(n, S)[0]
+        assert RR.FINAL_THREADS < parts <= RR.RC_MAX_BLOCKS
+        for kind in ("indep", "noisy"):
+            c = _case(n, S, kind, wname)
+            ferr = abs(float(_fwd_nan(c["x"].to(DEV), c["t"].to(DEV), c["w"])) - c["loss"])
+            print(f"n {n} S {S} {kind} {wname}: {parts} partials, err {ferr:.3e} bound {c['fbound']:.3e}")
+            assert ferr <= c["fbound"], (kind, ferr, c["fbound"])
+    else:
+        parts = RR.stream_blocks(n, S)[0]
+        assert RR.FINAL_THREADS < parts <= RR.RC_STREAM_BLOCKS
+        x, t = MR.make_pair("noisy", n, S, 5 * S + n)
+        _stream_check(x, t, share=lambda v: float(v.reshape(-1, 1024).sum(1).min()))
+
+
+@pytest.mark.parametrize("n,S", RR.STREAM_PAST_CAP)
+def test_stream_kernels_past_both_caps(n, S):
+    """More blocks wanted than the forward's 1024 and the backward's 2048: the stride loops of both stream kernels, with 16-byte and
+    with scalar loads and a three-element tail.  One block's trip is 256 quads; the tail's differences are set to 1 so that its share,
+    like every trip's, is above the bound."""
+    blocks, quads, tail = RR.stream_blocks(n, S)
+    assert blocks > 2 * RR.RC_STREAM_BLOCKS and (S % 4 == 0 or tail == 3)
+    x, t = MR.make_pair("noisy", n, S, 5 * S + n)
+    if tail:
+        x.view(-1)[-tail:], t.view(-1)[-tail:] = 1.0, 0.0
+
+    def share(v):
+        body = v[:4 * quads]
+        full = body[:body.numel() // 1024 * 1024].reshape(-1, 1024).sum(1)
+        rest = [float(body[full.numel() * 1024:].sum())] if body.numel() % 1024 else []
+        return min([float(full.min())] + rest + ([float(v[4 * quads:].sum())] if tail else []))
+
+    _stream_check(x, t, share)
 
 
 # ---- 3. refusals and the autograd nodes ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Sample grids, the parts that need no GPU: argument validation of dg_sample_grid_u8, the CLI surface, the PNG writer and the
 rounding rule the kernel is built on."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -32,6 +33,33 @@ def test_sample_grid_entry_point_validates_its_arguments():
         assert word in L.dg_last_error(), (over, L.dg_last_error())
     # a canvas whose rows do not fit 32-bit byte offsets
     assert call(S=2 ** 30, cols=8) == -1 and b"too large" in L.dg_last_error()
+
+
+GRID_MAX_BLOCKS, GRID_THREADS = 8192, 256      # csrc/export.hip, dg_sample_grid_u8: "if (g > 8192) g = 8192", 256 units per block and trip
+# (rows, cols, S): 16-byte loads and scalar quads; at both the cell units alone outnumber the grid, so every gutter unit is written on a later trip
+GRID_PAST_CAP = ((65, 8, 128), (8800, 8, 10))
+
+
+def grid_units(rows, cols, S, gap):
+    """(cell, band, strip) units of sample_grid_kernel's one index space, as dg_sample_grid_u8 counts them."""
+    Wc = cols * (S + gap) + gap
+    band = (rows + 1) * (gap * Wc * 3 // 4 + 2) if gap > 0 else 0
+    return cols * rows * S * ((S + 3) // 4), band, rows * S * (cols + 1) if gap > 0 else 0
+
+
+def test_grid_shapes_past_the_grid_cap():
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "discogan_modernized_amd", "csrc", "export.hip")).read()
+    assert f"if (g > {GRID_MAX_BLOCKS}) g = {GRID_MAX_BLOCKS};" in src and f"dim3({GRID_THREADS}), 0, (hipStream_t)s, a);" in src
+    assert "a.band_dwords = gap > 0 ? a.band_bytes / 4 + 2 : 0;" in src and "a.n_strip = gap > 0 ? (long)rows * S * (cols + 1) : 0;" in src
+    cap = GRID_MAX_BLOCKS * GRID_THREADS
+    assert [grid_units(r, c, S, 3)[0] for r, c, S in GRID_PAST_CAP] == [2129920, 2112000]
+    for r, c, S in GRID_PAST_CAP:
+        for gap in (0, 3):
+            cell, band, strip = grid_units(r, c, S, gap)
+            assert cell > cap and (gap == 0) == (band + strip == 0)
+    # the largest older case, the 5 x 6 grid at 512 px, stays under the cap at every gap it runs: no older test strides
+    assert [sum(grid_units(5, 6, 512, gap)) for gap in (0, 2, 3)] == [1966080, 2011786, 2025766]
+    assert all(sum(grid_units(r, c, S, 3)) <= cap for r, c in ((1, 1), (2, 3), (5, 6), (3, 8)) for S in (10, 16, 64, 512))
 
 
 def test_parser_gains_the_test_split_flags_and_keeps_every_default():

@@ -4,6 +4,7 @@ its neutrality for everything but the generators' BatchNorm buffers, and the CLI
 Kernel bar: no tolerance anywhere.  ``pixel = rint(clip(x, 0, 1) * float32(255))`` in fp32, NaN -> 0, whole canvas compared, gutters
 included.  Trainer bar: the one-forward-pass bounds of tests/test_model_gpu.py (outputs 1e-4 max|ref| + 1e-5, buffers 1e-4 max|ref| +
 1e-6), each comparison one generator deep (the oracle's second pass is fed the GPU's first-pass output)."""
+import ctypes
 import os
 import tempfile
 
@@ -20,6 +21,7 @@ from discogan_modernized_amd import _lib, ops, samples  # noqa: E402
 from discogan_modernized_amd import dataset as ds  # noqa: E402
 from discogan_modernized_amd import image_translation as it_cli  # noqa: E402
 from discogan_modernized_amd.trainer import DiscoGANTrainer, default_args, synthetic_batch  # noqa: E402
+from tests.test_samples_cpu import GRID_MAX_BLOCKS, GRID_PAST_CAP, GRID_THREADS, grid_units  # noqa: E402  (the host's grid arithmetic)
 from oracle import discogan_ref as O  # noqa: E402  (checker only)
 from oracle import image_prep_ref as R  # noqa: E402  (checker only)
 
@@ -81,6 +83,8 @@ def make_batches(rows, cols, S, seed):
 @pytest.mark.parametrize("rows,cols", [(1, 1), (2, 3), (5, 6), (3, 8)])
 @pytest.mark.parametrize("S", [10, 16, 64, 512])
 def test_grid_kernel_is_bit_exact(S, rows, cols):
+    """The largest case here, the 5 x 6 grid at 512 px, is 2 025 766 units at gap 3: 3 % UNDER the kernel's 8192 x 256 grid.  No case
+    of this test strides; test_grid_kernel_past_the_grid_cap does."""
     batches, all_planted = make_batches(rows, cols, S, seed=1000 * S + 10 * rows + cols)
     assert all_planted or cols * rows * S * S * 3 < 2 * len(special_values())
     dev = [torch.from_numpy(b).to(DEV) for b in batches]
@@ -92,6 +96,29 @@ def test_grid_kernel_is_bit_exact(S, rows, cols):
             got = got.cpu().numpy()
             bad = np.argwhere(got != want)
             assert bad.size == 0, f"S={S} {rows}x{cols} gap={gap} bg={bg}: {len(bad)} bytes differ, first at {bad[0]}"
+
+
+@pytest.mark.parametrize("rows,cols,S", GRID_PAST_CAP)
+def test_grid_kernel_past_the_grid_cap(rows, cols, S):
+    """More units than 8192 blocks x 256: the kernel's stride loop, with 16-byte loads (S = 128) and with scalar quads and a short last
+    quad (S = 10).  The cell units alone outnumber the grid, so every gutter byte is written on a later trip.  The canvas starts as 7s
+    (neither background nor, but by chance, a pixel), whole canvas compared."""
+    cap = GRID_MAX_BLOCKS * GRID_THREADS
+    batches, all_planted = make_batches(rows, cols, S, seed=1000 * S + 10 * rows + cols)
+    assert all_planted
+    dev = [torch.from_numpy(b).to(DEV) for b in batches]
+    assert all(d.data_ptr() % 16 == 0 for d in dev)
+    tab = (ctypes.c_void_p * cols)(*[d.data_ptr() for d in dev])
+    for gap in ((3, 0) if S == 128 else (3,)):
+        cell, band, strip = grid_units(rows, cols, S, gap)
+        assert cell > cap and (band > 0 and strip > 0) == (gap > 0)
+        got = torch.full(samples.canvas_shape(rows, cols, S, gap), 7, device=DEV, dtype=torch.uint8)
+        _lib.check(_lib.load().dg_sample_grid_u8(tab, cols, rows, S, gap, 255, got.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                   "dg_sample_grid_u8")
+        want = ref_canvas(batches, rows, S, gap, 255)
+        got = got.cpu().numpy()
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, f"S={S} {rows}x{cols} gap={gap}: {len(bad)} bytes differ, first at {bad[0]}"
 
 
 def test_grid_comparison_notices_a_misplaced_cell():

@@ -1,5 +1,8 @@
 """Sliced Wasserstein distance, the parts that need no GPU: the levels table, the reference's mirror filter against scipy, the draw's
 range and its independence from the other key chains, the patches-per-image rule, the CLI flags and the evaluation line."""
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -19,6 +22,31 @@ def test_levels_table(S):
     assert _lib.load().dg_swd_levels(S) == len(LEVELS[S])
     n = 3
     assert _lib.load().dg_lap_pyramid_elems(n, S) == sum(n * 3 * r * r for r in LEVELS[S])
+
+
+def test_shapes_past_the_grid_caps_reach_every_stride_loop():
+    """The launch arithmetic of dg_lap_pyramid and dg_swd_descriptors (csrc/swd.hip) at the shapes the GPU tests run past the caps, and
+    the constants swd_ref copies against the source."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "discogan_modernized_amd", "csrc", "swd.hip")).read()
+    assert int(re.search(r"#define SWD_PYR_MAX_BLOCKS (\d+)", src).group(1)) == R.PYR_MAX_BLOCKS
+    assert int(re.search(r"#define SWD_DESC_PER_BLOCK (\d+)", src).group(1)) == R.DESC_PER_BLOCK
+    assert "for (int i = threadIdx.x; i < nb; i += 256)" in src and R.SUM_THREADS == 256 and "const long b = (items + 255) / 256;" in src
+    cap = R.PYR_MAX_BLOCKS * R.PYR_THREADS
+    strided = [[(k, v, l, items) for k, v, l, items, _ in R.pyramid_launches(n, S) if items > cap] for n, S in R.PYRAMID_PAST_CAP]
+    assert strided == [[("lap", 4, 0, 4196352)], [("down", 1, 0, 4196280), ("lap", 1, 0, 16785120)],
+                       [("down", 4, 0, 4194816), ("lap", 4, 0, 16779264), ("lap", 4, 1, 4194816)]]
+    for n, S in R.PYRAMID_PAST_CAP:
+        assert all(items <= cap for _, _, _, items, _ in R.pyramid_launches(R.PYRAMID_CHUNK, S))      # the chunks do not stride
+        sel = R.pyramid_boundary_images(n, S)
+        assert 6 <= len(sel) <= 24 and sel[0] == 0 and sel[-1] == n - 1
+        for _, _, _, items, per in R.pyramid_launches(n, S):
+            for k in range(1, (items - 1) // cap + 1):
+                assert (k * cap - 1) // per in sel and (k * cap) // per in sel
+    assert R.pyramid_boundary_images(1366, 64) == [0, 1, 2, 683, 1363, 1364, 1365]
+    assert all(items <= cap for S in (16, 32, 34, 36, 64, 96) for _, _, _, items, _ in R.pyramid_launches(3, S))   # the older tests: one trip
+    max_row = _lib.load().dg_swd_max_row()
+    assert [(-(-n * P // R.DESC_PER_BLOCK), n * P <= max_row) for n, P in R.STATS_PAST_256] == [(257, True), (1024, True)]
+    assert 256 * 128 == max_row and -(-8 * 16 // R.DESC_PER_BLOCK) <= 16                   # the longest row; the older tests' 4 .. 16 partials
 
 
 def test_reference_filter_is_scipy_mirror():

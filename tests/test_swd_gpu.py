@@ -64,6 +64,47 @@ def test_pyramid_bits_do_not_depend_on_alignment_or_strides(S):
             assert torch.equal(_bits(a), _bits(b))
 
 
+def _pyramid_nan(x):
+    """dg_lap_pyramid into a buffer that starts as NaN (ops.lap_pyramid's is uninitialised): the list of levels."""
+    n, S = int(x.shape[0]), int(x.shape[3])
+    L = _lib.load()
+    out = torch.full((int(L.dg_lap_pyramid_elems(n, S)),), float("nan"), device=DEV)
+    assert x.is_contiguous() and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    _lib.check(L.dg_lap_pyramid(x.data_ptr(), n, S, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "dg_lap_pyramid")
+    levels, at = [], 0
+    for r in R.levels(S):
+        levels.append(out[at:at + n * 3 * r * r].view(n, 3, r, r))
+        at += n * 3 * r * r
+    return levels
+
+
+@pytest.mark.parametrize("n,S", R.PYRAMID_PAST_CAP)
+def test_pyramid_past_the_grid_cap(n, S):
+    """More items than SWD_PYR_MAX_BLOCKS x 256: the stride loops of swd_lap_kernel<4> (1366 x 64), swd_lap_kernel<1> and
+    swd_down_kernel<1> (4840 x 34), swd_down_kernel<4> (5462 x 64).  Every level equals, bit for bit, the pyramids of chunks of at most
+    512 images (which do not stride); the first and last image and the images either side of every trip boundary are held to float64."""
+    cap = R.PYR_MAX_BLOCKS * R.PYR_THREADS
+    strided = {(k, v) for k, v, _, items, _ in R.pyramid_launches(n, S) if items > cap}
+    assert strided == {(1366, 64): {("lap", 4)}, (4840, 34): {("lap", 1), ("down", 1)}, (5462, 64): {("lap", 4), ("down", 4)}}[(n, S)]
+    assert all(items <= cap for _, _, _, items, _ in R.pyramid_launches(R.PYRAMID_CHUNK, S))
+    sel = R.pyramid_boundary_images(n, S)
+    assert len(sel) >= 6 and sel[0] == 0 and sel[-1] == n - 1
+    x = torch.rand((n, 3, S, S), device=DEV, generator=torch.Generator(device=DEV).manual_seed(n + S))
+    x[sel] = _dev(R.make_set("mixed", len(sel), S, seed=S + n))
+    got = _pyramid_nan(x)
+    assert [tuple(g.shape) for g in got] == [(n, 3, r, r) for r in R.levels(S)]
+    for lo in range(0, n, R.PYRAMID_CHUNK):
+        part = _pyramid_nan(x[lo:lo + R.PYRAMID_CHUNK])
+        for l, (g, p) in enumerate(zip(got, part)):
+            assert torch.equal(_bits(g[lo:lo + R.PYRAMID_CHUNK]), _bits(p)), (lo, l)
+    xs = x[sel].cpu().numpy()
+    want, bound = R.pyramid(xs.astype(np.float64)), R.pyramid_bound(xs)
+    for l, (g, w, b) in enumerate(zip(got, want, bound)):
+        err = np.abs(g[sel].cpu().numpy().astype(np.float64) - w)
+        print(f"S={S} n={n} level {l}: {len(sel)} images, max err {err.max():.3e}, max err/bound {(err / np.maximum(b, 1e-300)).max():.3f}")
+        assert (err <= b).all()
+
+
 # ---- draw --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 5])
 @pytest.mark.parametrize("P", [1, 128])
@@ -122,6 +163,39 @@ def test_descriptors_clamp_hand_made_records():
     want = R.gather(lev.cpu().numpy(), recs.cpu().numpy())
     assert np.array_equal(desc.cpu().numpy().view(np.int32), want.view(np.int32))
     _stats_check(want, stats.cpu().numpy())
+
+
+@pytest.mark.parametrize("n,P", R.STATS_PAST_256)
+def test_statistics_with_more_partials_than_threads(n, P):
+    """nb = ceil(M / 32) > 256 block partials: the second (at M = DG_SWD_MAX_ROW the fourth) trip of swd_sum_parts, in every block of
+    swd_var_kernel and in swd_stats_kernel.  The last 32 descriptors -- the last partial, read on the last trip -- alone see a large
+    offset in channel 1: leaving them out moves the float64 mean and deviation by far more than the bounds, so a missed partial
+    cannot hide.  desc and stats start as NaN."""
+    Rl, M = 16, n * P
+    nb = -(-M // R.DESC_PER_BLOCK)
+    assert nb > R.SUM_THREADS and M <= MAX_ROW and nb == {257 * 32: 257, 256 * 128: 1024}[M] and (M == MAX_ROW) == (P == 128)
+    lev = R.make_set("mixed", n, Rl, seed=n + P)
+    lev[-1, 1, 9:] += 100.0                                          # rows 9 .. 15 of the last image's channel 1 ...
+    recs = ops.swd_draw(5, 2, n, Rl, P, device=DEV)
+    last = torch.arange(M - 32, M, device=DEV)
+    assert int(last[0]) // P == n - 1                                # ... which the last 32 descriptors read, and no other does
+    recs[-1, :, 0] = 0
+    recs.view(M, 2)[last, 0] = 9
+    desc = torch.full((M, 147), float("nan"), device=DEV)
+    stats = torch.full((3, 2), float("nan"), device=DEV, dtype=torch.float64)
+    ops.swd_descriptors(_dev(lev), recs, desc=desc, stats=stats)
+    want = R.gather(lev, recs.cpu().numpy())
+    assert np.array_equal(desc.cpu().numpy().view(np.int32), want.view(np.int32))
+    assert (want[:M - 32, 49:98] < 2).all() and (want[M - 32:, 49:98] > 99).all()
+    st = stats.cpu().numpy()
+    _stats_check(want, st)
+    d = want.astype(np.float64).reshape(-1, 3, R.CH)
+    N = M * R.CH
+    mean, std, mag = d[:, 1].mean(), d[:, 1].std(), np.abs(d[:, 1]).mean()
+    without = d[:M - 32, 1].sum() / N, np.sqrt(((d[:M - 32, 1] - mean) ** 2).sum() / N)
+    print(f"n={n} P={P}: without the last partial the mean moves by {abs(without[0] - mean):.3e} (bound {R.gamma(N, U64) * mag:.3e}), "
+          f"the deviation by {abs(without[1] - std):.3e} (bound {R.gamma(2 * N + 8, U64) * (std + mag):.3e})")
+    assert abs(without[0] - mean) > R.gamma(N, U64) * mag and abs(without[1] - std) > R.gamma(2 * N + 8, U64) * (std + mag)
 
 
 def test_flat_channel_gives_zeros():
