@@ -115,6 +115,10 @@ SIGNATURES = {
     "dg_bce_target_bwd": (_i, [_p, _p, _i, _p, _p, _p]),
     "dg_hinge_fwd": (_i, [_p, _p, _z, _f, _p, _p, _z, _p]),
     "dg_hinge_bwd": (_i, [_p, _p, _z, _f, _p, _p, _p]),
+    "dg_gan_loss_fwd": (_i, [_p, _i, _i, _i, _f, _p, _p]),
+    "dg_gan_loss_bwd": (_i, [_p, _i, _i, _i, _f, _p, _p, _p]),
+    "dg_gan_loss_fwd_g": (_i, [_i, _p, _i, _i, _p, _f, _p, _p]),
+    "dg_gan_loss_bwd_g": (_i, [_i, _p, _i, _i, _p, _f, _p, _p, _p]),
     "dg_dp_ready": (_i, [_p]),
     "dg_dp_unique_id_bytes": (_i, []),
     "dg_dp_get_unique_id": (_i, [_p, _z]),

@@ -11,6 +11,8 @@ buffer is all-reduced (sum, then divided by W inside the Adam kernel).  Rank 0 l
 (seed, rank, iteration, domain, role) -- the replicas see different augmentations of different batches, and the gradients are summed as usual.
 ``--recon_loss KIND`` (image_translation.py): every rank measures the reconstruction terms of its own batch with the criterion; it has no
 state, so there is nothing to exchange beside the gradients.
+``--gan_loss KIND`` / ``--gan_real_label`` (image_translation.py): likewise -- every rank measures the GAN terms of its own batch with the
+objective, and the gradients are summed as usual.
 """
 from __future__ import annotations
 

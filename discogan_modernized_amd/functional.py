@@ -418,6 +418,25 @@ class BCELossFn(Function):
         return ops.bce_bwd(pc, label, gout.contiguous()).reshape(shape), None, None
 
 
+class GanLossFn(Function):
+    """An adversarial objective on LOGITS (ops.gan_loss_fwd: kind, role and real_label as the library takes them); the loss lands in
+    ``out`` (a slot of the trainer's loss vector) if given."""
+
+    @_fwd
+    def forward(ctx, x, kind, role, real_label=1.0, out=None):
+        shape = x.shape
+        loss, xc = ops.gan_loss_fwd(x.reshape(-1), kind, role, real_label, out)
+        ctx.save_for_backward(xc)
+        ctx.cfg = (kind, role, real_label, shape)
+        return loss
+
+    @_bwd
+    def backward(ctx, gout):
+        (xc,) = ctx.saved_tensors
+        kind, role, real_label, shape = ctx.cfg
+        return ops.gan_loss_bwd(xc, kind, role, real_label, gout.contiguous()).reshape(shape), None, None, None, None
+
+
 class BCETargetLossFn(Function):
     """nn.BCELoss against a target TENSOR (no gradient w.r.t. the target), image_translation.py:157-166."""
 
@@ -775,6 +794,35 @@ class BCELossGroupFn(Function):
         for i, d in zip(live, dps):
             out[i] = d.reshape(ctx.shapes[i])
         return (None, None) + tuple(out) + (None,) * g
+
+
+class GanLossGroupFn(Function):
+    """GanLossFn of ``g`` logit vectors of one size under one kind and real label, each in its own role, in one launch.  The backward
+    launches the problems that received a gradient only.  args: x_0.., out_0.."""
+
+    @_fwd
+    def forward(ctx, g, kind, roles, real_label, *t):
+        xs, outs = list(t[:g]), list(t[g:2 * g])
+        ctx.shapes = [x.shape for x in xs]
+        xcs = ops.gan_loss_fwd_g([x.reshape(-1) for x in xs], kind, roles, real_label, outs)
+        ctx.g, ctx.cfg = g, (kind, tuple(roles), real_label)
+        ctx.save_for_backward(*xcs)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @_bwd
+    def backward(ctx, *gouts):
+        g = ctx.g
+        live = [i for i in range(g) if gouts[i] is not None]
+        if not live:
+            return (None,) * (4 + 2 * g)
+        kind, roles, real_label = ctx.cfg
+        xcs = ctx.saved_tensors
+        dxs = ops.gan_loss_bwd_g([xcs[i] for i in live], kind, [roles[i] for i in live], real_label, [gouts[i].contiguous() for i in live])
+        out = [None] * g
+        for i, d in zip(live, dxs):
+            out[i] = d.reshape(ctx.shapes[i])
+        return (None, None, None, None) + tuple(out) + (None,) * g
 
 
 class FeatureMatchGroupFn(Function):

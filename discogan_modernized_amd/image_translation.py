@@ -56,6 +56,14 @@ sigma 1.5, valid windows, that ``SSIM_ABA`` of the evaluation reports; needs ``-
 alpha (1 - SSIM) with ``--recon_ssim_alpha`` (default 0.84, Zhao et al. 2017).  One fused forward and one backward kernel per term
 (dg_recon_loss_fwd / dg_recon_loss_bwd) in the place of the MSE kernels: captured, replayed and resumed like them, nothing is saved, and
 the ``RECON:`` field of the log line prints the criterion's value.  With ``mse`` nothing changes.
+Adversarial objective: ``--gan_loss {bce,bce_logits,lsgan,hinge}`` (default ``bce``, the reference's nn.BCELoss on the sigmoid output)
+chooses what the six GAN terms are measured with.  The other three read the discriminators' LOGITS (the sigmoid is not launched):
+``bce_logits`` = the same cross entropy in its stable form (softplus; the gradient of a saturated logit stays accurate instead of coming
+from the -100 clamp), ``lsgan`` = mean (x - target)^2 (CycleGAN's), ``hinge`` = mean max(0, 1 -+ x) for the discriminators and -mean x
+for the generators (the DiffAugment baselines').  ``--gan_real_label`` (default 1.0, in (0.5, 1]) is the target of a discriminator's real
+batch (one-sided label smoothing; not with ``hinge``).  One fused forward and one backward kernel per term (dg_gan_loss_fwd /
+dg_gan_loss_bwd) in the place of the BCE kernels: captured, replayed and resumed like them, nothing is saved; ``GEN:`` / ``DIS:`` print
+the objective's values.
 
 Batch order.  Single process: A and B are shuffled independently every epoch (shuffle_data, dataset.py:24-35),
 ``data_size // batch_size`` batches.  Data parallel: the ``DistributedSampler`` contract of
@@ -76,7 +84,8 @@ from pathlib import Path
 
 import torch
 
-from .trainer import DiscoGANTrainer, check_diffaug, check_image_pool, check_recon_loss
+from .losses import GAN_KINDS
+from .trainer import DiscoGANTrainer, check_diffaug, check_gan_loss, check_image_pool, check_recon_loss
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -151,6 +160,11 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
                         "SSIM kinds need --image_size >= 11")
     p.add_argument("--recon_ssim_alpha", type=float, default=0.84,
                    help="with --recon_loss l1_ssim: the weight alpha of the SSIM term, in (0, 1) (Zhao et al. 2017: 0.84)")
+    p.add_argument("--gan_loss", type=str, default="bce", choices=list(GAN_KINDS),
+                   help="adversarial objective: bce (the reference's nn.BCELoss on the sigmoid output) or, on the discriminators' logits, "
+                        "bce_logits (the same in its stable form), lsgan ((x - target)^2, CycleGAN's) or hinge (max(0, 1 -+ x) | -x)")
+    p.add_argument("--gan_real_label", type=float, default=1.0,
+                   help="target of a discriminator's real batch, in (0.5, 1] (one-sided label smoothing, e.g. 0.9); hinge takes 1 only")
     p.add_argument("--synthetic_size", type=int, default=1024, help="images per domain when no data files are given")
     p.add_argument("--data_source", type=str, default="auto", choices=["auto", "files", "shards", "tensors", "synthetic"])
     p.add_argument("--data_root", type=str, default=None, help="root of the reference's dataset layout (dataset.py:14-22; default ./datasets)")
@@ -369,6 +383,7 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     diffaug = check_diffaug(getattr(args, "diffaug", ""))                   # likewise: an unknown --diffaug policy
     recon_loss = getattr(args, "recon_loss", "mse")                         # likewise: an SSIM criterion on images under 11 pixels
     recon_w = check_recon_loss(recon_loss, getattr(args, "recon_ssim_alpha", 0.84), args.image_size)
+    gan_loss, gan_real_label = check_gan_loss(getattr(args, "gan_loss", "bce"), getattr(args, "gan_real_label", 1.0))   # likewise: hinge with smoothing
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
     eval_swd = check_eval_swd(args)                                       # likewise: --eval_swd without --eval_interval
     if eval_interval > 0:
@@ -407,6 +422,8 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
         if recon_loss != "mse":
             print(f"reconstruction loss: {recon_loss} = {recon_w[0]:g} MSE + {recon_w[1]:g} L1 + {recon_w[2]:g} (1 - SSIM) on both cycle "
                   "terms (RECON: prints its value)", flush=True)
+        if gan_loss != "bce" or gan_real_label != 1.0:
+            print(f"adversarial loss: {gan_loss} (real label {gan_real_label:g})", flush=True)
     # the held-out split of the sample grids (samples.py) and of the evaluation (evaluate.py), resident on the device for the run; the
     # saving rank alone loads it, samples and evaluates
     split = None

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
+from . import ops
 
 
 class MSELoss(nn.Module):
@@ -82,6 +83,46 @@ class BCELoss(nn.Module):
         return F.BCELossFn.apply(input, label)
 
 
+GAN_KINDS = ("bce", "bce_logits", "lsgan", "hinge")
+GAN_KIND_CODES = {"bce_logits": ops.GAN_BCE_LOGITS, "lsgan": ops.GAN_LSGAN, "hinge": ops.GAN_HINGE}     # ("bce": the reference's sigmoid + BCELoss)
+GAN_ROLES = {"d_real": ops.GAN_D_REAL, "d_fake": ops.GAN_D_FAKE, "g_fake": ops.GAN_G_FAKE}
+
+
+def check_gan_loss(kind, real_label=1.0):
+    """The adversarial objective ``kind`` (one of GAN_KINDS) and the target ``real_label`` of a discriminator's real batch (one-sided
+    label smoothing: finite, in (0.5, 1]; the hinge has no target and takes 1 only).  Returns ``(kind, real_label as a float)``."""
+    if kind not in GAN_KINDS:
+        raise ValueError(f"unknown adversarial loss {kind!r} (one of {', '.join(GAN_KINDS)})")
+    try:
+        label = float(real_label)
+    except (TypeError, ValueError):
+        raise ValueError(f"gan_real_label must be a number in (0.5, 1], got {real_label!r}") from None
+    if not 0.5 < label <= 1.0:                              # (a NaN fails both comparisons)
+        raise ValueError(f"gan_real_label must be in (0.5, 1], got {real_label!r}")
+    if kind == "hinge" and label != 1.0:
+        raise ValueError(f"the hinge objective has no target to smooth: gan_real_label must be 1 with gan_loss 'hinge', got {real_label!r}")
+    return kind, label
+
+
+class GANLoss(nn.Module):
+    """An adversarial objective on a discriminator's LOGITS (``Discriminator(x, logits=True)``), called as ``(logits, role)`` with role
+    ``"d_real"`` (target ``real_label``), ``"d_fake"`` (target 0) or ``"g_fake"`` (target 1): ``bce_logits`` = binary cross entropy of
+    sigmoid(x) in its stable form, ``lsgan`` = mean (x - target)^2, ``hinge`` = mean max(0, 1 -+ x) for the discriminator and -mean x for
+    the generator (dg_gan_loss_fwd).  ``bce`` is not a kind of this module: it is ``BCELoss`` on the sigmoid output."""
+
+    def __init__(self, kind, real_label=1.0):
+        super().__init__()
+        kind, self.real_label = check_gan_loss(kind, real_label)
+        if kind == "bce":
+            raise ValueError("GANLoss works on logits: 'bce' is BCELoss() on the discriminator's sigmoid output (use 'bce_logits' here)")
+        self.kind = kind
+
+    def forward(self, logits, role):
+        if role not in GAN_ROLES:
+            raise ValueError(f"unknown role {role!r} (one of {', '.join(GAN_ROLES)})")
+        return F.GanLossFn.apply(logits, GAN_KIND_CODES[self.kind], GAN_ROLES[role], self.real_label)
+
+
 class HingeEmbeddingLoss(nn.Module):
     """nn.HingeEmbeddingLoss(margin=1.0) (mean reduction), targets in {+1, -1}.  The reference only calls it with
     all-ones targets (image_translation.py:141-142), where it is ``input.mean()`` (SURVEY.md Appendix C);
@@ -110,12 +151,15 @@ def get_fm_loss(real_feats, fake_feats, criterion=None, device=None):
 
 
 def get_gan_loss(dis_real, dis_fake, criterion, device=None):
-    """image_translation.py:146-168."""
+    """image_translation.py:146-168.  With a ``GANLoss`` criterion ``dis_real`` / ``dis_fake`` are the discriminator's LOGITS, and the
+    pair is ``(0.5 (D_REAL + D_FAKE), G_FAKE)``."""
     batch_size = dis_real.size(0)
     if len(dis_real.size()) > 2:
         dis_real = dis_real.view(batch_size, -1)
     if len(dis_fake.size()) > 2:
         dis_fake = dis_fake.view(batch_size, -1)
+    if isinstance(criterion, GANLoss):
+        return (criterion(dis_real, "d_real") + criterion(dis_fake, "d_fake")) * 0.5, criterion(dis_fake, "g_fake")
     dis_loss = (criterion(dis_real, 1.0) + criterion(dis_fake, 0.0)) * 0.5
     gen_loss = criterion(dis_fake, 1.0)
     return dis_loss, gen_loss

@@ -409,9 +409,10 @@ def group_generators(nets, xs, cut_at_bottleneck=False):
     return _group_layers([list(n_.decoder) for n_ in nets], leaves), hs, leaves
 
 
-def group_discriminators(nets, xs):
+def group_discriminators(nets, xs, logits=False):
     """[net(x) for ...] for discriminators of one architecture: list of (sigmoid output, feature maps).  A network may appear several
-    times (its real and its fake pass): those problems must be consecutive."""
+    times (its real and its fake pass): those problems must be consecutive.  ``logits=True``: the head convs' outputs as they are, no
+    sigmoid launch (the objectives of losses.GANLoss read them)."""
     g = len(xs)
     d0 = nets[0]
     hs = list(F.ConvC3GroupFn.apply(g, ops.ACT_LEAKY, d0.relu1.negative_slope, *xs, *[d.conv1.weight for d in nets]))
@@ -431,13 +432,14 @@ def group_discriminators(nets, xs):
             records[k].append((bns[k], ys[k], hs[k]))
     heads = [getattr(d, f"conv{d0.n_stages + 1}") for d in nets]
     ys = F.ConvGroupFn.apply(g, heads[0].stride, heads[0].padding, False, *hs, *[c.weight for c in heads])
-    outs = F.ActGroupFn.apply(g, ops.ACT_SIGMOID, 0.0, *ys)
+    outs = ys if logits else F.ActGroupFn.apply(g, ops.ACT_SIGMOID, 0.0, *ys)
     _fire_forward_hooks(records)
     return [(outs[k], feats[k]) for k in range(g)]
 
 
 class Discriminator(_FlatGradMixin, nn.Module):
-    """Reference model.py:5-69.  Returns ``(sigmoid [N,1,1,1], [relu2, ..., relu_n])``."""
+    """Reference model.py:5-69.  Returns ``(sigmoid [N,1,1,1], [relu2, ..., relu_n])``; with ``logits=True`` the first element is the
+    head conv's output in front of the sigmoid, and the sigmoid is not launched."""
 
     def __init__(self, image_size: int = 512):
         super().__init__()
@@ -453,10 +455,10 @@ class Discriminator(_FlatGradMixin, nn.Module):
         setattr(self, f"conv{len(ch) + 1}", Conv2d(cin, 1, 4, 1, 0, bias=False))
         self.sigmoid = Sigmoid()
 
-    def forward(self, input_tensor):
-        return drain(self.forward_steps(input_tensor))
+    def forward(self, input_tensor, logits=False):
+        return drain(self.forward_steps(input_tensor, logits))
 
-    def forward_steps(self, input_tensor):
+    def forward_steps(self, input_tensor, logits=False):
         """forward() as a generator that yields after every conv(+BN+act) group."""
         feats = []
         h = self.conv1(input_tensor, ops.ACT_LEAKY, self.relu1.negative_slope,
@@ -479,8 +481,8 @@ class Discriminator(_FlatGradMixin, nn.Module):
                 h = bn(y, ops.ACT_LEAKY, relu.negative_slope, st, False, dy_cm, False, dy_po)
             feats.append(h)
             yield
-        out = self.sigmoid(getattr(self, f"conv{self.n_stages + 1}")(h))
-        return out, feats
+        out = getattr(self, f"conv{self.n_stages + 1}")(h)
+        return (out if logits else self.sigmoid(out)), feats
 
 
 class Generator(_FlatGradMixin, nn.Module):

@@ -1458,6 +1458,27 @@ def bce_bwd(p, label, gout):
     return dp
 
 
+# Adversarial objectives on logits (dg_gan_loss_*): kind / role are the library's codes, real_label the target of the D_REAL role
+GAN_BCE_LOGITS, GAN_LSGAN, GAN_HINGE = 0, 1, 2
+GAN_D_REAL, GAN_D_FAKE, GAN_G_FAKE = 0, 1, 2
+
+
+def gan_loss_fwd(x, kind, role, real_label=1.0, out=None):
+    """mean_i f(x_i) of the logits ``x`` (include/discogan_hip.h: dg_gan_loss_fwd).  Returns (loss, the contiguous logits)."""
+    _check_dev(x)
+    x = x.contiguous()
+    loss = out if out is not None else torch.empty((), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().dg_gan_loss_fwd(_ptr(x), x.numel(), int(kind), int(role), float(real_label), _ptr(loss), _stream()), "dg_gan_loss_fwd")
+    return loss, x
+
+
+def gan_loss_bwd(x, kind, role, real_label, gout):
+    dx = torch.empty_like(x)
+    _lib.check(_lib.load().dg_gan_loss_bwd(_ptr(x), x.numel(), int(kind), int(role), float(real_label), _ptr(gout), _ptr(dx), _stream()),
+               "dg_gan_loss_bwd")
+    return dx
+
+
 def bce_target_fwd(p, target, out=None):
     _check_dev(p, target)
     p, target = p.contiguous(), target.contiguous()
@@ -1882,6 +1903,35 @@ def bce_bwd_g(ps, labels, gouts):
     dps = [torch.empty_like(p) for p in ps]
     _lib.check(_lib.load().dg_bce_bwd_g(len(ps), _tab(ps), ps[0].numel(), _labels(labels), _tab(gouts), _tab(dps), _stream()), "dg_bce_bwd_g")
     return dps
+
+
+def _roles(roles):
+    import ctypes as C
+    return (C.c_int * len(roles))(*[int(r) for r in roles])
+
+
+def _gan_group(what, xs, roles, others):
+    """One launch reads ``xs[0].numel()`` elements of every problem: the sizes must agree, with one role and one slot per problem."""
+    if len(roles) != len(xs) or len(others) != len(xs) or any(x.numel() != xs[0].numel() for x in xs):
+        raise ValueError(f"{what}: {len(xs)} logit vectors of sizes {[x.numel() for x in xs]}, {len(roles)} roles, {len(others)} scalars")
+
+
+def gan_loss_fwd_g(xs, kind, roles, real_label, outs):
+    _check_dev(*xs, *outs)
+    _gan_group("gan_loss_fwd_g", xs, roles, outs)
+    xs = [x.contiguous() for x in xs]
+    _lib.check(_lib.load().dg_gan_loss_fwd_g(len(xs), _tab(xs), xs[0].numel(), int(kind), _roles(roles), float(real_label), _tab(outs), _stream()),
+               "dg_gan_loss_fwd_g")
+    return xs
+
+
+def gan_loss_bwd_g(xs, kind, roles, real_label, gouts):
+    _check_dev(*xs, *gouts)
+    _gan_group("gan_loss_bwd_g", xs, roles, gouts)
+    dxs =[torch.empty_like(x) for x in xs]
+    _lib.check(_lib.load().dg_gan_loss_bwd_g(len(xs), _tab(xs), xs[0].numel(), int(kind), _roles(roles), float(real_label), _tab(gouts), _tab(dxs),
+                                             _stream()), "dg_gan_loss_bwd_g")
+    return dxs
 
 
 def fm_fwd_g(reals, fakes, outs):

@@ -47,7 +47,7 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
                 ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
-                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84)
+                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84, gan_loss="bce", gan_real_label=1.0)
 
 # The loss vector every term of an iteration is written into and dg_loss_mix_fwd / _bwd read (the layout is defined by the comment
 # above dg_loss_mix_fwd in include/discogan_hip.h): the two reconstruction terms, per discriminator BCE(real, 1), BCE(fake, 0),
@@ -58,6 +58,7 @@ FM0 = 8
 MIX_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")     # its out8
 WHICH_GEN, WHICH_DIS = 6, 7                # dg_loss_mix_bwd's ``which``: backward of gen_loss (out8[6]) / of dis_loss (out8[7])
 ARCH_CODES = {"discogan": 0, "recongan": 1, "gan": 2}
+D_REAL, D_FAKE, G_FAKE = ops.GAN_D_REAL, ops.GAN_D_FAKE, ops.GAN_G_FAKE         # the role of a GAN term (DG_GAN_*): which target it is held to
 PREC_OF = {"f32": ops.PREC_F32, "bf16": ops.PREC_BF16, "f32x3": ops.PREC_F32X3}
 
 
@@ -114,6 +115,11 @@ def check_recon_loss(kind, alpha, image_size):
     return w
 
 
+# ``gan_loss`` / ``gan_real_label``: the objective of the six GAN terms -- "bce" (the reference's nn.BCELoss on the sigmoid output) or, on the
+# discriminators' logits, "bce_logits", "lsgan", "hinge" -- and the target of a discriminator's real batch, in (0.5, 1] (1 with the hinge).
+check_gan_loss = L.check_gan_loss
+
+
 def format_grad_suffix(dis, gen):
     """The log suffix of gradient control from the two optimisers' ``grad_stats()``: each side's norm of its last step, then the
     counters of both sides together."""
@@ -156,6 +162,7 @@ class DiscoGANTrainer:
         grad_clip = check_grad_clip(self.args.grad_clip)
         self.recon_loss = self.args.recon_loss
         self.recon_w = check_recon_loss(self.recon_loss, self.args.recon_ssim_alpha, image_size)
+        self.gan_loss, self.gan_real_label = check_gan_loss(self.args.gan_loss, self.args.gan_real_label)
         guard, log_norm = bool(self.args.nonfinite_guard), bool(self.args.log_grad_norm)
         loss_slots(self.args.model_arch, True, 0)        # an unknown model_arch is refused here, before anything is allocated
         self.device = torch.device(device)
@@ -188,7 +195,12 @@ class DiscoGANTrainer:
         # MSELossGroupFn as ever.  Any other kind: one fused kernel pair per term (functional.ReconLossFn / ReconLossGroupFn,
         # csrc/recon.hip) in the same places on the same streams, capturable, stateless -- nothing to checkpoint or to exchange.
         self.recon_criterion = L.MSELoss() if self.recon_loss == "mse" else L.ReconLoss(self.recon_loss, self.args.recon_ssim_alpha)
-        self.gan_criterion = L.BCELoss()
+        # The objective of the six GAN terms (slots A_REAL1 .. B_FAKE1).  "bce": the reference's -- the discriminators end in their sigmoid
+        # and BCELossFn / BCELossGroupFn read it, as ever (gan_real_label only replaces the label 1 of the two *_REAL1 terms).  Any other
+        # kind: the discriminators return their head conv's LOGITS (no sigmoid launch) and GanLossFn / GanLossGroupFn (csrc/ganloss.hip)
+        # write the same slots in the same places on the same streams: capturable, stateless, nothing to checkpoint or to exchange.
+        self.gan_kind = None if self.gan_loss == "bce" else L.GAN_KIND_CODES[self.gan_loss]
+        self.gan_criterion = L.BCELoss() if self.gan_kind is None else L.GANLoss(self.gan_loss, self.gan_real_label)
         self.feat_criterion = L.HingeEmbeddingLoss()
         a = self.args
         self.optim_gen = optim.Adam(chain(self.generator_A.parameters(), self.generator_B.parameters()),
@@ -454,13 +466,14 @@ class DiscoGANTrainer:
         else:
             self._no_recon(lv, sl, terms)
         A_in, B_in, dis_inputs = A, B, None
+        logits = self.gan_kind is not None                   # an objective on logits: the discriminators skip their sigmoid
         if self.aug_A is not None:                           # the reals as the discriminators see them (no gradient is wanted of them)
             with torch.no_grad():
                 with on_side():
                     A_in = self.aug_A.apply(A)
                 B_in = self.aug_B.apply(B)
         (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = pair(
-            self.discriminator_A.forward_steps(A_in), self.discriminator_B.forward_steps(B_in))
+            self.discriminator_A.forward_steps(A_in, logits), self.discriminator_B.forward_steps(B_in, logits))
         # the fakes the discriminators see: in a D-step with a history pool the exchanged batches, each on its consumer's stream (BA was
         # produced on `side`, where D_A runs; AB on `main`, where D_B runs: no new join)
         BA_seen, AB_seen, seen = self._pooled_fakes(dstep, BA, AB, on_side)
@@ -471,23 +484,23 @@ class DiscoGANTrainer:
             AB_in = self.aug_AB.apply(AB_seen)
             dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
         (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = pair(
-            self.discriminator_A.forward_steps(BA_in), self.discriminator_B.forward_steps(AB_in))
+            self.discriminator_A.forward_steps(BA_in, logits), self.discriminator_B.forward_steps(AB_in, logits))
         assert nfm == len(A_feats_real)
 
-        def bce(p, label, k):
-            terms[k] = F_.BCELossFn.apply(p.reshape(p.size(0), -1), label, sl[k])
+        def gan(x, role, k):
+            terms[k], = self._gan_terms([x], [role], [sl[k]])
 
         with on_side():
             if want_recon:
                 with gen_ctx():
                     terms[RECON_A], = self._recon_terms([ABA], [A], [sl[RECON_A]])
-            bce(A_dis_real, 1.0, A_REAL1); bce(A_dis_fake, 0.0, A_FAKE0); bce(A_dis_fake, 1.0, A_FAKE1)
+            gan(A_dis_real, D_REAL, A_REAL1); gan(A_dis_fake, D_FAKE, A_FAKE0); gan(A_dis_fake, G_FAKE, A_FAKE1)
             for l, (r, f) in enumerate(zip(A_feats_real, A_feats_fake)):
                 terms[FM0 + l] = F_.FeatureMatchFn.apply(r, f, sl[FM0 + l])
         if want_recon:
             with gen_ctx():
                 terms[RECON_B], = self._recon_terms([BAB], [B], [sl[RECON_B]])
-        bce(B_dis_real, 1.0, B_REAL1); bce(B_dis_fake, 0.0, B_FAKE0); bce(B_dis_fake, 1.0, B_FAKE1)
+        gan(B_dis_real, D_REAL, B_REAL1); gan(B_dis_fake, D_FAKE, B_FAKE0); gan(B_dis_fake, G_FAKE, B_FAKE1)
         for l, (r, f) in enumerate(zip(B_feats_real, B_feats_fake)):
             terms[FM0 + nfm + l] = F_.FeatureMatchFn.apply(r, f, sl[FM0 + nfm + l])
         if self.two_streams:
@@ -551,6 +564,19 @@ class DiscoGANTrainer:
             return F_.MSELossGroupFn.apply(len(xs), *xs, *ts, *slots)
         return F_.ReconLossGroupFn.apply(len(xs), self.recon_w, *xs, *ts, *slots)
 
+    def _gan_terms(self, xs, roles, slots):
+        """The GAN terms of the discriminator outputs ``xs`` in their ``roles`` (D_REAL / D_FAKE / G_FAKE) into their slots of the loss
+        vector: one term on its own stream (two-chain schedule), or several as one grouped launch.  "bce": the reference's BCELoss of
+        the sigmoid outputs against the role's label (gan_real_label, 0, 1); any other kind: the objective on the logits."""
+        if self.gan_kind is None:
+            labels = tuple((self.gan_real_label, 0.0, 1.0)[r] for r in roles)
+            if len(xs) == 1:
+                return (F_.BCELossFn.apply(xs[0].reshape(xs[0].size(0), -1), labels[0], slots[0]),)
+            return F_.BCELossGroupFn.apply(len(xs), labels, *xs, *slots)
+        if len(xs) == 1:
+            return (F_.GanLossFn.apply(xs[0].reshape(xs[0].size(0), -1), self.gan_kind, roles[0], self.gan_real_label, slots[0]),)
+        return F_.GanLossGroupFn.apply(len(xs), self.gan_kind, tuple(roles), self.gan_real_label, *xs, *slots)
+
     def _pooled_fakes(self, dstep, BA, AB, ctx_for_BA=contextlib.nullcontext):
         """(BA_seen, AB_seen, seen): the fakes the discriminators see -- in a D-step with a history pool the exchanged batches (BA's
         exchange is issued under ``ctx_for_BA()``, AB's on the current stream), otherwise BA / AB themselves and seen = None."""
@@ -563,7 +589,9 @@ class DiscoGANTrainer:
 
     def _mix(self, lv, terms, iters, dstep, nfm, **tensors):
         """The tail of both schedules: the curriculum mix of the loss vector (one launch; its backward seeds the gradient of every term
-        in ``loss_slots``) and the iteration's namespace: the ten loss scalars, ``lossvec`` and the schedule's ``tensors``."""
+        in ``loss_slots``) and the iteration's namespace: the ten loss scalars, ``lossvec`` and the schedule's ``tensors``.  Among them
+        ``A_dis_real`` / ``A_dis_fake`` / ``B_dis_real`` / ``B_dis_fake`` are the discriminators' sigmoid outputs with ``gan_loss="bce"`` and
+        their LOGITS with every other objective."""
         arch, which, idx = loss_slots(self.args.model_arch, dstep, nfm)
         mixed = F_.LossMixFn.apply(lv, nfm, self.rate(iters), arch, which, idx, *[terms[i] for i in idx])
         return IterationOutputs(**dict(zip(MIX_KEYS, mixed)), recon_loss_A=terms[RECON_A], recon_loss_B=terms[RECON_B], lossvec=lv, **tensors)
@@ -607,6 +635,7 @@ class DiscoGANTrainer:
             self._no_recon(lv, sl, terms)
         dis_inputs = None
         aug = self.aug_A is not None
+        logits = self.gan_kind is not None                   # an objective on logits: the discriminators skip their sigmoid
         with on_side():
             BA_seen, AB_seen, seen = self._pooled_fakes(dstep, BA, AB)     # the history pool: both exchanges on the discriminators' stream
             if dstep:
@@ -614,23 +643,23 @@ class DiscoGANTrainer:
                 if aug:                                      # the four inputs of the group of four: one launch per pass
                     A_in, BA_in, B_in, AB_in = apply_group([self.aug_A, self.aug_BA, self.aug_B, self.aug_AB], [A, BA_seen, B, AB_seen])
                 (A_dis_real, A_feats_real), (A_dis_fake, A_feats_fake), (B_dis_real, B_feats_real), (B_dis_fake, B_feats_fake) = \
-                    group_discriminators([dA, dA, dB, dB], [A_in, BA_in, B_in, AB_in])
+                    group_discriminators([dA, dA, dB, dB], [A_in, BA_in, B_in, AB_in], logits)
             else:
                 A_in, BA_in, B_in, AB_in = A, BA, B, AB
                 with torch.no_grad():
                     if aug:
                         A_in, B_in = apply_group([self.aug_A, self.aug_B], [A, B])
-                    (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = group_discriminators([dA, dB], [A_in, B_in])
+                    (A_dis_real, A_feats_real), (B_dis_real, B_feats_real) = group_discriminators([dA, dB], [A_in, B_in], logits)
                 if aug:                                      # the gradient of the fakes flows back through the transform
                     BA_in, AB_in = apply_group([self.aug_BA, self.aug_AB], [BA, AB])
-                (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = group_discriminators([dA, dB], [BA_in, AB_in])
+                (A_dis_fake, A_feats_fake), (B_dis_fake, B_feats_fake) = group_discriminators([dA, dB], [BA_in, AB_in], logits)
             if aug:
                 dis_inputs = dict(A=A_in, BA=BA_in, B=B_in, AB=AB_in)
             # GAN terms (image_translation.py:157-166): bce(real, 1) and bce(fake, 1) of both sides in one launch, bce(fake, 0) in another
-            terms[A_REAL1], terms[A_FAKE1], terms[B_REAL1], terms[B_FAKE1] = F_.BCELossGroupFn.apply(
-                4, (1.0, 1.0, 1.0, 1.0), A_dis_real, A_dis_fake, B_dis_real, B_dis_fake,
-                sl[A_REAL1], sl[A_FAKE1], sl[B_REAL1], sl[B_FAKE1])
-            terms[A_FAKE0], terms[B_FAKE0] = F_.BCELossGroupFn.apply(2, (0.0, 0.0), A_dis_fake, B_dis_fake, sl[A_FAKE0], sl[B_FAKE0])
+            terms[A_REAL1], terms[A_FAKE1], terms[B_REAL1], terms[B_FAKE1] = self._gan_terms(
+                [A_dis_real, A_dis_fake, B_dis_real, B_dis_fake], [D_REAL, G_FAKE, D_REAL, G_FAKE],
+                [sl[A_REAL1], sl[A_FAKE1], sl[B_REAL1], sl[B_FAKE1]])
+            terms[A_FAKE0], terms[B_FAKE0] = self._gan_terms([A_dis_fake, B_dis_fake], [D_FAKE, D_FAKE], [sl[A_FAKE0], sl[B_FAKE0]])
             for l in range(nfm):
                 terms[FM0 + l], terms[FM0 + nfm + l] = F_.FeatureMatchGroupFn.apply(
                     2, A_feats_real[l], B_feats_real[l], A_feats_fake[l], B_feats_fake[l], sl[FM0 + l], sl[FM0 + nfm + l])

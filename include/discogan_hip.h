@@ -398,6 +398,30 @@ int dg_bce_target_bwd(const float* p, const float* target, int n, const float* g
  * reference's all-ones targets it is x.mean()).  ws >= dg_loss_workspace_bytes(). */
 int dg_hinge_fwd(const float* x, const float* y, size_t n, float margin, float* loss, void* ws, size_t ws_bytes, dg_stream_t s);
 int dg_hinge_bwd(const float* x, const float* y, size_t n, float margin, const float* gout, float* dx, dg_stream_t s);
+/* ---- adversarial objectives on LOGITS (trainer.py --gan_loss; csrc/ganloss.hip).  logit: float [n], the discriminator's head conv
+ * output in front of its sigmoid.  Per problem  loss = mean_i f(x_i)  and  dlogit_i = gout f'(x_i) / n  (gout a device scalar), with the
+ * target tau by role -- D_REAL: real_label (one-sided label smoothing, in (0.5, 1]), D_FAKE: 0, G_FAKE: 1 -- and by kind
+ *     BCE_LOGITS  f = tau sp(-x) + (1 - tau) sp(x)    f' = sigmoid(x) - tau     sp(x) = max(x, 0) + log1p(exp(-|x|))
+ *     LSGAN       f = (x - tau)^2                     f' = 2 (x - tau)          (no 1/2, as CycleGAN has it)
+ *     HINGE       D_REAL max(0, 1 - x), D_FAKE max(0, 1 + x), G_FAKE -x         f' = -[x < 1], +[x > -1], -1; 0 at the kink x = +-1
+ * sp and sigmoid are formed from exp(-|x|) (tau = 1: f' = -sigmoid(-x); tau = 0: sigmoid(x)), so a saturated logit keeps a relatively
+ * accurate, non-zero gradient; nothing is clamped.  HINGE takes real_label 1 only.  A NaN logit gives a NaN loss and a NaN in that
+ * element of dlogit, in every kind and role.  fwd: one workgroup per problem, fp64 partial sums in a fixed order, no atomics, no
+ * workspace: bitwise repeatable.  The *_g forms run `groups` (1..DG_MAX_GROUPS) problems of one (n, kind, real_label), each with its own
+ * role, in ONE launch, bitwise the single calls.  Refused with DG_ERR_INVALID and nothing launched: groups out of range, a null table or
+ * pointer, n < 1, an unknown kind or role, a real_label that is not finite or not in (0.5, 1], HINGE with real_label != 1. */
+#define DG_GAN_BCE_LOGITS 0
+#define DG_GAN_LSGAN 1
+#define DG_GAN_HINGE 2
+#define DG_GAN_D_REAL 0
+#define DG_GAN_D_FAKE 1
+#define DG_GAN_G_FAKE 2
+int dg_gan_loss_fwd(const float* logit, int n, int kind, int role, float real_label, float* loss, dg_stream_t s);
+int dg_gan_loss_bwd(const float* logit, int n, int kind, int role, float real_label, const float* gout, float* dlogit, dg_stream_t s);
+int dg_gan_loss_fwd_g(int groups, const float* const* logit, int n, int kind, const int* role /* host [groups] */, float real_label,
+                      float* const* loss, dg_stream_t s);
+int dg_gan_loss_bwd_g(int groups, const float* const* logit, int n, int kind, const int* role /* host [groups] */, float real_label,
+                      const float* const* gout, float* const* dlogit, dg_stream_t s);
 
 /* ---- data-parallel exchange group over RCCL / xGMI ---------------------------------------------
  * Replaces dist.init_process_group("nccl") (distributed_image_translation.py:31-38), DistributedDataParallel's
