@@ -143,6 +143,9 @@ SIGNATURES = {
     "dg_diffaug_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p]),
     "dg_diffaug_fwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _z, _p]),
     "dg_diffaug_bwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "dg_diffaug_draw_p": (_i, [C.c_uint64, _i, _l, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "dg_ada_accumulate": (_i, [_p, _i, _f, _p, _p]),
+    "dg_ada_update": (_i, [_p, _p, _d, _d, _d, _p]),
     "dg_sample_grid_u8":(_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "dg_image_metrics_workspace_bytes": (_z, [_i, _i]),
     "dg_image_metrics": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),

@@ -9,6 +9,8 @@ buffer is all-reduced (sum, then divided by W inside the Adam kernel).  Rank 0 l
 
 ``--diffaug POLICY`` (image_translation.py): every rank draws its own transforms of its own discriminator inputs, keyed on
 (seed, rank, iteration, domain, role) -- the replicas see different augmentations of different batches, and the gradients are summed as usual.
+``--ada_target T`` (image_translation.py): every rank counts the signs of its own real outputs; at the end of a window the ranks sum their
+windows (one 16-byte all-reduce behind the discriminators' gradient exchange, on the same stream), so every rank moves p alike.
 ``--recon_loss KIND`` (image_translation.py): every rank measures the reconstruction terms of its own batch with the criterion; it has no
 state, so there is nothing to exchange beside the gradients.
 ``--gan_loss KIND`` / ``--gan_real_label`` (image_translation.py): likewise -- every rank measures the GAN terms of its own batch with the
@@ -100,6 +102,9 @@ def main(argv=None):
         args.local_rank = int(os.environ["LOCAL_RANK"])
         args.distributed = True
         args.world_size = int(os.environ.get("WORLD_SIZE", args.world_size))
+    from .trainer import check_ada, check_diffaug
+    check_ada(check_diffaug(args.diffaug), args.diffaug_p, args.ada_target, args.ada_interval, args.ada_kimg, args.ada_p_max,
+              batch=args.batch_size, world=args.world_size if args.distributed else 1)       # refused before any device or group call
     main_worker(args.local_rank if args.distributed else 0, args)
 
 

@@ -49,7 +49,13 @@ front of everything a discriminator reads -- reals and fakes, D-steps and G-step
 generator (Zhao et al. 2020, DiffAugment; on images in [0, 1]: brightness amplitude halved, padding and cutout fill 0.5).  HIP kernels
 (dg_diffaug_fwd / dg_diffaug_bwd) on records drawn on the device from (seed, rank, iteration, domain, role): graph replay and ``--resume``
 reproduce the run bitwise and nothing is saved.  It goes behind the pool exchange; generators, reconstructions, sample grids, evaluation
-and the EMA never see it.
+and the EMA never see it.  ``--diffaug_p P`` applies each stage to a sample with probability P in [0, 1] instead of always (default 1.0;
+exactly 1.0 is the draw above).  ``--ada_target T`` (0 = off; in (0, 1), 0.6 is customary) adapts that probability during the run (Karras
+et al. 2020, ADA): every discriminator step adds the signs of its outputs on the real batch to a window, and every ``--ada_interval``-th
+(default 4) moves p by (real images of the window) / (1000 ``--ada_kimg``) (default 500) up when r_t = E[sign(D(real))] exceeds T, down when
+below, within [0, ``--ada_p_max``]; p starts from ``--diffaug_p`` (default 0 then).  One p per domain; p, the window and the controller live
+on the device (dg_diffaug_draw_p, dg_ada_accumulate, dg_ada_update), data-parallel ranks sum their windows in one 16-byte all-reduce, the
+state travels in ``train_state_*.pth`` (key ``ada``) and log lines end in `` ADA: p <pA>/<pB> rt <rtA>/<rtB>``.
 Reconstruction criterion: ``--recon_loss {mse,l1,ssim,l1_ssim}`` (default ``mse``, the reference's) chooses what the two cycle terms
 ABA against A and BAB against B are measured with: ``l1`` = mean |x - t| (CycleGAN), ``ssim`` = 1 - SSIM (the 11 x 11 Gaussian window,
 sigma 1.5, valid windows, that ``SSIM_ABA`` of the evaluation reports; needs ``--image_size >= 11``), ``l1_ssim`` = (1 - alpha) L1 +
@@ -85,7 +91,7 @@ from pathlib import Path
 import torch
 
 from .losses import GAN_KINDS
-from .trainer import DiscoGANTrainer, check_diffaug, check_gan_loss, check_image_pool, check_recon_loss
+from .trainer import DiscoGANTrainer, check_ada, check_diffaug, check_gan_loss, check_image_pool, check_recon_loss
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -154,6 +160,16 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--diffaug", type=str, default="",
                    help="comma list of 'color', 'translation', 'cutout': differentiable augmentation (DiffAugment) of every discriminator "
                         "input, reals and fakes, on the device, keyed on (seed, rank, iteration); empty or 'none' = off")
+    p.add_argument("--diffaug_p", type=float, default=None,
+                   help="with --diffaug: probability in [0, 1] that each stage of the policy is applied to a sample (drawn per sample and "
+                        "stage); default 1.0 (every stage on every sample), or with --ada_target the initial p, default 0.0")
+    p.add_argument("--ada_target", type=float, default=0.0,
+                   help="with --diffaug: adapt the probability on the device (ADA, Karras et al. 2020) so that the discriminators' "
+                        "overfitting measure r_t = E[sign(D(real))] approaches this target in (0, 1) (0.6 is customary); 0 = off")
+    p.add_argument("--ada_interval", type=int, default=4, help="with --ada_target: discriminator steps per update of p")
+    p.add_argument("--ada_kimg", type=float, default=500.0,
+                   help="with --ada_target: thousands of real images it takes p to travel from 0 to 1 (the step per image is 1 / (1000 kimg))")
+    p.add_argument("--ada_p_max", type=float, default=1.0, help="with --ada_target: the upper bound of p, in (0, 1]")
     p.add_argument("--recon_loss", type=str, default="mse", choices=["mse", "l1", "ssim", "l1_ssim"],
                    help="criterion of the two reconstruction (cycle) terms: mse (the reference's nn.MSELoss), l1 (CycleGAN's), ssim "
                         "(1 - SSIM, the 11 x 11 Gaussian window of the evaluation) or l1_ssim ((1 - alpha) L1 + alpha (1 - SSIM)); the "
@@ -381,6 +397,9 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
     aug = augment_of(args, rank)                          # a mistyped --augment token or a scale below 1 raises before anything is built
     image_pool = check_image_pool(getattr(args, "image_pool", 0))           # likewise: a negative --image_pool
     diffaug = check_diffaug(getattr(args, "diffaug", ""))                   # likewise: an unknown --diffaug policy
+    diffaug_p, ada = check_ada(diffaug, getattr(args, "diffaug_p", None), getattr(args, "ada_target", 0.0),     # likewise: --ada_target or
+                               getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0),             # --diffaug_p without --diffaug
+                               getattr(args, "ada_p_max", 1.0), batch=args.batch_size, world=world_size)
     recon_loss = getattr(args, "recon_loss", "mse")                         # likewise: an SSIM criterion on images under 11 pixels
     recon_w = check_recon_loss(recon_loss, getattr(args, "recon_ssim_alpha", 0.84), args.image_size)
     gan_loss, gan_real_label = check_gan_loss(getattr(args, "gan_loss", "bce"), getattr(args, "gan_real_label", 1.0))   # likewise: hinge with smoothing
@@ -419,6 +438,11 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
             from .diffaug import policy_names
             print(f"differentiable augmentation: {policy_names(diffaug)} on every discriminator input (reals and fakes, every step); "
                   "keyed on seed, rank and iteration; generators, reconstructions, samples and evaluation never see it", flush=True)
+            if ada is not None:
+                print(f"ADA: each stage with probability p, from {diffaug_p:g} within [0, {ada['p_max']:g}], moved on the device every "
+                      f"{ada['interval']} discriminator steps towards r_t = {ada['target']:g} ({ada['kimg']:g} kimg from 0 to 1)", flush=True)
+            elif diffaug_p is not None:
+                print(f"differentiable augmentation: each stage applied to a sample with probability {diffaug_p:g}", flush=True)
         if recon_loss != "mse":
             print(f"reconstruction loss: {recon_loss} = {recon_w[0]:g} MSE + {recon_w[1]:g} L1 + {recon_w[2]:g} (1 - SSIM) on both cycle "
                   "terms (RECON: prints its value)", flush=True)

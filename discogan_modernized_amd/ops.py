@@ -324,6 +324,49 @@ def diffaug_draw(seed, rank, iteration, domain, role, n, S, flags, out=None, dev
     return out[:n]
 
 
+ADA_MAX_OUTPUTS = 65536        # discriminator outputs per dg_ada_accumulate call
+
+
+def _check_ada_state(t, dtype, n, who, what):
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.numel() == n and t.is_contiguous()):
+        raise _lib.DiscoganHipError(f"{who} needs {what}")
+
+
+def diffaug_draw_p(seed, rank, iteration, domain, role, n, S, flags, p, out=None):
+    """diffaug_draw with every stage of the policy kept per sample with probability ``p[0]``: ``p`` is a float64 tensor ON THE DEVICE (a
+    view of an ADA control block, or any 1-element tensor) that the kernel reads -- the host never does (dg_diffaug_draw_p;
+    include/discogan_hip.h, "adaptive discriminator augmentation", defines the gate).  p = 1 gives diffaug_draw's table bit for bit."""
+    if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float64 and p.numel() >= 1 and p.is_contiguous()):
+        raise _lib.DiscoganHipError("diffaug_draw_p needs the probability as a contiguous float64 HIP tensor")
+    if out is None:
+        out = torch.empty((n, 8), device=p.device, dtype=torch.int32)
+    check_diffaug_table(out, n, "diffaug_draw_p")
+    _lib.check(_lib.load().dg_diffaug_draw_p(int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank), int(iteration), int(domain), int(role), int(n), int(S),
+                                             int(flags), _ptr(p), _ptr(out), _stream()), "dg_diffaug_draw_p")
+    return out[:n]
+
+
+def ada_accumulate(d_out, threshold, acc):
+    """Add the signs of one batch of discriminator outputs ``d_out`` (float32, any shape, 1..65536 values) against ``threshold`` to the
+    window ``acc`` = float32 [2] (sum of signs, count) on the device, in place (dg_ada_accumulate)."""
+    _check_dev(d_out, acc)
+    if not (d_out.dtype == torch.float32 and d_out.is_contiguous() and 1 <= d_out.numel() <= ADA_MAX_OUTPUTS):
+        raise _lib.DiscoganHipError(f"ada_accumulate needs 1..{ADA_MAX_OUTPUTS} contiguous float32 values, got {tuple(d_out.shape)} {d_out.dtype}")
+    _check_ada_state(acc, torch.float32, 2, "ada_accumulate", "the window as a contiguous float32 HIP tensor [2]")
+    _lib.check(_lib.load().dg_ada_accumulate(_ptr(d_out), int(d_out.numel()), float(threshold), _ptr(acc), _stream()), "dg_ada_accumulate")
+    return acc
+
+
+def ada_update(ctl, acc, target, step_per_image, p_max=1.0):
+    """Close the window ``acc`` (float32 [2]) into the control block ``ctl`` (float64 [8]: p, r_t, updates, images, last adjustment, 0, 0,
+    0), both on the device, in place: p moves by count x ``step_per_image`` towards more augmentation when r_t > ``target``, towards less
+    when below, clamped to [0, ``p_max``]; the window is zeroed.  An empty window changes nothing (dg_ada_update)."""
+    _check_ada_state(ctl, torch.float64, 8, "ada_update", "the control block as a contiguous float64 HIP tensor [8]")
+    _check_ada_state(acc, torch.float32, 2, "ada_update", "the window as a contiguous float32 HIP tensor [2]")
+    _lib.check(_lib.load().dg_ada_update(_ptr(ctl), _ptr(acc), float(target), float(step_per_image), float(p_max), _stream()), "dg_ada_update")
+    return ctl
+
+
 def _diffaug_g(name, xs, flags, recs, outs):
     """``len(xs)`` batches [n,3,S,S] of one shape through dg_diffaug_{fwd,bwd}[_g]: one launch per pass for all of them."""
     g = len(xs)

@@ -39,7 +39,7 @@ from . import ops
 from . import optim
 from .model import Discriminator, Generator, group_discriminators, group_generators
 from .pool import ImagePool
-from .diffaug import DiffAugment, apply_group, parse_policy
+from .diffaug import AdaController, DiffAugment, apply_group, fixed_p, format_ada_suffix, parse_policy
 
 LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A", "recon_loss_B",
             "dis_loss_A", "dis_loss_B", "gen_loss", "dis_loss")
@@ -47,7 +47,8 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
                 ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
-                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84, gan_loss="bce", gan_real_label=1.0)
+                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84, gan_loss="bce", gan_real_label=1.0,
+                diffaug_p=None, ada_target=0.0, ada_interval=4, ada_kimg=500.0, ada_p_max=1.0)
 
 # The loss vector every term of an iteration is written into and dg_loss_mix_fwd / _bwd read (the layout is defined by the comment
 # above dg_loss_mix_fwd in include/discogan_hip.h): the two reconstruction terms, per discriminator BCE(real, 1), BCE(fake, 0),
@@ -103,6 +104,52 @@ def check_diffaug(policy):
     """``diffaug``: "" (or "none") = off, else a comma-separated subset of color, translation, cutout (diffaug.parse_policy).  Returns the
     DG_DIFFAUG_* flags; raises ValueError on an unknown name."""
     return parse_policy(policy)
+
+
+ADA_WINDOW_LIMIT = 2 ** 24      # a window's two float32 fields are integer-valued: exact below this
+
+
+def check_ada(diffaug_flags, diffaug_p=None, ada_target=0.0, ada_interval=4, ada_kimg=500.0, ada_p_max=1.0, batch=None, world=1):
+    """The probability of the differentiable augmentation and its controller.  ``diffaug_p``: the probability every stage is applied to a
+    sample with, in [0, 1]; None = 1.0 without a controller, 0.0 (the initial p) with one.  ``ada_target``: 0 = no controller, else the
+    target of r_t = E[sign(D(real))] in (0, 1) (0.6 is customary) that p is moved by: every ``ada_interval`` discriminator steps, by
+    (real images of the window) / (1000 ``ada_kimg``), within [0, ``ada_p_max``].  Both need a ``diffaug`` policy.  ``batch`` (if known):
+    ``ada_interval x batch x world`` must stay below 2^24, where the window's float32 counters are exact.
+
+    Returns ``(p, ada)``: ``p`` None = dg_diffaug_draw (every stage on every sample) or the fixed / initial probability; ``ada`` None or
+    ``dict(target=, interval=, kimg=, p_max=)``."""
+    target = float(ada_target or 0.0)
+    if not (target == 0.0 or 0.0 < target < 1.0):
+        raise ValueError(f"ada_target must be 0 (off) or lie in (0, 1) (0.6 is customary), got {ada_target!r}")
+    if diffaug_p is not None:
+        diffaug_p = float(diffaug_p)
+        if not 0.0 <= diffaug_p <= 1.0:
+            raise ValueError(f"diffaug_p must lie in [0, 1], got {diffaug_p}")
+    if not diffaug_flags:
+        if target != 0.0:
+            raise ValueError("ada_target moves the probability of the differentiable augmentation: it needs a diffaug policy")
+        if diffaug_p is not None:
+            raise ValueError("diffaug_p is the probability of the differentiable augmentation: it needs a diffaug policy")
+        return None, None
+    if target == 0.0:
+        return (None if diffaug_p is None or diffaug_p == 1.0 else diffaug_p), None
+    if isinstance(ada_interval, bool) or not isinstance(ada_interval, numbers.Integral) or ada_interval < 1:
+        raise ValueError(f"ada_interval must be an integer >= 1 (discriminator steps per update), got {ada_interval!r}")
+    kimg, p_max = float(ada_kimg), float(ada_p_max)
+    if not 1e-3 <= kimg < float("inf"):
+        raise ValueError(f"ada_kimg must be >= 0.001 (thousands of real images for p to travel from 0 to 1), got {ada_kimg!r}")
+    if not 0.0 < p_max <= 1.0:
+        raise ValueError(f"ada_p_max must lie in (0, 1], got {ada_p_max!r}")
+    if batch is not None and int(ada_interval) * int(batch) * int(world) >= ADA_WINDOW_LIMIT:
+        raise ValueError(f"ada_interval x batch x world = {int(ada_interval) * int(batch) * int(world)} real images per window: the "
+                         f"window counters are exact below 2^24 only")
+    return (0.0 if diffaug_p is None else diffaug_p), dict(target=target, interval=int(ada_interval), kimg=kimg, p_max=p_max)
+
+
+def ada_threshold(gan_loss, gan_real_label=1.0):
+    """Where a discriminator's output changes sides for r_t: 0.5 on the sigmoid outputs of "bce", half the real target for "lsgan", 0 on
+    the logits of "bce_logits" and "hinge"."""
+    return {"bce": 0.5, "lsgan": float(gan_real_label) / 2.0}.get(gan_loss, 0.0)
 
 
 def check_recon_loss(kind, alpha, image_size):
@@ -241,9 +288,29 @@ class DiscoGANTrainer:
         # iteration, domain, role): nothing to checkpoint.  Generators, reconstruction passes, sampling, evaluation and the EMA never
         # see the transform.
         self.diffaug_flags = check_diffaug(self.args.diffaug)
+        # The probability of the transform (diffaug_p) and its controller (ada_target > 0; diffaug.AdaController: Karras et al. 2020).
+        # Every stage is applied to a sample with probability p, which the draw kernel reads from device memory: a constant, or the
+        # first field of the domain's control block -- aug_A and aug_BA (what D_A reads) share p_A, aug_B and aug_AB share p_B.  With a
+        # controller every discriminator step adds the signs of its own A_dis_real / B_dis_real against ada_threshold to the domain's
+        # window, and every ada_interval-th closes both windows (one 16-byte all-reduce of them under data parallelism) and moves p:
+        # eager launches directly behind that step's gradient exchange and Adam, on the same stream (_ada_step), never captured, never
+        # read by the host; the next iteration's draws are ordered behind them (_draw_ahead).  The captured graphs read the record
+        # tables only, so no graph key changes.  Unset (diffaug_p None or 1.0, ada_target 0): dg_diffaug_draw as ever.
+        p0, ada = check_ada(self.diffaug_flags, self.args.diffaug_p, self.args.ada_target, self.args.ada_interval, self.args.ada_kimg,
+                            self.args.ada_p_max)
+        self.ada = None
+        self._ada_real = self._ev_ada = None               # a D-step's real outputs until its apply_step; the event behind the update
+        self.ada_threshold = ada_threshold(self.gan_loss, self.gan_real_label)
         self.aug_A = self.aug_BA = self.aug_B = self.aug_AB = None
         if self.diffaug_flags:
-            mk = lambda domain, role: DiffAugment(self.diffaug_flags, image_size, stream_seed, rank, domain, role, device=self.device)  # noqa: E731
+            p_of = (None, None)
+            if ada is not None:
+                self.ada = AdaController(ada["target"], ada["interval"], ada["kimg"], ada["p_max"], p0, device=self.device)
+                p_of = (self.ada.p_view(0), self.ada.p_view(1))
+            elif p0 is not None:
+                p_of = (fixed_p(p0, self.device),) * 2
+            mk = lambda domain, role: DiffAugment(self.diffaug_flags, image_size, stream_seed, rank, domain, role,  # noqa: E731
+                                                  device=self.device, p=p_of[domain])
             self.aug_A, self.aug_BA, self.aug_B, self.aug_AB = mk(0, 0), mk(0, 1), mk(1, 0), mk(1, 1)
         self._graphs = {}
         self._static = None
@@ -808,10 +875,18 @@ class DiscoGANTrainer:
         """The device draws ahead of an iteration's dispatch, outside any capture.  With a history pool, in a D-step: the record tables
         of this iteration's two exchanges (BA = G_A(B) has B's batch size, AB = G_B(A) has A's).  With differentiable augmentation, in
         EVERY iteration: the four tables of the discriminators' inputs.  Eager launches on the current stream, which everything the
-        iteration issues -- eagerly or by graph replay -- is ordered behind."""
+        iteration issues -- eagerly or by graph replay -- is ordered behind.  With an ADA controller the draws read p from its control
+        block: they are ordered behind the update of the last D-step, also where that ran on the communication stream."""
         if self.pool_BA is not None and self.is_dis_step(iters):
             self.pool_BA.draw(iters, B.shape[0])
             self.pool_AB.draw(iters, A.shape[0])
+        if self.ada is not None:                              # (host arithmetic: the window counters stay exact)
+            check_ada(self.diffaug_flags, None, self.ada.target, self.ada.interval, self.ada.kimg, self.ada.p_max,
+                      batch=max(A.shape[0], B.shape[0]), world=self.world_size)
+        if self._ev_ada is not None:
+            # the controller's update of the last D-step may still be queued on the communication stream: the draws read its p
+            torch.cuda.current_stream(self.device).wait_event(self._ev_ada)
+            self._ev_ada = None
         if self.aug_A is not None:
             self.aug_A.draw(iters, A.shape[0])
             self.aug_BA.draw(iters, B.shape[0])
@@ -849,6 +924,7 @@ class DiscoGANTrainer:
             self._buckets.finish()
             self._ema_update(iters)                           # (finish() made the main stream wait for every bucket's update)
             return out
+        self._ada_note(out, dstep)
         if do_step:
             self.apply_step(iters)
         else:
@@ -869,11 +945,37 @@ class DiscoGANTrainer:
                 opt.step(grad_scale=scale, active=self.active_ranges(dstep))
                 self._ev_dis_ready = torch.cuda.Event()
                 self._ev_dis_ready.record(self.comm_stream)
+                self._ada_step(self.comm_stream)
             return
         scale = self._exchange(opt, "D" if dstep else "G")
         opt.step(grad_scale=scale, active=self.active_ranges(dstep))
-        if not dstep:
+        if dstep:
+            self._ada_step(None)
+        else:
             self._ema_update(iters)
+
+    def _ada_note(self, out, dstep):
+        """A D-step's discriminator outputs on its real batches, kept for the controller until that step's ``apply_step``."""
+        if self.ada is not None and dstep:
+            self._ada_real = (out.A_dis_real, out.B_dis_real)
+
+    def _ada_step(self, comm_stream):
+        """The controller's part of a discriminator step, on the current stream directly behind that step's gradient exchange and Adam:
+        both windows take the signs of the step's real outputs, and every ada_interval-th step closes them (all-reduce of the 16 bytes
+        first, so every rank enqueues the collectives of the one communicator in the same order).  ``comm_stream``: the stream this
+        runs on when it is not the main one -- the outputs were produced elsewhere, and the next draws wait for the event."""
+        if self.ada is None or self._ada_real is None:
+            return
+        reals, self._ada_real = self._ada_real, None
+        for domain, t in enumerate(reals):
+            t = t.detach()
+            if comm_stream is not None:
+                t.record_stream(comm_stream)
+            self.ada.accumulate(domain, t if t.dtype == torch.float32 else t.float(), self.ada_threshold)
+        self.ada.step(self.xg)
+        if comm_stream is not None:
+            self._ev_ada = torch.cuda.Event()
+            self._ev_ada.record(comm_stream)
 
     def _ema_update(self, iters):
         """Behind a generator Adam step that is ordered before this point on the current (main) stream."""
@@ -895,6 +997,7 @@ class DiscoGANTrainer:
             out = self._fwd_bwd_graphed(A, B, iters, need_losses)
         else:
             out = self._fwd_bwd(A, B, iters, need_losses)
+        self._ada_note(out, dstep)
         if not do_step:
             opt.fill_unwritten_grads()
             return out
@@ -922,6 +1025,8 @@ class DiscoGANTrainer:
     def finish(self):
         """Join the communication stream (call before reading parameters / saving / timing)."""
         self._wait_dis_ready(torch.cuda.current_stream(self.device), keep=True)     # (kept: the next forward's streams wait on their own)
+        if self._ev_ada is not None:                      # the controller's update behind it (kept for the next draws alike)
+            torch.cuda.current_stream(self.device).wait_event(self._ev_ada)
 
     def sample(self, test_A, test_B):
         """The four generator passes of a sampling event on the held-out split (image_translation.py:170-184):
@@ -991,7 +1096,15 @@ class DiscoGANTrainer:
                 f"GEN: {f['gen_loss_A']:.4f}/{f['gen_loss_B']:.4f}, "
                 f"FM: {f['fm_loss_A']:.4f}/{f['fm_loss_B']:.4f}, "
                 f"RECON: {f['recon_loss_A']:.4f}/{f['recon_loss_B']:.4f}, "
-                f"DIS: {f['dis_loss_A']:.4f}/{f['dis_loss_B']:.4f}" + self.grad_log_suffix())
+                f"DIS: {f['dis_loss_A']:.4f}/{f['dis_loss_B']:.4f}" + self.grad_log_suffix() + self.ada_log_suffix())
+
+    def ada_log_suffix(self):
+        """With the controller: `` ADA: p {pA}/{pB} rt {rtA}/{rtB}`` from the two control blocks (read here, where the host waits for
+        the losses anyway; rt is nan before the first update); without: the empty string."""
+        if self.ada is None:
+            return ""
+        self.finish()
+        return format_ada_suffix(self.ada.stats())
 
     def grad_log_suffix(self):
         """With gradient control: `` GRAD: D {norm} G {norm} clipped {c}/{n} skipped {s}`` from the two control blocks (read here, where
@@ -1017,6 +1130,8 @@ class DiscoGANTrainer:
             st["ema"] = self.ema.state_dict()
         if self.pool_BA is not None:
             st["image_pool"] = dict(BA=self.pool_BA.state_dict(), AB=self.pool_AB.state_dict())
+        if self.ada is not None:
+            st["ada"] = self.ada.state_dict()
         if extra:
             st["loader"] = dict(extra)
         return st
@@ -1040,6 +1155,13 @@ class DiscoGANTrainer:
                 self.pool_AB.clear()
                 print(f"image pool: the loaded training state holds no image_pool; both pools ({self.pool_BA.size} images per domain) "
                       "start empty", flush=True)
+        if self.ada is not None:
+            self._ada_real = None
+            if "ada" in st:
+                self.ada.load_state_dict(st["ada"])
+            else:                                  # a state written without the controller: p starts from its initial value
+                self.ada.reset()
+                print(f"ADA: the loaded training state holds no ada entry; p starts from {self.ada.p0:g} with empty windows", flush=True)
         self._graphs = {}
         start = int(st["iters"])
         # like a fresh run, the first D,G,G cycle after a resume is dispatched eagerly before anything is captured

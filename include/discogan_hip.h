@@ -566,6 +566,39 @@ int dg_diffaug_fwd_g(int groups, const float* const* x, float* const* z, int n, 
                      void* const* ws, size_t ws_bytes, dg_stream_t s);
 int dg_diffaug_bwd_g(int groups, const float* const* dz, float* const* dx, int n, int S, int flags, const int32_t* const* recs,
                      void* const* ws, size_t ws_bytes, dg_stream_t s);
+/* ---- adaptive discriminator augmentation (Karras et al., NeurIPS 2020, "ADA"): p, r_t and the controller on the device ----------------
+ * Every stage of the differentiable augmentation is applied to a sample with a probability p, and a controller moves p by an overfitting
+ * measure of the discriminator, r_t = E[sign(D(real) - threshold)], towards a target.  p, the window of signs and the controller live in
+ * device memory: the host never reads them to drive a launch.  State per discriminator:
+ *   ctl: device double[8], 8-byte aligned = (p, r_t of the last closed window (NaN before the first), updates done, real outputs counted
+ *        in total, the last adjustment, 0, 0, 0);
+ *   acc: device float[2] = (window sum of signs, window count).  Both are integer-valued: exact below 2^24, and a SUM all-reduce of them
+ *        over data-parallel ranks is order-independent.
+ *
+ * dg_diffaug_draw_p fills the table of dg_diffaug_draw with each stage in `flags` kept, per sample and independently, with probability
+ * (float)*p (one rounding of the device double, read BY THE KERNEL).  The gate words come from one more link of dg_diffaug_draw's key
+ * chain (the per-sample stride of q_1..q_4 is 4, so they are no further q_i):
+ *   k2 = mix(k ^ 0x6164610000000000);  g_1 = mix(k2 + G (2j + 1));  g_2 = mix(k2 + G (2j + 2));
+ *   u_color = unit(hi g_1);  u_translation = unit(lo g_1);  u_cutout = unit(hi g_2);       a stage is kept iff u < (float)p,
+ * so p = 1 keeps every stage (the table is dg_diffaug_draw's bit for bit) and p = 0 keeps none.  A stage that is not kept writes its
+ * neutral fields: colour (0.0f, 1.0f, 1.0f), translation (0, 0), cutout (cx0, cy0) = (S, S) -- an EMPTY square, because the apply kernels
+ * still evaluate the stage.  Arguments are refused as by dg_diffaug_draw; p must be non-null and 8-byte aligned.
+ *
+ * dg_ada_accumulate adds one batch of discriminator outputs to a window: acc[0] += sum over i < n of ((v_i > thr) - (v_i < thr)),
+ * acc[1] += n.  The sign comes from the two comparisons: a NaN and v == thr add 0 to the sum and 1 to the count.  1 <= n <= 65536; ONE
+ * workgroup, integer partials in a fixed tree, no atomics, one lane updates acc.  thr: 0.5 on sigmoid outputs, 0 on logits
+ * (real label / 2 for the least-squares objective).
+ *
+ * dg_ada_update closes a window, in one lane.  acc[1] == 0: nothing changes.  Otherwise, in this order, every operation rounded once:
+ *   rt = double(acc[0]) / double(acc[1]);   adj = double(acc[1]) step_per_image;
+ *   a = +adj if rt > target, -adj if rt < target, 0 if equal;   p = min(p_max, max(0, p + a));
+ *   ctl[1] = rt;  ctl[2] += 1;  ctl[3] += acc[1];  ctl[4] = a;   acc[0] = acc[1] = 0.
+ * -1 < target < 1, 0 <= step_per_image <= 1, 0 <= p_max <= 1. */
+int dg_diffaug_draw_p(uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S, int flags,
+                      const double* p /* device, 8-byte aligned */, int32_t* recs /* device [n][8] */, dg_stream_t s);
+int dg_ada_accumulate(const float* d_out, int n, float threshold, float* acc /* device [2] */, dg_stream_t s);
+int dg_ada_update(double* ctl /* device [8] */, float* acc /* device [2] */, double target, double step_per_image, double p_max,
+                  dg_stream_t s);
 /* ---- sample grids (image_translation.py:170-209): the inverse of the ingest, tiled -------------------------
    src: HOST table of `cols` device pointers, each a float batch [n_c][3][S][S] (NCHW, n_c >= rows).
    canvas: device uint8 [Hc][Wc][3], Hc = rows*(S+gap)+gap, Wc = cols*(S+gap)+gap.
