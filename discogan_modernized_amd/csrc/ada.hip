@@ -3,87 +3,13 @@
 // controller that moves p towards a target r_t, all in device memory.  include/discogan_hip.h ("adaptive discriminator augmentation")
 // defines the state, the gate words and the order of the controller's operations; tests/ada_ref.py restates them in numpy.
 //
-// Three kernels, none of them a hot path.  diffaug_draw_p_kernel is diffaug.hip's draw with each stage of a sample kept with probability
-// (float)*p, read from device memory by the kernel.  ada_accumulate_kernel adds the signs of one batch of discriminator outputs to a
-// window: ONE block, integer partials, a fixed tree, no atomics.  ada_update_kernel closes a window: one lane.
+// Two kernels, neither a hot path.  ada_accumulate_kernel adds the signs of one batch of discriminator outputs to a window: ONE block,
+// integer partials, a fixed tree, no atomics.  ada_update_kernel closes a window: one lane.  The draw that reads p (dg_diffaug_draw_p:
+// each stage of a sample kept with probability (float)*p, read from device memory by the kernel) is the GATED form of diffaug.hip's one
+// record builder and lives there.
 #include "dg_common.h"
 
-// ---- the draw's generator, as in diffaug.hip (one text each: a table drawn here with p = 1 is dg_diffaug_draw's bit for bit) ---------
-__host__ __device__ __forceinline__ uint64_t ada_mix(uint64_t z) {       // the SplitMix64 output function
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-#define ADA_G 0x9E3779B97F4A7C15ull
-#define ADA_DIFF_LINK 0x6469666600000000ull       // "diff": the link of dg_diffaug_draw's key
-#define ADA_GATE_LINK 0x6164610000000000ull       // "ada": one more link behind it, for the gate words
-#define ADA_MAX_BATCH 4096                        // DG_DIFFAUG_MAX_BATCH
-#define ADA_MAX_SIZE 32768                        // DG_DIFFAUG_MAX_SIZE
 #define ADA_MAX_OUTPUTS 65536                     // values of one dg_ada_accumulate call
-
-static inline int ada_T(int S) { return (S + 4) / 8; }                    // floor(S / 8 + 0.5)
-__device__ __forceinline__ int ada_cs(int S) { return (S + 1) / 2; }      // floor(S / 2 + 0.5)
-__device__ __forceinline__ int ada_range(uint32_t w, int lo, uint32_t count) { return lo + (int)(((uint64_t)w * count) >> 32); }
-__device__ __forceinline__ float ada_unit(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }
-
-__global__ __launch_bounds__(256) void diffaug_draw_p_kernel(uint64_t key, uint64_t key2, int n, int S, int T, int flags,
-                                                             const double* __restrict__ p_dev, int* __restrict__ recs) {
-    const float p = (float)*p_dev;                                      // one rounding; u < p: p = 1 keeps every stage, p = 0 (or NaN) none
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
-        const uint64_t q1 = ada_mix(key + ADA_G * (4ull * (uint64_t)j + 1ull)), q2 = ada_mix(key + ADA_G * (4ull * (uint64_t)j + 2ull));
-        const uint64_t q3 = ada_mix(key + ADA_G * (4ull * (uint64_t)j + 3ull)), q4 = ada_mix(key + ADA_G * (4ull * (uint64_t)j + 4ull));
-        const uint64_t g1 = ada_mix(key2 + ADA_G * (2ull * (uint64_t)j + 1ull)), g2 = ada_mix(key2 + ADA_G * (2ull * (uint64_t)j + 2ull));
-        const bool keep_color = ada_unit((uint32_t)(g1 >> 32)) < p, keep_trans = ada_unit((uint32_t)g1) < p;
-        const bool keep_cut = ada_unit((uint32_t)(g2 >> 32)) < p;
-        int4 a, b;
-        a.x = a.y = a.z = a.w = 0;
-        float fb = 0.0f, fs = 1.0f, fc = 1.0f;
-        if ((flags & DG_DIFFAUG_COLOR) && keep_color) {
-            fb = (ada_unit((uint32_t)(q1 >> 32)) - 0.5f) * 0.5f;
-            fs = 2.0f * ada_unit((uint32_t)q1);
-            fc = ada_unit((uint32_t)(q2 >> 32)) + 0.5f;
-        }
-        if ((flags & DG_DIFFAUG_TRANSLATION) && keep_trans) {
-            a.x = ada_range((uint32_t)q2, -T, 2u * (uint32_t)T + 1u);
-            a.y = ada_range((uint32_t)(q3 >> 32), -T, 2u * (uint32_t)T + 1u);
-        }
-        if (flags & DG_DIFFAUG_CUTOUT) {
-            if (keep_cut) {
-                const int cs = ada_cs(S);
-                const uint32_t count = (uint32_t)S + 1u - (uint32_t)(cs & 1);
-                a.z = ada_range((uint32_t)q3, 0, count) - cs / 2;
-                a.w = ada_range((uint32_t)(q4 >> 32), 0, count) - cs / 2;
-            } else {
-                a.z = a.w = S;                                          // the apply kernels still evaluate the stage: an empty square
-            }
-        }
-        b.x = __float_as_int(fb); b.y = __float_as_int(fs); b.z = __float_as_int(fc); b.w = 0;
-        reinterpret_cast<int4*>(recs)[2 * j] = a;
-        reinterpret_cast<int4*>(recs)[2 * j + 1] = b;
-    }
-}
-
-extern "C" int dg_diffaug_draw_p(uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S, int flags, const double* p,
-                                 int32_t* recs, dg_stream_t s) {
-    DG_CHECK_ARG(recs != nullptr, "dg_diffaug_draw_p: null record table");
-    DG_CHECK_ARG(((uintptr_t)recs & 15) == 0, "dg_diffaug_draw_p: the record table must be 16-byte aligned");
-    DG_CHECK_ARG(p != nullptr, "dg_diffaug_draw_p: null probability pointer");
-    DG_CHECK_ARG(((uintptr_t)p & 7) == 0, "dg_diffaug_draw_p: the probability (a device double) must be 8-byte aligned");
-    DG_CHECK_ARG(n >= 1 && n <= ADA_MAX_BATCH, "dg_diffaug_draw_p: 1 <= n <= %d samples per batch, got %d", ADA_MAX_BATCH, n);
-    DG_CHECK_ARG(S >= 2 && S <= ADA_MAX_SIZE, "dg_diffaug_draw_p: 2 <= S <= %d, got %d", ADA_MAX_SIZE, S);
-    DG_CHECK_ARG((flags & ~DG_DIFFAUG_ALL) == 0, "dg_diffaug_draw_p: unknown policy flags %d", flags);
-    DG_CHECK_ARG(rank >= 0 && iteration >= 0 && (domain == 0 || domain == 1) && (role == 0 || role == 1),
-                 "dg_diffaug_draw_p: rank >= 0, iteration >= 0, domain 0 (A) or 1 (B), role 0 (real) or 1 (fake)");
-    uint64_t k = ada_mix(seed + ADA_G);
-    k = ada_mix(k ^ (((uint64_t)(uint32_t)rank << 32) | (uint64_t)(uint32_t)domain));
-    k = ada_mix(k ^ (uint64_t)iteration);
-    k = ada_mix(k ^ (ADA_DIFF_LINK | (uint64_t)(uint32_t)role));
-    const uint64_t k2 = ada_mix(k ^ ADA_GATE_LINK);
-    hipLaunchKernelGGL(diffaug_draw_p_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, k, k2, n, S, ada_T(S), flags, p, recs);
-    DG_CHECK_LAUNCH("diffaug_draw_p");
-    return DG_OK;
-}
 
 __device__ __forceinline__ int ada_wave_sum_i(int v) {
 #pragma unroll

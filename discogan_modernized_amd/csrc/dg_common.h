@@ -86,6 +86,28 @@ __device__ __forceinline__ float dg_block_sum256(float v, float* red /*>=4 float
     return r;
 }
 
+// fp64 block sums for blockDim.x == 256 (4 waves): the wave sum of each of the N values, lane 0 of every wave to red[c][wave]; a barrier
+// before (the previous use of red is read: item loops) and after.  The four wave sums of value c are then added by ONE of the two
+// combiners below -- every site keeps the order it was written with, which its bits depend on: pairwise in metrics, recon, swd,
+// diffaug and optim, sequential in loss and ganloss.
+template <int N>
+__device__ __forceinline__ void dg_block_stage_d(double (&a)[N], double (*red)[4]) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) a[c] = dg_wave_sum_d(a[c]);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) red[c][threadIdx.x >> 6] = a[c];
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void dg_block_stage_d(double v, double* red /*4 doubles LDS*/) {      // one value
+    double a[1] = {v};
+    dg_block_stage_d(a, (double (*)[4])red);
+}
+__device__ __forceinline__ double dg_sum4_pair(const double* r) { return (r[0] + r[1]) + (r[2] + r[3]); }
+__device__ __forceinline__ double dg_sum4_seq(const double* r) { return r[0] + r[1] + r[2] + r[3]; }
+
 __device__ __forceinline__ float dg_apply_act(float u, int act, float slope) {
     if (act == DG_ACT_LEAKY) return u > 0.f ? u : u * slope;
     if (act == DG_ACT_RELU) return u > 0.f ? u : 0.f;

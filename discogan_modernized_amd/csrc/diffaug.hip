@@ -2,22 +2,19 @@
 // images in [0, 1].  include/discogan_hip.h ("differentiable augmentation") defines the transform, its adjoint, the draw and the record
 // table; tests/diffaug_ref.py restates them in numpy next to the published function.
 //
-// Three kernels.  diffaug_draw_kernel fills a record table (eight int32 per sample) from a key.  diffaug_stats_kernel, with
+// Three kernels.  diffaug_draw_kernel fills a record table (eight int32 per sample) from a key of dg_draw.h's generator (four words per
+// record); its GATED form (dg_diffaug_draw_p: adaptive augmentation, ada.hip) keeps each stage of a sample with probability (float)*p,
+// read from device memory, by three gate words from one more link of the key -- one record builder, so a table drawn with p = 1 is
+// dg_diffaug_draw's bit for bit.  diffaug_stats_kernel, with
 // DG_DIFFAUG_COLOR only, leaves per sample `parts(S)` fp64 partial sums (forward: of x; backward: of the gathered gradient g, summed where
 // it comes from) in the workspace: a fixed partition of the sample, a fixed order inside a block, no atomics.  diffaug_apply_kernel
 // is the one pass over the data: every block works on ONE sample (blockIdx.y), adds that sample's partials in a fixed tree, and then
 // gathers.  Forward and backward are the same gather with the shift negated: out(p) = in(p + d) where p + d is inside the image and the
 // cut test -- on p in the forward, on p + d in the backward -- passes, else the fill (0.5 forward, 0 backward).
-#include "dg_common.h"
+#include "dg_draw.h"
 
-__host__ __device__ __forceinline__ uint64_t da_mix(uint64_t z) {        // the SplitMix64 output function, as ingest.hip's aug_mix
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-#define DA_G 0x9E3779B97F4A7C15ull
 #define DA_LINK 0x6469666600000000ull             // "diff" in the high word; the role sits in the low one
+#define DA_GATE_LINK 0x6164610000000000ull        // "ada": one more link behind it, for the gate words
 #define DG_DIFFAUG_MAX_BATCH 4096
 #define DG_DIFFAUG_MAX_SIZE 32768                 // 3 S S stays far below 2^63 and a row index below 2^31
 #define DA_MAX_PARTS 64                           // one lane of a wave per partial in the apply kernel's tree
@@ -36,30 +33,42 @@ static inline long da_chunk(int S) {
     return ((E + p - 1) / p + 3) / 4 * 4;
 }
 
-__device__ __forceinline__ int da_range(uint32_t w, int lo, uint32_t count) { return lo + (int)(((uint64_t)w * count) >> 32); }
-__device__ __forceinline__ float da_unit(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }
-
-__global__ __launch_bounds__(256) void diffaug_draw_kernel(uint64_t key, int n, int S, int T, int flags, int* __restrict__ recs) {
+// GATED: stage kept where its gate word's unit float u < p, p = (float)*p_dev (one rounding): p = 1 keeps every stage, p = 0 (or NaN) none
+template <bool GATED>
+__global__ __launch_bounds__(256) void diffaug_draw_kernel(uint64_t key, uint64_t key2, int n, int S, int T, int flags,
+                                                           const double* __restrict__ p_dev, int* __restrict__ recs) {
+    const float p = GATED ? (float)*p_dev : 1.0f;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
-        const uint64_t q1 = da_mix(key + DA_G * (4ull * (uint64_t)j + 1ull)), q2 = da_mix(key + DA_G * (4ull * (uint64_t)j + 2ull));
-        const uint64_t q3 = da_mix(key + DA_G * (4ull * (uint64_t)j + 3ull)), q4 = da_mix(key + DA_G * (4ull * (uint64_t)j + 4ull));
+        const uint64_t q1 = dg_mix(key + DG_DRAW_G * (4ull * (uint64_t)j + 1ull)), q2 = dg_mix(key + DG_DRAW_G * (4ull * (uint64_t)j + 2ull));
+        const uint64_t q3 = dg_mix(key + DG_DRAW_G * (4ull * (uint64_t)j + 3ull)), q4 = dg_mix(key + DG_DRAW_G * (4ull * (uint64_t)j + 4ull));
+        bool keep_color = true, keep_trans = true, keep_cut = true;
+        if (GATED) {
+            const uint64_t g1 = dg_mix(key2 + DG_DRAW_G * (2ull * (uint64_t)j + 1ull)), g2 = dg_mix(key2 + DG_DRAW_G * (2ull * (uint64_t)j + 2ull));
+            keep_color = dg_draw_unit((uint32_t)(g1 >> 32)) < p;
+            keep_trans = dg_draw_unit((uint32_t)g1) < p;
+            keep_cut = dg_draw_unit((uint32_t)(g2 >> 32)) < p;
+        }
         int4 a, b;
         a.x = a.y = a.z = a.w = 0;
         float fb = 0.0f, fs = 1.0f, fc = 1.0f;
-        if (flags & DG_DIFFAUG_COLOR) {
-            fb = (da_unit((uint32_t)(q1 >> 32)) - 0.5f) * 0.5f;
-            fs = 2.0f * da_unit((uint32_t)q1);
-            fc = da_unit((uint32_t)(q2 >> 32)) + 0.5f;
+        if ((flags & DG_DIFFAUG_COLOR) && keep_color) {
+            fb = (dg_draw_unit((uint32_t)(q1 >> 32)) - 0.5f) * 0.5f;
+            fs = 2.0f * dg_draw_unit((uint32_t)q1);
+            fc = dg_draw_unit((uint32_t)(q2 >> 32)) + 0.5f;
         }
-        if (flags & DG_DIFFAUG_TRANSLATION) {
-            a.x = da_range((uint32_t)q2, -T, 2u * (uint32_t)T + 1u);
-            a.y = da_range((uint32_t)(q3 >> 32), -T, 2u * (uint32_t)T + 1u);
+        if ((flags & DG_DIFFAUG_TRANSLATION) && keep_trans) {
+            a.x = dg_draw_range((uint32_t)q2, -T, 2u * (uint32_t)T + 1u);
+            a.y = dg_draw_range((uint32_t)(q3 >> 32), -T, 2u * (uint32_t)T + 1u);
         }
         if (flags & DG_DIFFAUG_CUTOUT) {
-            const int cs = da_cs(S);
-            const uint32_t count = (uint32_t)S + 1u - (uint32_t)(cs & 1);
-            a.z = da_range((uint32_t)q3, 0, count) - cs / 2;
-            a.w = da_range((uint32_t)(q4 >> 32), 0, count) - cs / 2;
+            if (keep_cut) {
+                const int cs = da_cs(S);
+                const uint32_t count = (uint32_t)S + 1u - (uint32_t)(cs & 1);
+                a.z = dg_draw_range((uint32_t)q3, 0, count) - cs / 2;
+                a.w = dg_draw_range((uint32_t)(q4 >> 32), 0, count) - cs / 2;
+            } else {
+                a.z = a.w = S;                                          // the apply kernels still evaluate the stage: an empty square
+            }
         }
         b.x = __float_as_int(fb); b.y = __float_as_int(fs); b.z = __float_as_int(fc); b.w = 0;
         reinterpret_cast<int4*>(recs)[2 * j] = a;
@@ -67,22 +76,35 @@ __global__ __launch_bounds__(256) void diffaug_draw_kernel(uint64_t key, int n, 
     }
 }
 
+// both draw entry points; p: the device probability of the gated form, else NULL
+static int da_draw(const char* who, bool gated, uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S,
+                   int flags, const double* p, int32_t* recs, dg_stream_t s) {
+    DG_CHECK_ARG(recs != nullptr, "%s: null record table", who);
+    DG_CHECK_ARG(((uintptr_t)recs & 15) == 0, "%s: the record table must be 16-byte aligned", who);
+    DG_CHECK_ARG(!gated || p != nullptr, "%s: null probability pointer", who);
+    DG_CHECK_ARG(((uintptr_t)p & 7) == 0, "%s: the probability (a device double) must be 8-byte aligned", who);
+    DG_CHECK_ARG(n >= 1 && n <= DG_DIFFAUG_MAX_BATCH, "%s: 1 <= n <= %d samples per batch, got %d", who, DG_DIFFAUG_MAX_BATCH, n);
+    DG_CHECK_ARG(S >= 2 && S <= DG_DIFFAUG_MAX_SIZE, "%s: 2 <= S <= %d, got %d", who, DG_DIFFAUG_MAX_SIZE, S);
+    DG_CHECK_ARG((flags & ~DG_DIFFAUG_ALL) == 0, "%s: unknown policy flags %d", who, flags);
+    DG_CHECK_ARG(rank >= 0 && iteration >= 0 && (domain == 0 || domain == 1) && (role == 0 || role == 1),
+                 "%s: rank >= 0, iteration >= 0, domain 0 (A) or 1 (B), role 0 (real) or 1 (fake)", who);
+    const uint64_t k = dg_mix(dg_draw_key(seed, rank, iteration, domain) ^ (DA_LINK | (uint64_t)(uint32_t)role));
+    const dim3 grid((n + 255) / 256);
+    if (gated)
+        hipLaunchKernelGGL(diffaug_draw_kernel<true>, grid, dim3(256), 0, (hipStream_t)s, k, dg_mix(k ^ DA_GATE_LINK), n, S, da_T(S), flags, p, recs);
+    else
+        hipLaunchKernelGGL(diffaug_draw_kernel<false>, grid, dim3(256), 0, (hipStream_t)s, k, (uint64_t)0, n, S, da_T(S), flags, p, recs);
+    DG_CHECK_LAUNCH(who + 3);                                           // the kernel's name: who without "dg_"
+    return DG_OK;
+}
+
 extern "C" int dg_diffaug_draw(uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S, int flags, int32_t* recs,
                                dg_stream_t s) {
-    DG_CHECK_ARG(recs != nullptr, "dg_diffaug_draw: null record table");
-    DG_CHECK_ARG(((uintptr_t)recs & 15) == 0, "dg_diffaug_draw: the record table must be 16-byte aligned");
-    DG_CHECK_ARG(n >= 1 && n <= DG_DIFFAUG_MAX_BATCH, "dg_diffaug_draw: 1 <= n <= %d samples per batch, got %d", DG_DIFFAUG_MAX_BATCH, n);
-    DG_CHECK_ARG(S >= 2 && S <= DG_DIFFAUG_MAX_SIZE, "dg_diffaug_draw: 2 <= S <= %d, got %d", DG_DIFFAUG_MAX_SIZE, S);
-    DG_CHECK_ARG((flags & ~DG_DIFFAUG_ALL) == 0, "dg_diffaug_draw: unknown policy flags %d", flags);
-    DG_CHECK_ARG(rank >= 0 && iteration >= 0 && (domain == 0 || domain == 1) && (role == 0 || role == 1),
-                 "dg_diffaug_draw: rank >= 0, iteration >= 0, domain 0 (A) or 1 (B), role 0 (real) or 1 (fake)");
-    uint64_t k = da_mix(seed + DA_G);
-    k = da_mix(k ^ (((uint64_t)(uint32_t)rank << 32) | (uint64_t)(uint32_t)domain));
-    k = da_mix(k ^ (uint64_t)iteration);
-    k = da_mix(k ^ (DA_LINK | (uint64_t)(uint32_t)role));
-    hipLaunchKernelGGL(diffaug_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, k, n, S, da_T(S), flags, recs);
-    DG_CHECK_LAUNCH("diffaug_draw");
-    return DG_OK;
+    return da_draw("dg_diffaug_draw", false, seed, rank, iteration, domain, role, n, S, flags, nullptr, recs, s);
+}
+extern "C" int dg_diffaug_draw_p(uint64_t seed, int rank, int64_t iteration, int domain, int role, int n, int S, int flags, const double* p,
+                                 int32_t* recs, dg_stream_t s) {
+    return da_draw("dg_diffaug_draw_p", true, seed, rank, iteration, domain, role, n, S, flags, p, recs, s);
 }
 
 // What the kernels keep of one record: the shift of the gather (64-bit: any int32 is safe), the cut square, the factors.
@@ -155,10 +177,8 @@ __global__ __launch_bounds__(256) void diffaug_stats_kernel(const DaStatArgs A) 
         }
         acc += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
     }
-    acc = dg_wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) dg_pick<double>(A.ws, grp)[j * A.parts + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    dg_block_stage_d(acc, red);
+    if (threadIdx.x == 0) dg_pick<double>(A.ws, grp)[j * A.parts + blockIdx.x] = dg_sum4_pair(red);
 }
 
 struct DaApplyArgs {

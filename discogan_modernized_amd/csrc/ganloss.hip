@@ -58,10 +58,8 @@ __global__ __launch_bounds__(256) void gan_loss_fwd_kernel(const DgPtrs xs, int 
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += (double)gan_term(kind, role, tau, x[i]);
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / n);
+    dg_block_stage_d(s, red);
+    if (threadIdx.x == 0) loss[0] = (float)(dg_sum4_seq(red) / n);
 }
 
 __global__ __launch_bounds__(256) void gan_loss_bwd_kernel(const DgPtrs xs, int n, int kind, const DgGanRoles roles, float real_label,

@@ -14,7 +14,7 @@
 //      float64 at cv2.resize (255. - image), so its result is not rounded to uint8 -- neither is this one.
 //   1  8-bit fixed point, cv2's CV_8U path: coefficients round(2048 a) as int16, rows S0 a0 + S1 a1 (int32), output
 //      (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2, a uint8; then / 255 (correctly rounded fp32 division).
-#include "dg_common.h"
+#include "dg_draw.h"
 
 struct PrepArgs {
     const uint8_t* src;
@@ -121,32 +121,20 @@ extern "C" int dg_image_prep(const uint8_t* src, float* dst, int N, int H, int W
 // and the interpolation below at that coordinate with scale = cw / L and H / L.  image_prep_kernel above stays as it is; prep_pixel restates
 // its arithmetic expression by expression, and the result is bitwise dg_image_prep at L, sliced and flipped (tests/test_augment_gpu.py).
 //
-// The per-sample record (ox, oy, flip, 0) comes from a table dg_augment_draw fills on the device.  The draw is a pure function of
-// (seed, rank, iteration, domain, position in the batch) -- no generator state, so a resumed run continues the same sequence and the grouping
-// of a mixed-size batch into launches does not matter.  Definition (all arithmetic modulo 2^64; mix = the SplitMix64 output function of
-// Steele, Lea & Flood 2014, G = 0x9E3779B97F4A7C15):
-//   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
-//   k = mix(seed + G);   k = mix(k ^ (uint64(uint32(rank)) << 32 | uint32(domain)));   k = mix(k ^ uint64(iteration))
+// The per-sample record (ox, oy, flip, 0) comes from a table dg_augment_draw fills on the device: dg_draw.h's generator (its key, two
+// words per record, range) with
 //   a = mix(k + G * (2 j + 1));   b = mix(k + G * (2 j + 2))                 (j = position in the batch)
 //   w0 = a >> 32,  w1 = a & 0xFFFFFFFF,  w2 = b >> 32
 //   flip = w0 >> 31;   ox = (uint64(w1) * (L - S + 1)) >> 32;   oy = (uint64(w2) * (L - S + 1)) >> 32
 // flip is 0 without DG_AUG_FLIP, both offsets are 0 without DG_AUG_CROP.  tests/augment_ref.py restates this in numpy.
-__host__ __device__ __forceinline__ uint64_t aug_mix(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-#define AUG_G 0x9E3779B97F4A7C15ull
-
 __global__ __launch_bounds__(256) void augment_draw_kernel(uint64_t key, int n, uint32_t range, int flags, int* __restrict__ recs) {
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
-        const uint64_t a = aug_mix(key + AUG_G * (2ull * (uint64_t)j + 1ull)), b = aug_mix(key + AUG_G * (2ull * (uint64_t)j + 2ull));
+        const uint64_t a = dg_mix(key + DG_DRAW_G * (2ull * (uint64_t)j + 1ull)), b = dg_mix(key + DG_DRAW_G * (2ull * (uint64_t)j + 2ull));
         const uint32_t w0 = (uint32_t)(a >> 32), w1 = (uint32_t)a, w2 = (uint32_t)(b >> 32);
         const bool crop = (flags & DG_AUG_CROP) != 0;
         int4 r;
-        r.x = crop ? (int)(((uint64_t)w1 * range) >> 32) : 0;
-        r.y = crop ? (int)(((uint64_t)w2 * range) >> 32) : 0;
+        r.x = crop ? dg_draw_range(w1, 0, range) : 0;
+        r.y = crop ? dg_draw_range(w2, 0, range) : 0;
         r.z = (flags & DG_AUG_FLIP) ? (int)(w0 >> 31) : 0;
         r.w = 0;
         reinterpret_cast<int4*>(recs)[j] = r;                    // one 16-byte store per record
@@ -162,12 +150,10 @@ extern "C" int dg_augment_draw(uint64_t seed, int rank, int64_t iteration, int d
     DG_CHECK_ARG(rank >= 0 && iteration >= 0 && (domain == 0 || domain == 1), "dg_augment_draw: rank >= 0, iteration >= 0, domain 0 (A) or 1 (B)");
     DG_CHECK_ARG((flags & ~(DG_AUG_FLIP | DG_AUG_CROP)) == 0, "dg_augment_draw: flags is a sum of DG_AUG_FLIP and DG_AUG_CROP, got %d", flags);
     if (n == 0) return DG_OK;
-    uint64_t k = aug_mix(seed + AUG_G);
-    k = aug_mix(k ^ (((uint64_t)(uint32_t)rank << 32) | (uint64_t)(uint32_t)domain));
-    k = aug_mix(k ^ (uint64_t)iteration);
     int g = (n + 255) / 256;
     if (g > 1024) g = 1024;
-    hipLaunchKernelGGL(augment_draw_kernel, dim3(g), dim3(256), 0, (hipStream_t)s, k, n, (uint32_t)(L - S + 1), flags, recs);
+    hipLaunchKernelGGL(augment_draw_kernel, dim3(g), dim3(256), 0, (hipStream_t)s, dg_draw_key(seed, rank, iteration, domain), n,
+                       (uint32_t)(L - S + 1), flags, recs);
     DG_CHECK_LAUNCH("augment_draw");
     return DG_OK;
 }

@@ -17,18 +17,14 @@ __global__ __launch_bounds__(256) void final_sum_kernel(const DgPtrs parts, int 
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)((red[0] + red[1] + red[2] + red[3]) * scale);
+    dg_block_stage_d(s, red);
+    if (threadIdx.x == 0) out[0] = (float)(dg_sum4_seq(red) * scale);
 }
 
 __device__ __forceinline__ void block_partial_store(float v, double* part) {
     __shared__ double red[4];
-    double d = dg_wave_sum_d((double)v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    dg_block_stage_d((double)v, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = dg_sum4_seq(red);
 }
 
 __global__ __launch_bounds__(256) void mse_partial_kernel(const DgPtrs xs, const DgPtrs ts, long n, const DgPtrs parts) {
@@ -75,10 +71,8 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const DgPtrs ps, int n, co
         const float l1 = fmaxf(logf(v), -100.f), l0 = fmaxf(logf(1.f - v), -100.f);
         s += (double)((label - 1.f) * l0 - label * l1);
     }
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / n);
+    dg_block_stage_d(s, red);
+    if (threadIdx.x == 0) loss[0] = (float)(dg_sum4_seq(red) / n);
 }
 __global__ __launch_bounds__(256) void bce_bwd_kernel(const DgPtrs ps, int n, const DgLabels labels, const DgPtrs gouts, const DgPtrs dps) {
     const float* __restrict__ p = dg_pick<const float>(ps, blockIdx.y);
@@ -102,10 +96,8 @@ __global__ __launch_bounds__(256) void bce_target_fwd_kernel(const float* __rest
         const float l1 = fmaxf(logf(v), -100.f), l0 = fmaxf(logf(1.f - v), -100.f);
         s += (double)((y - 1.f) * l0 - y * l1);
     }
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / n);
+    dg_block_stage_d(s, red);
+    if (threadIdx.x == 0) loss[0] = (float)(dg_sum4_seq(red) / n);
 }
 __global__ __launch_bounds__(256) void bce_target_bwd_kernel(const float* __restrict__ p, const float* __restrict__ t, int n,
                                                              const float* __restrict__ gout, float* __restrict__ dp) {

@@ -318,21 +318,17 @@ __global__ __launch_bounds__(256) void grad_sumsq_partial_kernel(const float* __
     double s = (a[0] + a[1]) + (a[2] + a[3]);
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (long e = n4 * 4; e < n; ++e) s += (double)g[e] * (double)g[e];
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    dg_block_stage_d(s, red);
+    if (threadIdx.x == 0) ws[blockIdx.x] = dg_sum4_pair(red);
 }
 __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ ws, int slots, double pre_scale,
                                                                  double max_norm, int guard, double* __restrict__ ctl) {
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < slots; i += 256) s += ws[i];
-    s = dg_wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    dg_block_stage_d(s, red);
     if (threadIdx.x != 0) return;
-    const double sumsq = (red[0] + red[1]) + (red[2] + red[3]);
+    const double sumsq = dg_sum4_pair(red);
     const double norm = sqrt(sumsq) * pre_scale;
     double scale = pre_scale;
     bool clipped = false;

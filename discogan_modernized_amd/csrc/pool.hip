@@ -8,15 +8,9 @@
 // thread then writes pool[slot] = x[st_src] at the same element offset.  In a drawn table only the FIRST toucher of a slot carries its
 // store, the stored image is the LAST toucher's, and no slot is read by one record and written by another -- so no element of the pool is
 // touched by two threads, and the one thread that both reads and writes an element reads first.
-#include "dg_common.h"
+// The draws are dg_draw.h's generator: its key with one more link, one word per sample.
+#include "dg_draw.h"
 
-__host__ __device__ __forceinline__ uint64_t pool_mix(uint64_t z) {      // the SplitMix64 output function, as ingest.hip's aug_mix
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-#define POOL_G 0x9E3779B97F4A7C15ull
 #define POOL_LINK 0x706F6F6Cull                  // "pool": the extra link of the key chain that keeps pool draws apart from augmentation draws
 #define DG_POOL_MAX_BATCH 4096
 
@@ -24,8 +18,8 @@ __host__ __device__ __forceinline__ uint64_t pool_mix(uint64_t z) {      // the 
 __device__ __forceinline__ int pool_touch(uint64_t key, int i, uint32_t P, int filled, bool* insert) {
     *insert = (long)filled + i < (long)P;
     if (*insert) return filled + i;
-    const uint64_t a = pool_mix(key + POOL_G * ((uint64_t)i + 1ull));
-    return (a >> 63) ? (int)(((uint64_t)(uint32_t)a * P) >> 32) : -1;
+    const uint64_t a = dg_mix(key + DG_DRAW_G * ((uint64_t)i + 1ull));
+    return (a >> 63) ? dg_draw_range((uint32_t)a, 0, P) : -1;
 }
 
 // One thread per sample; every thread re-evaluates the draws of the other samples to find prev(j) = the last earlier toucher of its slot
@@ -61,10 +55,7 @@ extern "C" int dg_pool_draw(uint64_t seed, int rank, int64_t iteration, int doma
     DG_CHECK_ARG(filled >= 0 && filled <= P, "dg_pool_draw: filled = %d outside [0, P = %d]", filled, P);
     DG_CHECK_ARG(n >= 1 && n <= DG_POOL_MAX_BATCH, "dg_pool_draw: 1 <= n <= %d samples per batch, got %d", DG_POOL_MAX_BATCH, n);
     DG_CHECK_ARG(rank >= 0 && iteration >= 0 && (domain == 0 || domain == 1), "dg_pool_draw: rank >= 0, iteration >= 0, domain 0 (A) or 1 (B)");
-    uint64_t k = pool_mix(seed + POOL_G);
-    k = pool_mix(k ^ (((uint64_t)(uint32_t)rank << 32) | (uint64_t)(uint32_t)domain));
-    k = pool_mix(k ^ (uint64_t)iteration);
-    k = pool_mix(k ^ POOL_LINK);
+    const uint64_t k = dg_mix(dg_draw_key(seed, rank, iteration, domain) ^ POOL_LINK);
     hipLaunchKernelGGL(pool_draw_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, k, n, (uint32_t)P, filled, recs);
     DG_CHECK_LAUNCH("pool_draw");
     return DG_OK;

@@ -1,16 +1,12 @@
 // Trainable reconstruction criterion (include/discogan_hip.h, "reconstruction loss"): for float NCHW batches x (the reconstruction) and
 // t (the real image) of [n][3][S][S] and weights (w_mse, w_l1, w_ssim) >= 0
 //   loss = w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ssim (1 - mean over n 3 (S - 10)^2 valid windows of SSIM)
-// with SSIM exactly the quantity of metrics.hip (11-tap sigma 1.5 Gaussian normalised in double and rounded once, C1 = 0.01^2, C2 = 0.03^2),
-// and its gradient with respect to x.  The reference trains on nn.MSELoss only (image_translation.py:267,349-350); this is the CycleGAN
-// (L1) and the restoration (SSIM + L1, Zhao et al. 2017) choice of the same term.
+// with SSIM exactly the quantity of dg_image_metrics: both run the one stencil of ssim_tile.h (window, constants, tile geometry and the
+// moments about a per-tile constant are written there), and its gradient with respect to x.  The reference trains on nn.MSELoss only
+// (image_translation.py:267,349-350); this is the CycleGAN (L1) and the restoration (SSIM + L1, Zhao et al. 2017) choice of the same term.
 //
-// Forward.  w_ssim > 0: the tile form of metrics.hip -- one 256-thread block per 32 x 32 tile of one channel of one image stages the
-// 42 x 42 halo of x and t in LDS (16-byte loads when S % 4 == 0 and the batches are 16-byte aligned, scalar loads otherwise), sums its own
-// pixels' (x - t)^2 and |x - t| (4 per thread, pairwise, fp32), runs the horizontal and then the vertical 11-tap pass over the five
-// moment planes taken about a per-tile constant (x' = x - cx, cx = the pixel at the halo's centre clamped into the image: variances do
-// not depend on it and a flat region does not cancel), and hands three fp64 block sums to the workspace: [3][n P] doubles per problem,
-// P = 3 ceil(S / 32)^2.  w_ssim == 0: no stencil, a plain streaming pass (quads summed pairwise in fp32, fp64 from there on) into
+// Forward.  w_ssim > 0: ssim_tile.h's forward tile body with problems picked by blockIdx.y, three fp64 block sums per item to the
+// workspace: [3][n P] doubles per problem, P = 3 ceil(S / 32)^2.  w_ssim == 0: no stencil, a plain streaming pass (quads summed pairwise in fp32, fp64 from there on) into
 // [2][blocks] partials.  One final block per problem sums the partials in a fixed order (thread t: t, t + 256, ...; wave; four waves),
 // forms w_mse sse / N + w_l1 sae / N + w_ssim (1 - ss / windows) in double and rounds once into loss[g], a slot of the trainer's loss
 // vector.  A term whose weight is 0 is left out of the sum (0 x inf would poison it).
@@ -37,138 +33,30 @@
 // (DgPtrs).  A tile belongs to one image: a NaN / inf stays in that image's rows of dx.
 // fp32 inside the stencils; the per-pixel combination gout (...) is formed in double and rounded once, so the MSE and L1 parts alone are
 // one rounding away from gout 2 (x - t) / N and gout sign(x - t) / N.
-#include "dg_common.h"
-#include <math.h>
+#include "ssim_tile.h"
 
 #define RC_MAX_BLOCKS 8192
 #define RC_STREAM_BLOCKS 1024
 #define RT 32                 // tile side
-#define RK 11                 // window taps
-#define RH (RT + RK - 1)      // forward halo side: 42
-#define RP 44                 // forward halo pitch (whole quads)
-#define RQ (RP / 4)
-#define BC (RT + RK - 1)      // backward: window corners per axis around a tile: 42
+#define RK SSIM_K             // window taps
+#define BC SSIM_C             // backward: window corners per axis around a tile: 42
 #define BH (BC + RK - 1)      // backward halo rows: 52
 #define BY0 (RK - 1)          // the halo starts 10 rows above the tile
 #define BX0 12                // and 12 columns left of it (a whole number of quads)
 #define BP 56                 // backward halo pitch: 12 + 32 + 10 = 54 columns, rounded up to quads
-#define BQ (BP / 4)
 #define BT 512                // backward block size
+static_assert(RT == SSIM_T, "one tile side");
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-struct RcTaps {
-    float g[RK];
-};
 struct RcW {
     float mse, l1, ssim;
 };
 
-__global__ __launch_bounds__(256) void recon_fwd_tile_kernel(const DgPtrs xs, const DgPtrs ts, long items, int S, int T, int vec, const RcTaps taps,
+__global__ __launch_bounds__(256) void recon_fwd_tile_kernel(const DgPtrs xs, const DgPtrs ts, long items, int S, int T, int vec, const SsimTaps taps,
                                                              const DgPtrs parts) {
-    __shared__ __attribute__((aligned(16))) float sx[RH * RP];
-    __shared__ __attribute__((aligned(16))) float sy[RH * RP];
-    __shared__ float hp[5][RH * RT];
-    __shared__ double red[3][4];
-    const float* __restrict__ x = dg_pick<const float>(xs, blockIdx.y);
-    const float* __restrict__ y = dg_pick<const float>(ts, blockIdx.y);
-    double* __restrict__ part = dg_pick<double>(parts, blockIdx.y);
-    const int t = threadIdx.x;
-    const long plane = (long)S * S;
-    const int P = 3 * T * T;
-    const int nvalid = S - (RK - 1);
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    for (long item = blockIdx.x; item < items; item += gridDim.x) {
-        const long img = item / P;
-        const int p = (int)(item - img * P);
-        const int ch = p / (T * T), tt = p - ch * T * T;
-        const int gy0 = (tt / T) * RT, gx0 = (tt % T) * RT;
-        const float* bx = x + (img * 3 + ch) * plane;
-        const float* by = y + (img * 3 + ch) * plane;
-        __syncthreads();                           // the previous item's LDS reads are done
-        for (int i = t; i < RH * RQ; i += 256) {
-            const int r = i / RQ, q = i - r * RQ;
-            const int gy = gy0 + r, gx = gx0 + 4 * q;
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-            if (gy < S) {
-                const long o = (long)gy * S + gx;
-                if (vec) {
-                    if (gx + 3 < S) {              // S % 4 == 0: a quad is inside or outside as a whole
-                        a = *(const f32x4*)(bx + o);
-                        b = *(const f32x4*)(by + o);
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (gx + j < S) {
-                            a[j] = bx[o + j];
-                            b[j] = by[o + j];
-                        }
-                }
-            }
-            *(f32x4*)(sx + r * RP + 4 * q) = a;
-            *(f32x4*)(sy + r * RP + 4 * q) = b;
-        }
-        __syncthreads();
-        float e2[4], e1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = t + 256 * j, r = i >> 5, c = i & 31;
-            const bool in = gy0 + r < S && gx0 + c < S;
-            const float d = sx[r * RP + c] - sy[r * RP + c];
-            e2[j] = in ? d * d : 0.f;
-            e1[j] = in ? fabsf(d) : 0.f;
-        }
-        const float sse = (e2[0] + e2[1]) + (e2[2] + e2[3]);
-        const float sae = (e1[0] + e1[1]) + (e1[2] + e1[3]);
-        const int cr = min(RH / 2, S - 1 - gy0), cc = min(RH / 2, S - 1 - gx0);
-        const float cx = sx[cr * RP + cc], cy = sy[cr * RP + cc];
-        for (int i = t; i < RH * RT; i += 256) {
-            const int r = i >> 5, c = i & 31;
-            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-            for (int k = 0; k < RK; ++k) {
-                const float w = taps.g[k];
-                const float a = sx[r * RP + c + k] - cx, b = sy[r * RP + c + k] - cy;
-                m0 += w * a;
-                m1 += w * b;
-                m2 += w * (a * a);
-                m3 += w * (b * b);
-                m4 += w * (a * b);
-            }
-            hp[0][i] = m0; hp[1][i] = m1; hp[2][i] = m2; hp[3][i] = m3; hp[4][i] = m4;
-        }
-        __syncthreads();
-        float ss = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = t + 256 * j, r = i >> 5, c = i & 31;
-            if (gy0 + r < nvalid && gx0 + c < nvalid) {
-                float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-                for (int k = 0; k < RK; ++k) {
-                    const float w = taps.g[k];
-                    const int o = (r + k) * RT + c;
-                    m0 += w * hp[0][o];
-                    m1 += w * hp[1][o];
-                    m2 += w * hp[2][o];
-                    m3 += w * hp[3][o];
-                    m4 += w * hp[4][o];
-                }
-                const float mx = cx + m0, my = cy + m1;
-                const float vx = m2 - m0 * m0, vy = m3 - m1 * m1, cxy = m4 - m0 * m1;
-                ss += ((2.f * mx * my + C1) * (2.f * cxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2));
-            }
-        }
-        const double d0 = dg_wave_sum_d((double)sse), d1 = dg_wave_sum_d((double)sae), d2 = dg_wave_sum_d((double)ss);
-        if ((t & 63) == 0) {
-            red[0][t >> 6] = d0;
-            red[1][t >> 6] = d1;
-            red[2][t >> 6] = d2;
-        }
-        __syncthreads();
-        if (t < 3) part[t * items + item] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-    }
+    ssim_fwd_tiles(dg_pick<const float>(xs, blockIdx.y), dg_pick<const float>(ts, blockIdx.y), items, S, T, vec, taps,
+                   dg_pick<double>(parts, blockIdx.y), [items](int t, long img, int p, long item) { return t * items + item; });
 }
 
 // w_ssim == 0: sums of (x - t)^2 and |x - t| over all `count` values; part: [2][gridDim.x]
@@ -178,7 +66,7 @@ __global__ __launch_bounds__(256) void recon_fwd_stream_kernel(const DgPtrs xs, 
     const float* __restrict__ y = dg_pick<const float>(ts, blockIdx.y);
     double* __restrict__ part = dg_pick<double>(parts, blockIdx.y);
     const int t = threadIdx.x;
-    double s2 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};                      // sums of (x - t)^2 and of |x - t|
     const long n4 = count >> 2;
     for (long i = (long)blockIdx.x * 256 + t; i < n4; i += (long)gridDim.x * 256) {
         f32x4 a, b;
@@ -193,23 +81,17 @@ __global__ __launch_bounds__(256) void recon_fwd_stream_kernel(const DgPtrs xs, 
             }
         }
         const f32x4 d = a - b;
-        s2 += (double)((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-        s1 += (double)((fabsf(d[0]) + fabsf(d[1])) + (fabsf(d[2]) + fabsf(d[3])));
+        s[0] += (double)((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
+        s[1] += (double)((fabsf(d[0]) + fabsf(d[1])) + (fabsf(d[2]) + fabsf(d[3])));
     }
     if (blockIdx.x == 0 && t == 0)
         for (long e = n4 * 4; e < count; ++e) {
             const float d = x[e] - y[e];
-            s2 += (double)(d * d);
-            s1 += (double)fabsf(d);
+            s[0] += (double)(d * d);
+            s[1] += (double)fabsf(d);
         }
-    s2 = dg_wave_sum_d(s2);
-    s1 = dg_wave_sum_d(s1);
-    if ((t & 63) == 0) {
-        red[0][t >> 6] = s2;
-        red[1][t >> 6] = s1;
-    }
-    __syncthreads();
-    if (t < 2) part[(long)t * gridDim.x + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    dg_block_stage_d(s, red);
+    if (t < 2) part[(long)t * gridDim.x + blockIdx.x] = dg_sum4_pair(red[t]);
 }
 
 // part: [nsum][nparts] doubles per problem (nsum = 3 with the SSIM plane, else 2); one block per problem
@@ -219,26 +101,18 @@ __global__ __launch_bounds__(256) void recon_final_kernel(const DgPtrs parts, lo
     const double* __restrict__ p = dg_pick<const double>(parts, blockIdx.x);
     float* __restrict__ out = dg_pick<float>(outs, blockIdx.x);
     const int t = threadIdx.x;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
     for (long i = t; i < nparts; i += 256) {
-        s0 += p[i];
-        s1 += p[nparts + i];
-        if (nsum == 3) s2 += p[2 * nparts + i];
+        s[0] += p[i];
+        s[1] += p[nparts + i];
+        if (nsum == 3) s[2] += p[2 * nparts + i];
     }
-    s0 = dg_wave_sum_d(s0);
-    s1 = dg_wave_sum_d(s1);
-    s2 = dg_wave_sum_d(s2);
-    if ((t & 63) == 0) {
-        red[0][t >> 6] = s0;
-        red[1][t >> 6] = s1;
-        red[2][t >> 6] = s2;
-    }
-    __syncthreads();
+    dg_block_stage_d(s, red);
     if (t == 0) {
         double v = 0.0;
-        if (w.mse > 0.f) v += (double)w.mse * (((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * inv_px);
-        if (w.l1 > 0.f) v += (double)w.l1 * (((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * inv_px);
-        if (w.ssim > 0.f) v += (double)w.ssim * (1.0 - ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * inv_win);
+        if (w.mse > 0.f) v += (double)w.mse * (dg_sum4_pair(red[0]) * inv_px);
+        if (w.l1 > 0.f) v += (double)w.l1 * (dg_sum4_pair(red[1]) * inv_px);
+        if (w.ssim > 0.f) v += (double)w.ssim * (1.0 - dg_sum4_pair(red[2]) * inv_win);
         out[0] = (float)v;
     }
 }
@@ -288,7 +162,7 @@ __global__ __launch_bounds__(256) void recon_bwd_stream_kernel(const DgPtrs xs, 
 }
 
 __global__ __launch_bounds__(BT) void recon_bwd_tile_kernel(const DgPtrs xs, const DgPtrs ts, const DgPtrs gouts, const DgPtrs dxs, long items, int S,
-                                                            int T, int vec, const RcTaps taps, const RcW w, double inv_px, double inv_win) {
+                                                            int T, int vec, const SsimTaps taps, const RcW w, double inv_px, double inv_win) {
     __shared__ __attribute__((aligned(16))) float sx[BH * BP];
     __shared__ __attribute__((aligned(16))) float sy[BH * BP];
     __shared__ __attribute__((aligned(16))) float hp[5][BH * BC];      // horizontal moment planes: 52 rows x 42 corner columns
@@ -302,7 +176,6 @@ __global__ __launch_bounds__(BT) void recon_bwd_tile_kernel(const DgPtrs xs, con
     const long plane = (long)S * S;
     const int P = 3 * T * T;
     const int nvalid = S - (RK - 1);
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     const double go = (double)gout[0];
     const double kmse = go * (double)w.mse * 2.0 * inv_px, kl1 = go * (double)w.l1 * inv_px, kss = go * (double)w.ssim * inv_win;
     for (long item = blockIdx.x; item < items; item += gridDim.x) {
@@ -311,54 +184,15 @@ __global__ __launch_bounds__(BT) void recon_bwd_tile_kernel(const DgPtrs xs, con
         const int ch = p / (T * T), tt = p - ch * T * T;
         const int gy0 = (tt / T) * RT, gx0 = (tt % T) * RT;
         const long base = (img * 3 + ch) * plane;
-        const float* bx = x + base;
-        const float* by = y + base;
         __syncthreads();                           // the previous item's LDS reads are done
-        // 1. halo: rows [gy0 - 10, gy0 + 42), columns [gx0 - 12, gx0 + 44); outside the image 0 (feeds invalid corners only)
-        for (int i = t; i < BH * BQ; i += BT) {
-            const int r = i / BQ, q = i - r * BQ;
-            const int gy = gy0 - BY0 + r, gx = gx0 - BX0 + 4 * q;
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-            if (gy >= 0 && gy < S) {
-                const long o = (long)gy * S + gx;
-                if (vec) {
-                    if (gx >= 0 && gx + 3 < S) {   // S % 4 == 0 and gx % 4 == 0: a quad is inside or outside as a whole
-                        a = *(const f32x4*)(bx + o);
-                        b = *(const f32x4*)(by + o);
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (gx + j >= 0 && gx + j < S) {
-                            a[j] = bx[o + j];
-                            b[j] = by[o + j];
-                        }
-                }
-            }
-            *(f32x4*)(sx + r * BP + 4 * q) = a;
-            *(f32x4*)(sy + r * BP + 4 * q) = b;
-        }
+        // 1. halo: rows [gy0 - 10, gy0 + 42), columns [gx0 - 12, gx0 + 44)
+        ssim_stage_halo<BT, BH, BP, BY0, BX0>(x + base, y + base, S, gy0, gx0, vec, sx, sy);
         __syncthreads();
         // the tile's constants: the pixel at the tile's centre, clamped into the image
         const int cr = min(gy0 + RT / 2, S - 1) - gy0 + BY0, cc = min(gx0 + RT / 2, S - 1) - gx0 + BX0;
         const float cx = sx[cr * BP + cc], cy = sy[cr * BP + cc];
         // 2. horizontal pass: corner column cj (global gx0 - 10 + cj) starts at halo column cj + 2
-        for (int i = t; i < BH * BC; i += BT) {
-            const int r = i / BC, c = i - r * BC;
-            const int o = r * BP + c + (BX0 - BY0);
-            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-            for (int k = 0; k < RK; ++k) {
-                const float g = taps.g[k];
-                const float a = sx[o + k] - cx, b = sy[o + k] - cy;
-                m0 += g * a;
-                m1 += g * b;
-                m2 += g * (a * a);
-                m3 += g * (b * b);
-                m4 += g * (a * b);
-            }
-            hp[0][i] = m0; hp[1][i] = m1; hp[2][i] = m2; hp[3][i] = m3; hp[4][i] = m4;
-        }
+        ssim_hpass<BT, BH, BC, BP, BX0 - BY0>(sx, sy, cx, cy, taps, hp);
         __syncthreads();
         // 3. vertical pass and the coefficient maps; a corner outside the valid range contributes nothing
         for (int i = t; i < BC * BC; i += BT) {
@@ -366,26 +200,14 @@ __global__ __launch_bounds__(BT) void recon_bwd_tile_kernel(const DgPtrs xs, con
             const int gr = gy0 - BY0 + ci, gc = gx0 - BY0 + cj;
             float ca = 0.f, cb = 0.f, cq = 0.f;
             if (gr >= 0 && gr < nvalid && gc >= 0 && gc < nvalid) {
-                float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-                for (int k = 0; k < RK; ++k) {
-                    const float g = taps.g[k];
-                    const int o = (ci + k) * BC + cj;
-                    m0 += g * hp[0][o];
-                    m1 += g * hp[1][o];
-                    m2 += g * hp[2][o];
-                    m3 += g * hp[3][o];
-                    m4 += g * hp[4][o];
-                }
-                const float mx = cx + m0, my = cy + m1;
-                const float vx = m2 - m0 * m0, vy = m3 - m1 * m1, cxy = m4 - m0 * m1;
-                const float A1 = 2.f * mx * my + C1, A2 = 2.f * cxy + C2, B1 = mx * mx + my * my + C1, B2 = vx + vy + C2;
-                const float r12 = 1.f / (B1 * B2);
-                const float sv = A1 * A2 * r12;                       // the window's SSIM
-                const float dmu = 2.f * my * A2 * r12 - 2.f * mx * sv / B1;
-                const float dsig = -sv / B2;
-                const float dc = 2.f * A1 * r12;
-                ca = dmu - 2.f * m0 * dsig - m1 * dc;
+                const SsimMoments m = ssim_vpass<BH, BC>(hp, ci, cj, taps);
+                const SsimTerms s = ssim_terms(m, cx, cy);
+                const float r12 = 1.f / (s.B1 * s.B2);
+                const float sv = s.A1 * s.A2 * r12;                   // the window's SSIM
+                const float dmu = 2.f * s.my * s.A2 * r12 - 2.f * s.mx * sv / s.B1;
+                const float dsig = -sv / s.B2;
+                const float dc = 2.f * s.A1 * r12;
+                ca = dmu - 2.f * m.m0 * dsig - m.m1 * dc;
                 cb = 2.f * dsig;
                 cq = dc;
             }
@@ -441,26 +263,9 @@ __global__ __launch_bounds__(BT) void recon_bwd_tile_kernel(const DgPtrs xs, con
     }
 }
 
-static long recon_tiles(int S) {
-    const long T = ((long)S + RT - 1) / RT;
-    return 3 * T * T;
-}
-
-static RcTaps recon_taps(void) {
-    RcTaps taps;
-    double g[RK], sum = 0.0;
-    for (int k = 0; k < RK; ++k) {
-        const double d = k - RK / 2;
-        g[k] = exp(-(d * d) / (2.0 * 1.5 * 1.5));
-        sum += g[k];
-    }
-    for (int k = 0; k < RK; ++k) taps.g[k] = (float)(g[k] / sum);
-    return taps;
-}
-
 extern "C" size_t dg_recon_loss_workspace_bytes(int n, int S) {
     if (n < 1 || S < 1) return 0;
-    const size_t tile = (size_t)3 * (size_t)n * (size_t)recon_tiles(S), stream = (size_t)2 * RC_STREAM_BLOCKS;
+    const size_t tile = (size_t)3 * (size_t)n * (size_t)ssim_tiles(S), stream = (size_t)2 * RC_STREAM_BLOCKS;
     return (tile > stream ? tile : stream) * sizeof(double);
 }
 
@@ -472,7 +277,7 @@ static int recon_check(const char* who, int groups, int n, int S, const float* w
     DG_CHECK_ARG(w[0] > 0.f || w[1] > 0.f || w[2] > 0.f, "%s: all three weights are 0", who);
     DG_CHECK_ARG(n >= 1 && S >= 1, "%s: n=%d, S=%d", who, n, S);
     DG_CHECK_ARG(w[2] == 0.f || S >= RK, "%s: S %d < %d with the SSIM term on (the window does not fit)", who, S, RK);
-    DG_CHECK_ARG(recon_tiles(S) <= 0x7fffffffL / 3, "%s: S %d is too large", who, S);
+    DG_CHECK_ARG(ssim_tiles(S) <= 0x7fffffffL / 3, "%s: S %d is too large", who, S);
     for (int k = 0; k < ntabs; ++k) {
         DG_CHECK_ARG(tabs[k] != nullptr, "%s: null pointer table", who);
         for (int i = 0; i < groups; ++i) {
@@ -503,11 +308,11 @@ extern "C" int dg_recon_loss_fwd_g(int groups, const float* const* x, const floa
     const DgPtrs px = dg_ptrs(tabs[0], groups), pt = dg_ptrs(tabs[1], groups), pw = dg_ptrs(tabs[3], groups), pl = dg_ptrs(tabs[2], groups);
     hipStream_t st = (hipStream_t)stream;
     if (rw.ssim > 0.f) {
-        const int P = (int)recon_tiles(S), T = (S + RT - 1) / RT;
+        const int P = (int)ssim_tiles(S), T = (S + RT - 1) / RT;
         const long items = (long)n * P;
         const int win = S - (RK - 1);
         hipLaunchKernelGGL(recon_fwd_tile_kernel, dim3((unsigned)(items < RC_MAX_BLOCKS ? items : RC_MAX_BLOCKS), groups), dim3(256), 0, st, px, pt, items,
-                           S, T, vec, recon_taps(), pw);
+                           S, T, vec, ssim_taps(), pw);
         DG_CHECK_LAUNCH("recon_fwd_tile");
         hipLaunchKernelGGL(recon_final_kernel, dim3(groups), dim3(256), 0, st, pw, items, 3, 1.0 / (double)count,
                            1.0 / ((double)n * 3.0 * (double)win * (double)win), rw, pl);
@@ -539,11 +344,11 @@ extern "C" int dg_recon_loss_bwd_g(int groups, const float* const* x, const floa
     const DgPtrs px = dg_ptrs(tabs[0], groups), pt = dg_ptrs(tabs[1], groups), pg = dg_ptrs(tabs[2], groups), pd = dg_ptrs(tabs[3], groups);
     hipStream_t st = (hipStream_t)stream;
     if (rw.ssim > 0.f) {
-        const int P = (int)recon_tiles(S), T = (S + RT - 1) / RT;
+        const int P = (int)ssim_tiles(S), T = (S + RT - 1) / RT;
         const long items = (long)n * P;
         const int win = S - (RK - 1);
         hipLaunchKernelGGL(recon_bwd_tile_kernel, dim3((unsigned)(items < RC_MAX_BLOCKS ? items : RC_MAX_BLOCKS), groups), dim3(BT), 0, st, px, pt, pg, pd,
-                           items, S, T, vec, recon_taps(), rw, 1.0 / (double)count, 1.0 / ((double)n * 3.0 * (double)win * (double)win));
+                           items, S, T, vec, ssim_taps(), rw, 1.0 / (double)count, 1.0 / ((double)n * 3.0 * (double)win * (double)win));
         DG_CHECK_LAUNCH("recon_bwd_tile");
     } else {
         long g = (count / 4 + 255) / 256;

@@ -9,7 +9,7 @@
 //                        multiple of 4 and the bases are 16-byte aligned, else one output; both forms evaluate the same chain of explicit
 //                        fmaf per element (nothing is left to the compiler's contraction, which differed between the two forms), so the
 //                        bits do not depend on alignment.  Filter taps are read as scalars (they hit L2).
-//   dg_swd_draw          one thread per record.
+//   dg_swd_draw          one thread per record, one word of dg_draw.h's generator each.
 //   dg_swd_descriptors   block b owns descriptors [32 b, 32 b + 32): NB = ceil(M / 32) blocks, a function of M alone.  Pass 1 gathers
 //                        (a bit copy) and leaves three fp64 sums per block; pass 2 re-reads the block's descriptors and leaves the sums
 //                        of (v - mean)^2 (two passes: no cancellation, a flat channel gives a variance of exactly 0); a one-block kernel
@@ -36,7 +36,7 @@
 //                     |err| <= gamma((l + 1) SWD_K_DOWN + SWD_K_UP + 1) (mag(G_l) + up(mag(G_{l+1}))), mag = the same chain on |x|
 //   projection:       147 fma + the rounding of xhat + the fp64 statistics: gamma(147 + 3) sum_k |xhat_k| |dir_k|
 //   distance:         ceil(M / 1024) terms per thread, one rounding for the difference, fp64 after that: gamma(ceil(M / 1024) + 2)
-#include "dg_common.h"
+#include "dg_draw.h"
 
 #define SWD_PATCH 7
 #define SWD_DESC 147               // 3 x 7 x 7, [channel][dy][dx]
@@ -44,17 +44,7 @@
 #define SWD_PYR_MAX_BLOCKS 16384
 #define SWD_DESC_PER_BLOCK 32
 #define SWD_SORT_THREADS 1024
-#define SWD_G 0x9E3779B97F4A7C15ull
-#define SWD_LINK 0x7377640000000000ull
-
-__host__ __device__ __forceinline__ uint64_t swd_mix(uint64_t z) {        // the SplitMix64 output function, as diffaug.hip's da_mix
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
+#define SWD_LINK 0x7377640000000000ull             // "swd" in the high word; the level sits in the low one
 
 static int swd_levels(int S) {
     if (S < 16) return 0;
@@ -217,9 +207,9 @@ extern "C" int dg_lap_pyramid(const float* x, int n, int S, float* out, dg_strea
 __global__ __launch_bounds__(256) void swd_draw_kernel(uint64_t key, long count, int span, int* __restrict__ recs) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < count) {
-        const uint64_t q = swd_mix(key + SWD_G * ((uint64_t)i + 1ull));
-        recs[2 * i] = (int)(((q >> 32) * (uint64_t)span) >> 32);
-        recs[2 * i + 1] = (int)(((q & 0xFFFFFFFFull) * (uint64_t)span) >> 32);
+        const uint64_t q = dg_mix(key + DG_DRAW_G * ((uint64_t)i + 1ull));
+        recs[2 * i] = dg_draw_range((uint32_t)(q >> 32), 0, (uint32_t)span);
+        recs[2 * i + 1] = dg_draw_range((uint32_t)q, 0, (uint32_t)span);
     }
 }
 
@@ -229,8 +219,7 @@ extern "C" int dg_swd_draw(uint64_t seed, int level, int n, int R, int P, int32_
     DG_CHECK_ARG(level >= 0 && level < 64, "dg_swd_draw: 0 <= level < 64, got %d", level);
     DG_CHECK_ARG(n >= 1 && P >= 1 && (long)n * P <= DG_SWD_MAX_ROW, "dg_swd_draw: n, P >= 1 and n P <= %d, got n=%d P=%d", DG_SWD_MAX_ROW, n, P);
     DG_CHECK_ARG(R >= SWD_PATCH && R <= 16384, "dg_swd_draw: %d <= R <= 16384, got %d", SWD_PATCH, R);
-    uint64_t k = swd_mix(seed + SWD_G);
-    k = swd_mix(k ^ (SWD_LINK | (uint64_t)(uint32_t)level));
+    const uint64_t k = dg_mix(dg_mix(seed + DG_DRAW_G) ^ (SWD_LINK | (uint64_t)(uint32_t)level));
     const long count = (long)n * P;
     hipLaunchKernelGGL(swd_draw_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)s, k, count, R - (SWD_PATCH - 1), recs);
     DG_CHECK_LAUNCH("swd_draw");
@@ -247,17 +236,9 @@ extern "C" size_t dg_swd_descriptors_workspace_bytes(int M) {
 
 // three block sums (one per channel) in fixed order; the results are valid in every thread.  red: 3 x 4 doubles of LDS
 __device__ __forceinline__ void swd_block_sum3(double (&a)[3], double (*red)[4]) {
-    const int t = threadIdx.x;
+    dg_block_stage_d(a, red);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = dg_wave_sum_d(a[c]);
-    __syncthreads();                               // the previous use of red is read
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) red[c][t >> 6] = a[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
+    for (int c = 0; c < 3; ++c) a[c] = dg_sum4_pair(red[c]);
 }
 
 // the sum of the nb block partials part[c][0..nb) of every channel, the same bits in every block

@@ -141,6 +141,22 @@ def test_bound_rejects_wrong_problems(n, S):
                 assert err > c["gbound"], (kind, wrong, err, c["gbound"])
 
 
+@pytest.mark.parametrize("S", (11, 43, 64))
+def test_the_ssim_term_is_the_ssim_of_image_metrics(S):
+    """recon.hip's promise "SSIM exactly the quantity of dg_image_metrics": one image (S = 11: one window; 43: ragged tiles, scalar
+    loads; 64: 16-byte loads), weights (0, 0, 1).  Both tile kernels run one stencil (csrc/ssim_tile.h) and, with one image, both final
+    kernels add the same partials in the same order and form the same double D = ss / windows.  dg_image_metrics returns fl32(D): off
+    by at most 2^-24 |D|, |D| <= 1.  dg_recon_loss_fwd returns fl32(1 - D): off by at most 2^-24 |1 - D|, |1 - D| <= 2.  Together
+    3 x 2^-24 -- derived, not measured; a miss means the two kernels no longer share a stencil."""
+    g = torch.Generator().manual_seed(1000 + S)
+    x, t = (torch.rand((1, 3, S, S), generator=g, dtype=torch.float32).to(DEV) for _ in range(2))
+    loss = float(ops.recon_loss_fwd(x, t, (0.0, 0.0, 1.0)))
+    ssim = float(ops.image_metrics(x, t)[0, 2].double())
+    err = abs(loss - (1.0 - ssim))
+    print(f"S {S}: recon loss {loss!r} 1 - SSIM {1.0 - ssim!r} distance {err:.3e} bound {3 * 2.0 ** -24:.3e}")
+    assert err <= 3 * 2.0 ** -24, (S, loss, ssim, err)
+
+
 # ---- 2. bitwise equalities ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,S", SHAPES)
 def test_repeat_grouped_and_alignment_are_bitwise(n, S):
