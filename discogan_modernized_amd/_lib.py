@@ -154,6 +154,15 @@ SIGNATURES = {
     "dg_recon_loss_bwd": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "dg_recon_loss_fwd_g": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
     "dg_recon_loss_bwd_g": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "dg_ms_ssim_max_scales": (_i, [_i]),
+    "dg_ms_ssim_workspace_bytes": (_z, [_i, _i, _i]),
+    "dg_ms_ssim_bwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "dg_ms_ssim_save_bytes": (_z, [_i, _i, _i]),
+    "dg_ms_ssim_loss_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _z, _p]),
+    "dg_ms_ssim_loss_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _p, _z, _p]),
+    "dg_ms_ssim_loss_fwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _z, _p]),
+    "dg_ms_ssim_loss_bwd_g": (_i, [_i, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _p, _z, _p]),
+    "dg_image_ms_ssim": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p]),
     "dg_swd_max_row": (_i, []),
     "dg_swd_levels": (_i, [_i]),
     "dg_lap_pyramid_elems": (_z, [_i, _i]),

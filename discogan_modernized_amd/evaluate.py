@@ -10,6 +10,8 @@ What is scored:
   trans_AB, trans_BA    paired splits only (``edges2shoes`` / ``edges2handbags``: image i of A and image i of B are the two halves of
                         one file): the translation ``A->B`` against ``B`` and ``B->A`` against ``A``, over the first min(n_A, n_B) images
 
+  ms_ssim               with ``--eval_ms_ssim`` / ``--ms_ssim``: every entry above also holds the multi-scale SSIM (``ops.image_ms_ssim``:
+                        Wang, Simoncelli, Bovik 2003, over as many scales as the size carries, at most 5)
   swd_AB, swd_BA        with ``--eval_swd`` / ``--swd``, paired or not: the sliced Wasserstein distance (``SWD`` below) between the
                         translations ``A->B`` and ``test_B``, and between ``B->A`` and ``test_A`` -- the only score an unpaired split has
                         for the translations themselves
@@ -47,11 +49,15 @@ def paired_default(args, data_kind):
 
 
 def summarise(rows):
-    """float [n,3] host rows of (mse, mae, ssim) -> dict of n and the float64 means; psnr = mean of the per-image 10 log10(1 / mse)."""
+    """float [n,3] host rows of (mse, mae, ssim) -> dict of n and the float64 means; psnr = mean of the per-image 10 log10(1 / mse).
+    A fourth column is the multi-scale SSIM (``--ms_ssim``) and adds the key ``ms_ssim``."""
     r = rows.double()
     mse = r[:, 0]
     psnr = torch.where(mse == 0, torch.full_like(mse, math.inf), 10.0 * torch.log10(1.0 / mse))
-    return dict(n=int(r.shape[0]), mse=float(mse.mean()), mae=float(r[:, 1].mean()), ssim=float(r[:, 2].mean()), psnr=float(psnr.mean()))
+    res = dict(n=int(r.shape[0]), mse=float(mse.mean()), mae=float(r[:, 1].mean()), ssim=float(r[:, 2].mean()), psnr=float(psnr.mean()))
+    if r.shape[1] > 3:
+        res["ms_ssim"] = float(r[:, 3].mean())
+    return res
 
 
 class SWD:
@@ -140,16 +146,19 @@ def format_swd(r):
     return "/".join(f"{v:.3f}" for v in r["levels"]) + f"={r['mean']:.3f}"
 
 
-def evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, paired, swd=None):
+def evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, paired, swd=None, ms_ssim=False):
     """The metric launches of one evaluation event on the six device batches of a sampling event -> dict of ``summarise`` dicts.
     ``swd``: two ``SWD`` objects with their references set, ``(against test_B, against test_A)``: the result also holds ``swd_AB`` and
-    ``swd_BA`` (dicts of ``SWD.score``), for paired and unpaired splits alike."""
+    ``swd_BA`` (dicts of ``SWD.score``), for paired and unpaired splits alike.  ``ms_ssim``: every entry that has ``ssim`` also gets
+    ``ms_ssim``, the mean of ``ops.image_ms_ssim`` over as many scales as the size carries."""
     from . import ops
     pairs = [("recon_A", test_A, ABA), ("recon_B", test_B, BAB)]
     if paired:
         n = min(len(test_A), len(test_B))
         pairs += [("trans_AB", test_B[:n], AB[:n]), ("trans_BA", test_A[:n], BA[:n])]
     rows = [ops.image_metrics(ref, got) for _, ref, got in pairs]
+    if ms_ssim:
+        rows = [torch.cat([r, ops.image_ms_ssim(ref, got)[:, None]], dim=1) for r, (_, ref, got) in zip(rows, pairs)]
     host = torch.cat(rows).cpu()                                      # one D2H copy
     res, at = {}, 0
     for (name, _, _), r in zip(pairs, rows):
@@ -171,16 +180,20 @@ def format_eval(iters, res):
               f"TRANS_MAE: {pair('mae', 'trans_AB', 'trans_BA', '.5f')}")
     if "swd_AB" in res:
         s += f", SWD_AB: {format_swd(res['swd_AB'])}, SWD_BA: {format_swd(res['swd_BA'])}"
+    if "ms_ssim" in res["recon_A"]:
+        s += f", RECON_MSSSIM: {pair('ms_ssim', 'recon_A', 'recon_B', '.4f')}"
+        if "trans_AB" in res:
+            s += f", TRANS_MSSSIM: {pair('ms_ssim', 'trans_AB', 'trans_BA', '.4f')}"
     return s + f" (n={res['recon_A']['n']}/{res['recon_B']['n']})"
 
 
-def evaluate_split(trainer, split, paired, outs=None, swd=None):
+def evaluate_split(trainer, split, paired, outs=None, swd=None, ms_ssim=False):
     """One evaluation event of a training run: the four passes of ``trainer.sample`` (unless the sampling event of the same iteration
-    already ran them: ``outs``), then the metrics (``swd``: see ``evaluate_outputs``).  Returns ``(res, outs)``."""
+    already ran them: ``outs``), then the metrics (``swd``, ``ms_ssim``: see ``evaluate_outputs``).  Returns ``(res, outs)``."""
     test_A, test_B = split
     if outs is None:
         outs = trainer.sample(test_A, test_B)
-    return evaluate_outputs(test_A, test_B, *outs, paired, swd=swd), outs
+    return evaluate_outputs(test_A, test_B, *outs, paired, swd=swd, ms_ssim=ms_ssim), outs
 
 
 def check_size(image_size, swd=False):
@@ -206,6 +219,9 @@ def parse_args(argv=None):
                    help="also score the sliced Wasserstein distance of the translations against the other domain's test images "
                         "(swd_AB, swd_BA) and of the two test sets against each other (swd_domains); works on unpaired splits")
     p.add_argument("--swd_seed", type=int, default=0, help="key of the patch positions and directions of --swd")
+    p.add_argument("--ms_ssim", action="store_true",
+                   help="also score the multi-scale SSIM (Wang et al. 2003; up to five scales of a 2 x 2 average pyramid): an ms_ssim "
+                        "entry next to every ssim")
     p.add_argument("--output", type=str, default="eval.json")
     return p.parse_args(argv)
 
@@ -232,7 +248,7 @@ def main(argv=None):
         AB, BA = g_ab(test_A), g_ba(test_B)
         ABA, BAB = g_ba(AB), g_ab(BA)
     swd, domains = make_swd_pair(test_A, test_B, args.image_size, args.swd_seed) if args.swd else (None, None)
-    res = evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, args.paired, swd=swd)
+    res = evaluate_outputs(test_A, test_B, AB, BA, ABA, BAB, args.paired, swd=swd, ms_ssim=args.ms_ssim)
     if args.swd:
         res["swd_domains"] = domains
         print(f"SWD_DOMAINS: {format_swd(domains)} (n={domains['n']}, {domains['patches']} patches per image)", flush=True)

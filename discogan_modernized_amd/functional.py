@@ -400,6 +400,26 @@ class ReconLossFn(Function):
         return dx, None, None, None
 
 
+class MsSsimLossFn(Function):
+    """``w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ms (1 - mean MS-SSIM over M scales)`` of an image batch against data
+    (ops.ms_ssim_loss_fwd); ``w = (w_mse, w_l1, w_ms)``; the gradient is taken with respect to ``x`` only.  The forward's save buffer
+    (both pyramids and the k table) lives until the backward."""
+
+    @_fwd
+    def forward(ctx, x, t, M, w, out=None):
+        xd, td = x.contiguous(), t.contiguous()
+        loss, save = ops.ms_ssim_loss_fwd(xd, td, M, w, out)
+        ctx.save_for_backward(xd, td, save)
+        ctx.M, ctx.w = int(M), tuple(w)
+        return loss
+
+    @_bwd
+    def backward(ctx, gout):
+        xd, td, save = ctx.saved_tensors
+        dx = ops.ms_ssim_loss_bwd(xd, td, ctx.M, ctx.w, gout.contiguous(), save) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None
+
+
 class BCELossFn(Function):
     """nn.BCELoss against a constant label tensor (image_translation.py:157-166)."""
 
@@ -767,6 +787,28 @@ class ReconLossGroupFn(Function):
         sv = ctx.saved_tensors
         dxs = ops.recon_loss_bwd_g(list(sv[:g]), list(sv[g:]), ctx.w, [go.contiguous() for go in gouts])
         return (None, None) + tuple(dxs) + (None,) * (2 * g)
+
+
+class MsSsimLossGroupFn(Function):
+    """MsSsimLossFn of ``g`` (x, target) pairs under one (M, weight triple); the losses land in ``outs``.  args: x_0.., t_0.., out_0.."""
+
+    @_fwd
+    def forward(ctx, g, M, w, *t):
+        xs, ts, outs = [v.contiguous() for v in t[:g]], [v.contiguous() for v in t[g:2 * g]], list(t[2 * g:3 * g])
+        saves = ops.ms_ssim_loss_fwd_g(xs, ts, M, w, outs)
+        ctx.g, ctx.M, ctx.w = g, int(M), tuple(w)
+        ctx.save_for_backward(*xs, *ts, *saves)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @_bwd
+    def backward(ctx, *gouts):
+        g = ctx.g
+        if not _all_or_none(gouts, "MsSsimLossGroupFn"):
+            return (None,) * (3 + 3 * g)
+        sv = ctx.saved_tensors
+        dxs = ops.ms_ssim_loss_bwd_g(list(sv[:g]), list(sv[g:2 * g]), ctx.M, ctx.w, [go.contiguous() for go in gouts], list(sv[2 * g:]))
+        return (None, None, None) + tuple(dxs) + (None,) * (2 * g)
 
 
 class BCELossGroupFn(Function):

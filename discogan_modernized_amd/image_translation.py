@@ -61,7 +61,12 @@ ABA against A and BAB against B are measured with: ``l1`` = mean |x - t| (CycleG
 sigma 1.5, valid windows, that ``SSIM_ABA`` of the evaluation reports; needs ``--image_size >= 11``), ``l1_ssim`` = (1 - alpha) L1 +
 alpha (1 - SSIM) with ``--recon_ssim_alpha`` (default 0.84, Zhao et al. 2017).  One fused forward and one backward kernel per term
 (dg_recon_loss_fwd / dg_recon_loss_bwd) in the place of the MSE kernels: captured, replayed and resumed like them, nothing is saved, and
-the ``RECON:`` field of the log line prints the criterion's value.  With ``mse`` nothing changes.
+the ``RECON:`` field of the log line prints the criterion's value.  With ``mse`` nothing changes.  ``ms_ssim`` = 1 - MS-SSIM (Wang,
+Simoncelli, Bovik 2003: the contrast-structure term at every scale of a 2 x 2 average pyramid, the full SSIM at the coarsest, exponents
+normalised) and ``l1_ms_ssim`` = (1 - alpha) L1 + alpha (1 - MS-SSIM) -- the mix Zhao et al.'s 0.84 belongs to -- over
+``--recon_ms_scales`` scales (default 0: as many as ``--image_size`` carries with every side >= 11, at most 5); dg_ms_ssim_loss_fwd /
+_bwd, whose forward keeps both pyramids and a small table for its backward (freed with the graph of the iteration; nothing to checkpoint).
+``--eval_ms_ssim`` appends ``RECON_MSSSIM: a/b`` (paired: and ``TRANS_MSSSIM``) to the evaluation lines.
 Adversarial objective: ``--gan_loss {bce,bce_logits,lsgan,hinge}`` (default ``bce``, the reference's nn.BCELoss on the sigmoid output)
 chooses what the six GAN terms are measured with.  The other three read the discriminators' LOGITS (the sigmoid is not launched):
 ``bce_logits`` = the same cross entropy in its stable form (softplus; the gradient of a saturated logit stays accurate instead of coming
@@ -90,8 +95,9 @@ from pathlib import Path
 
 import torch
 
-from .losses import GAN_KINDS
+from .losses import GAN_KINDS, MS_SSIM_KINDS
 from .trainer import DiscoGANTrainer, check_ada, check_diffaug, check_gan_loss, check_image_pool, check_recon_loss
+from .trainer import recon_ms_scales as recon_ms_scales_of
 
 TASKS = ["facescrub", "celebA", "edges2shoes", "edges2handbags", "handbags2shoes", "tops2hanbok", "hanbok2tops"]
 
@@ -137,6 +143,9 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
                    help="with --eval_interval: also score the sliced Wasserstein distance on Laplacian-pyramid patches between the "
                         "translations and the other domain's held-out images (SWD_AB, SWD_BA; needs no pairing); keeps "
                         "512 * n * P * 4 bytes per pyramid level and domain on the device (evaluate.SWD)")
+    p.add_argument("--eval_ms_ssim", action="store_true",
+                   help="with --eval_interval: append the multi-scale SSIM of the reconstructions (and of the translations of a paired "
+                        "split) to every evaluation line: RECON_MSSSIM: a/b")
     p.add_argument("--eval_swd_seed", type=int, default=0, help="key of the patch positions and directions of --eval_swd")
     p.add_argument("--ema_decay", type=float, default=0.0,
                    help="keep an exponential moving average of both generators' weights with this decay (e.g. 0.999; 0 = off) and "
@@ -170,12 +179,16 @@ def build_parser(description="HIP/MI355X implementation of the DiscoGAN training
     p.add_argument("--ada_kimg", type=float, default=500.0,
                    help="with --ada_target: thousands of real images it takes p to travel from 0 to 1 (the step per image is 1 / (1000 kimg))")
     p.add_argument("--ada_p_max", type=float, default=1.0, help="with --ada_target: the upper bound of p, in (0, 1]")
-    p.add_argument("--recon_loss", type=str, default="mse", choices=["mse", "l1", "ssim", "l1_ssim"],
+    p.add_argument("--recon_loss", type=str, default="mse", choices=["mse", "l1", "ssim", "l1_ssim", "ms_ssim", "l1_ms_ssim"],
                    help="criterion of the two reconstruction (cycle) terms: mse (the reference's nn.MSELoss), l1 (CycleGAN's), ssim "
-                        "(1 - SSIM, the 11 x 11 Gaussian window of the evaluation) or l1_ssim ((1 - alpha) L1 + alpha (1 - SSIM)); the "
-                        "SSIM kinds need --image_size >= 11")
+                        "(1 - SSIM, the 11 x 11 Gaussian window of the evaluation), l1_ssim ((1 - alpha) L1 + alpha (1 - SSIM)), ms_ssim "
+                        "(1 - multi-scale SSIM) or l1_ms_ssim ((1 - alpha) L1 + alpha (1 - MS-SSIM)); the SSIM kinds need "
+                        "--image_size >= 11")
     p.add_argument("--recon_ssim_alpha", type=float, default=0.84,
-                   help="with --recon_loss l1_ssim: the weight alpha of the SSIM term, in (0, 1) (Zhao et al. 2017: 0.84)")
+                   help="with --recon_loss l1_ssim / l1_ms_ssim: the weight alpha of the SSIM term, in (0, 1) (Zhao et al. 2017: 0.84)")
+    p.add_argument("--recon_ms_scales", type=int, default=0,
+                   help="with --recon_loss ms_ssim / l1_ms_ssim: the number of scales, each half the side of the one before and at least "
+                        "11 pixels; 0 = as many as --image_size carries, at most 5 (64 px: 3, 176 px and more: 5)")
     p.add_argument("--gan_loss", type=str, default="bce", choices=list(GAN_KINDS),
                    help="adversarial objective: bce (the reference's nn.BCELoss on the sigmoid output) or, on the discriminators' logits, "
                         "bce_logits (the same in its stable form), lsgan ((x - target)^2, CycleGAN's) or hinge (max(0, 1 -+ x) | -x)")
@@ -401,7 +414,8 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                                getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0),             # --diffaug_p without --diffaug
                                getattr(args, "ada_p_max", 1.0), batch=args.batch_size, world=world_size)
     recon_loss = getattr(args, "recon_loss", "mse")                         # likewise: an SSIM criterion on images under 11 pixels
-    recon_w = check_recon_loss(recon_loss, getattr(args, "recon_ssim_alpha", 0.84), args.image_size)
+    recon_ms_scales = getattr(args, "recon_ms_scales", 0)
+    recon_w = check_recon_loss(recon_loss, getattr(args, "recon_ssim_alpha", 0.84), args.image_size, recon_ms_scales)
     gan_loss, gan_real_label = check_gan_loss(getattr(args, "gan_loss", "bce"), getattr(args, "gan_real_label", 1.0))   # likewise: hinge with smoothing
     eval_interval = int(getattr(args, "eval_interval", 0) or 0)
     eval_swd = check_eval_swd(args)                                       # likewise: --eval_swd without --eval_interval
@@ -443,7 +457,11 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                       f"{ada['interval']} discriminator steps towards r_t = {ada['target']:g} ({ada['kimg']:g} kimg from 0 to 1)", flush=True)
             elif diffaug_p is not None:
                 print(f"differentiable augmentation: each stage applied to a sample with probability {diffaug_p:g}", flush=True)
-        if recon_loss != "mse":
+        if recon_loss in MS_SSIM_KINDS:
+            print(f"reconstruction loss: {recon_loss} = {recon_w[0]:g} MSE + {recon_w[1]:g} L1 + {recon_w[2]:g} (1 - MS-SSIM over "
+                  f"{recon_ms_scales_of(recon_loss, args.image_size, recon_ms_scales)} scales) on both cycle terms (RECON: prints its value)",
+                  flush=True)
+        elif recon_loss != "mse":
             print(f"reconstruction loss: {recon_loss} = {recon_w[0]:g} MSE + {recon_w[1]:g} L1 + {recon_w[2]:g} (1 - SSIM) on both cycle "
                   "terms (RECON: prints its value)", flush=True)
         if gan_loss != "bce" or gan_real_label != 1.0:
@@ -514,7 +532,8 @@ def train(args, trainer=None, rank=0, world_size=1, is_main=True, process_group=
                 if sampling:
                     samples.save_samples(trainer, split, result_path / "samples", iters, outs=outs)
                 if evaluating:
-                    res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs, swd=swd)
+                    res, _ = evaluate.evaluate_split(trainer, split, eval_paired, outs=outs, swd=swd,
+                                                     ms_ssim=bool(getattr(args, "eval_ms_ssim", False)))
                     msg = evaluate.format_eval(iters, res) + (" [ema]" if on_ema else "")
                     print(msg, flush=True)
                     with open(result_path / "eval_log.txt", "a") as f:

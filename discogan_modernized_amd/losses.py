@@ -21,19 +21,47 @@ class MSELoss(nn.Module):
         return F.MSELossFn.apply(input, target)
 
 
-RECON_KINDS = ("mse", "l1", "ssim", "l1_ssim")
+RECON_KINDS = ("mse", "l1", "ssim", "l1_ssim", "ms_ssim", "l1_ms_ssim")
+MS_SSIM_KINDS = ("ms_ssim", "l1_ms_ssim")           # the third weight multiplies 1 - MS-SSIM (dg_ms_ssim_loss_fwd), not 1 - SSIM
+MS_SSIM_EXPONENTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def ms_ssim_max_scales(image_size):
+    """min(5, number of j with image_size >> j >= 11): every scale of the pyramid must hold the 11 x 11 window (dg_ms_ssim_max_scales;
+    0 under 11 pixels, 11 -> 1, 22 -> 2, 64 -> 3, 176 and more -> 5)."""
+    m = 0
+    while m < len(MS_SSIM_EXPONENTS) and (int(image_size) >> m) >= 11:
+        m += 1
+    return m
+
+
+def ms_ssim_scales(scales, image_size):
+    """The scale count of an MS-SSIM criterion at ``image_size``: ``scales`` itself, or the maximum for 0; ValueError when the size
+    cannot carry it."""
+    top = ms_ssim_max_scales(image_size)
+    if top < 1:
+        raise ValueError(f"multi-scale SSIM needs image_size >= 11 (the 11 x 11 SSIM window), got {image_size}")
+    M = int(scales)
+    if M == 0:
+        return top
+    if not 1 <= M <= top:
+        raise ValueError(f"recon_ms_scales {M} does not fit image_size {image_size}: every scale needs a side >= 11, so 1..{top} "
+                         "(0: the maximum)")
+    return M
 
 
 def recon_weights(kind, alpha=0.84):
     """The weights ``(w_mse, w_l1, w_ssim)`` of a reconstruction criterion (``dg_recon_loss_fwd``): ``mse`` -> (1, 0, 0), ``l1`` ->
-    (0, 1, 0), ``ssim`` -> (0, 0, 1) (the loss is 1 - SSIM), ``l1_ssim`` -> (0, 1 - alpha, alpha) (Zhao et al. 2017: alpha = 0.84)."""
+    (0, 1, 0), ``ssim`` -> (0, 0, 1) (the loss is 1 - SSIM), ``l1_ssim`` -> (0, 1 - alpha, alpha) (Zhao et al. 2017: alpha = 0.84).
+    ``ms_ssim`` and ``l1_ms_ssim`` (MS_SSIM_KINDS) have the tables of ``ssim`` and ``l1_ssim``; their third weight is w_ms of
+    ``dg_ms_ssim_loss_fwd``."""
     if kind == "mse":
         return (1.0, 0.0, 0.0)
     if kind == "l1":
         return (0.0, 1.0, 0.0)
-    if kind == "ssim":
+    if kind in ("ssim", "ms_ssim"):
         return (0.0, 0.0, 1.0)
-    if kind == "l1_ssim":
+    if kind in ("l1_ssim", "l1_ms_ssim"):
         alpha = float(alpha)
         if not 0.0 < alpha < 1.0:
             raise ValueError(f"recon_ssim_alpha must be in (0, 1), got {alpha}")
@@ -48,11 +76,31 @@ class ReconLoss(nn.Module):
 
     def __init__(self, kind="l1_ssim", alpha=0.84):
         super().__init__()
+        if kind in MS_SSIM_KINDS:
+            raise ValueError(f"ReconLoss is the single-scale criterion: {kind!r} is MSSSIMLoss")
         self.kind = kind
         self.weights = recon_weights(kind, alpha)
 
     def forward(self, input, target):
         return F.ReconLossFn.apply(input, target, self.weights)
+
+
+class MSSSIMLoss(nn.Module):
+    """``w_l1 mean |x - t| + w_ms (1 - mean MS-SSIM)`` of an image batch ``input`` [n,3,S,S] against the data ``target`` (no gradient
+    flows into it): kind ``ms_ssim`` (1 - MS-SSIM) or ``l1_ms_ssim`` ((1 - alpha) L1 + alpha (1 - MS-SSIM), Zhao et al. 2017: alpha =
+    0.84).  MS-SSIM (Wang, Simoncelli, Bovik 2003) over ``scales`` levels of a 2 x 2 average pyramid (0: as many as the input's size
+    carries, at most 5), the quantity ``ops.image_ms_ssim`` reports."""
+
+    def __init__(self, kind="l1_ms_ssim", alpha=0.84, scales=0):
+        super().__init__()
+        if kind not in MS_SSIM_KINDS:
+            raise ValueError(f"MSSSIMLoss takes one of {', '.join(MS_SSIM_KINDS)}, got {kind!r}")
+        self.kind = kind
+        self.weights = recon_weights(kind, alpha)
+        self.scales = int(scales)
+
+    def forward(self, input, target):
+        return F.MsSsimLossFn.apply(input, target, ms_ssim_scales(self.scales, input.shape[-1]), self.weights)
 
 
 class L1Loss(ReconLoss):

@@ -1487,6 +1487,68 @@ def recon_loss_bwd(x, t, w, gout):
     return dx
 
 
+# Multi-scale SSIM criterion (dg_ms_ssim_loss_*): w = (w_mse, w_l1, w_ms) host floats, M scales (0: as many as the size carries)
+def ms_ssim_max_scales(S):
+    """min(5, number of j with S >> j >= 11): the scales an S x S image carries (0 under 11 pixels)."""
+    return int(_lib.load().dg_ms_ssim_max_scales(int(S)))
+
+
+def _ms_args(who, xs, ts, M, w):
+    """The argument checks of the ms_ssim_* wrappers.  Returns (n, S, M, the weights as a C float[3])."""
+    n, S, cw = _recon_args(who, xs, ts, w)
+    top = ms_ssim_max_scales(S)
+    if top < 1:
+        raise _lib.DiscoganHipError(f"{who}: multi-scale SSIM needs S >= 11 pixels (the 11 x 11 window), got S={S}")
+    M = top if int(M) == 0 else int(M)
+    if not 1 <= M <= top:
+        raise _lib.DiscoganHipError(f"{who}: {M} scales at S={S}: every scale needs a side >= 11, so 1..{top} (0: the maximum)")
+    return n, S, M, cw
+
+
+def _ms_save(L, n, S, M, g, device):
+    """The caller-owned buffers the forward fills for the backward (pyramids of x and t, the k table), one per problem."""
+    nbytes = L.dg_ms_ssim_save_bytes(n, S, M)
+    per = (nbytes + 255) // 256 * 64
+    t = torch.empty(g * per, device=device, dtype=torch.float32)
+    return [t[i * per:(i + 1) * per] for i in range(g)], nbytes
+
+
+def ms_ssim_loss_fwd(x, t, M, w, out=None):
+    """loss = w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ms (1 - mean MS-SSIM) of two float32 NCHW batches [n,3,S,S] over M scales.
+    Returns (loss: a device scalar -- ``out``, the slot to write it into --, save: the buffer ``ms_ssim_loss_bwd`` reads)."""
+    n, S, M, cw = _ms_args("ms_ssim_loss_fwd", [x], [t], M, w)
+    loss = out if out is not None else torch.empty((), device=x.device, dtype=torch.float32)
+    L = _lib.load()
+    ws, wsb = _ws(L.dg_ms_ssim_workspace_bytes(n, S, M), x.device)
+    (save,), sb = _ms_save(L, n, S, M, 1, x.device)
+    _lib.check(L.dg_ms_ssim_loss_fwd(_ptr(x), _ptr(t), n, S, M, cw, _ptr(loss), _ptr(save), sb, _ptr(ws), wsb, _stream()), "dg_ms_ssim_loss_fwd")
+    return loss, save
+
+
+def ms_ssim_loss_bwd(x, t, M, w, gout, save):
+    """d loss / d x times the device scalar ``gout`` (overwriting); ``save``: what ``ms_ssim_loss_fwd`` returned for these x, t, M."""
+    n, S, M, cw = _ms_args("ms_ssim_loss_bwd", [x], [t], M, w)
+    _check_dev(gout, save)
+    dx = torch.empty_like(x)
+    L = _lib.load()
+    ws, wsb = _ws(L.dg_ms_ssim_bwd_workspace_bytes(n, S, M), x.device)
+    _lib.check(L.dg_ms_ssim_loss_bwd(_ptr(x), _ptr(t), n, S, M, cw, _ptr(gout), _ptr(save), save.numel() * 4, _ptr(dx), _ptr(ws), wsb, _stream()),
+               "dg_ms_ssim_loss_bwd")
+    return dx
+
+
+def image_ms_ssim(x, y, M=0):
+    """Two float32 NCHW batches [n,3,S,S] (S >= 11) -> float32 [n] on the device: the multi-scale SSIM of the pair (x[i], y[i]) over M
+    scales (0: ``ms_ssim_max_scales(S)``), the mean over the channels.  Row i depends on pair i alone and is bitwise repeatable."""
+    xc, yc = x.detach().contiguous(), y.detach().contiguous()
+    n, S, M, _ = _ms_args("image_ms_ssim", [xc], [yc], M, (0.0, 0.0, 1.0))
+    out = torch.empty((n,), device=x.device, dtype=torch.float32)
+    L = _lib.load()
+    ws, wsb = _ws(L.dg_ms_ssim_workspace_bytes(n, S, M), x.device)
+    _lib.check(L.dg_image_ms_ssim(_ptr(xc), _ptr(yc), n, S, M, _ptr(out), _ptr(ws), wsb, _stream()), "dg_image_ms_ssim")
+    return out
+
+
 def bce_fwd(p, label, out=None):
     _check_dev(p)
     p = p.contiguous()
@@ -1927,6 +1989,28 @@ def recon_loss_bwd_g(xs, ts, w, gouts):
     _check_dev(*gouts)
     dxs = [torch.empty_like(x) for x in xs]
     _lib.check(_lib.load().dg_recon_loss_bwd_g(len(xs), _tab(xs), _tab(ts), n, S, cw, _tab(gouts), _tab(dxs), _stream()), "dg_recon_loss_bwd_g")
+    return dxs
+
+
+def ms_ssim_loss_fwd_g(xs, ts, M, w, outs):
+    """ms_ssim_loss_fwd of ``len(xs)`` problems of one (n, S, M, w) in one launch per kernel; returns the save buffers, one per problem."""
+    n, S, M, cw = _ms_args("ms_ssim_loss_fwd_g", xs, ts, M, w)
+    L = _lib.load()
+    wsl, wsb = _ws_g(L.dg_ms_ssim_workspace_bytes(n, S, M), len(xs), xs[0].device)
+    saves, sb = _ms_save(L, n, S, M, len(xs), xs[0].device)
+    _lib.check(L.dg_ms_ssim_loss_fwd_g(len(xs), _tab(xs), _tab(ts), n, S, M, cw, _tab(outs), _tab(saves), sb, _tab(wsl), wsb, _stream()),
+               "dg_ms_ssim_loss_fwd_g")
+    return saves
+
+
+def ms_ssim_loss_bwd_g(xs, ts, M, w, gouts, saves):
+    n, S, M, cw = _ms_args("ms_ssim_loss_bwd_g", xs, ts, M, w)
+    _check_dev(*gouts, *saves)
+    dxs = [torch.empty_like(x) for x in xs]
+    L = _lib.load()
+    wsl, wsb = _ws_g(L.dg_ms_ssim_bwd_workspace_bytes(n, S, M), len(xs), xs[0].device)
+    _lib.check(L.dg_ms_ssim_loss_bwd_g(len(xs), _tab(xs), _tab(ts), n, S, M, cw, _tab(gouts), _tab(saves), min(s.numel() for s in saves) * 4,
+                                       _tab(dxs), _tab(wsl), wsb, _stream()), "dg_ms_ssim_loss_bwd_g")
     return dxs
 
 

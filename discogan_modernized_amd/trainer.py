@@ -47,7 +47,7 @@ LOG_KEYS = ("gen_loss_A", "gen_loss_B", "fm_loss_A", "fm_loss_B", "recon_loss_A"
 DEFAULTS = dict(learning_rate=2e-4, beta1=0.5, beta2=0.999, weight_decay=0.00001, gan_curriculum=10000,
                 starting_rate=0.01, default_rate=0.5, update_interval=3, model_arch="discogan",
                 ema_decay=0.0, ema_start_iter=0, grad_clip=0.0, nonfinite_guard=False, log_grad_norm=False, image_pool=0,
-                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84, gan_loss="bce", gan_real_label=1.0,
+                diffaug="", recon_loss="mse", recon_ssim_alpha=0.84, recon_ms_scales=0, gan_loss="bce", gan_real_label=1.0,
                 diffaug_p=None, ada_target=0.0, ada_interval=4, ada_kimg=500.0, ada_p_max=1.0)
 
 # The loss vector every term of an iteration is written into and dg_loss_mix_fwd / _bwd read (the layout is defined by the comment
@@ -152,14 +152,23 @@ def ada_threshold(gan_loss, gan_real_label=1.0):
     return {"bce": 0.5, "lsgan": float(gan_real_label) / 2.0}.get(gan_loss, 0.0)
 
 
-def check_recon_loss(kind, alpha, image_size):
+def check_recon_loss(kind, alpha, image_size, ms_scales=0):
     """``recon_loss``: the criterion of the two reconstruction (cycle) terms -- "mse" (the reference's nn.MSELoss), "l1", "ssim" (1 - SSIM)
-    or "l1_ssim" ((1 - alpha) L1 + alpha (1 - SSIM), ``recon_ssim_alpha`` in (0, 1), read by that kind only).  The SSIM kinds need images
-    of at least 11 pixels (the 11 x 11 window).  Returns the weights (w_mse, w_l1, w_ssim) (losses.recon_weights)."""
+    or "l1_ssim" ((1 - alpha) L1 + alpha (1 - SSIM), ``recon_ssim_alpha`` in (0, 1), read by that kind only), and their multi-scale forms
+    "ms_ssim" and "l1_ms_ssim" (MS-SSIM over ``ms_scales`` scales, 0 = as many as the size carries; read by those kinds only).  The SSIM
+    kinds need images of at least 11 pixels (the 11 x 11 window), at every scale.  Returns the weights (w_mse, w_l1, w_ssim)
+    (losses.recon_weights); ``recon_ms_scales`` gives the scale count."""
     w = L.recon_weights(kind, alpha)
     if w[2] > 0.0 and image_size < 11:
         raise ValueError(f"recon_loss {kind!r} needs image_size >= 11 (the 11 x 11 SSIM window), got {image_size}")
+    recon_ms_scales(kind, image_size, ms_scales)
     return w
+
+
+def recon_ms_scales(kind, image_size, ms_scales=0):
+    """The scale count M of the criterion ``kind`` at ``image_size`` (0 for the kinds that have no pyramid); ValueError for a count the
+    size cannot carry."""
+    return L.ms_ssim_scales(ms_scales, image_size) if kind in L.MS_SSIM_KINDS else 0
 
 
 # ``gan_loss`` / ``gan_real_label``: the objective of the six GAN terms -- "bce" (the reference's nn.BCELoss on the sigmoid output) or, on the
@@ -208,7 +217,8 @@ class DiscoGANTrainer:
         ema_decay = check_ema_decay(self.args.ema_decay)
         grad_clip = check_grad_clip(self.args.grad_clip)
         self.recon_loss = self.args.recon_loss
-        self.recon_w = check_recon_loss(self.recon_loss, self.args.recon_ssim_alpha, image_size)
+        self.recon_w = check_recon_loss(self.recon_loss, self.args.recon_ssim_alpha, image_size, self.args.recon_ms_scales)
+        self.recon_ms = recon_ms_scales(self.recon_loss, image_size, self.args.recon_ms_scales)      # M; 0: a single-scale kind
         self.gan_loss, self.gan_real_label = check_gan_loss(self.args.gan_loss, self.args.gan_real_label)
         guard, log_norm = bool(self.args.nonfinite_guard), bool(self.args.log_grad_norm)
         loss_slots(self.args.model_arch, True, 0)        # an unknown model_arch is refused here, before anything is allocated
@@ -240,8 +250,12 @@ class DiscoGANTrainer:
                          dis_A=self.discriminator_A, dis_B=self.discriminator_B)
         # The criterion of the two reconstruction terms (slots 0 and 1 of the loss vector).  "mse": the reference's, through MSELossFn /
         # MSELossGroupFn as ever.  Any other kind: one fused kernel pair per term (functional.ReconLossFn / ReconLossGroupFn,
-        # csrc/recon.hip) in the same places on the same streams, capturable, stateless -- nothing to checkpoint or to exchange.
-        self.recon_criterion = L.MSELoss() if self.recon_loss == "mse" else L.ReconLoss(self.recon_loss, self.args.recon_ssim_alpha)
+        # csrc/recon.hip) in the same places on the same streams, capturable, stateless -- nothing to checkpoint or to exchange.  The
+        # multi-scale kinds likewise, through MsSsimLossFn / MsSsimLossGroupFn (csrc/msssim.hip) over ``recon_ms`` scales.
+        if self.recon_ms:
+            self.recon_criterion = L.MSSSIMLoss(self.recon_loss, self.args.recon_ssim_alpha, self.recon_ms)
+        else:
+            self.recon_criterion = L.MSELoss() if self.recon_loss == "mse" else L.ReconLoss(self.recon_loss, self.args.recon_ssim_alpha)
         # The objective of the six GAN terms (slots A_REAL1 .. B_FAKE1).  "bce": the reference's -- the discriminators end in their sigmoid
         # and BCELossFn / BCELossGroupFn read it, as ever (gan_real_label only replaces the label 1 of the two *_REAL1 terms).  Any other
         # kind: the discriminators return their head conv's LOGITS (no sigmoid launch) and GanLossFn / GanLossGroupFn (csrc/ganloss.hip)
@@ -625,6 +639,10 @@ class DiscoGANTrainer:
         """The reconstruction terms of ``xs`` against ``ts`` into their slots of the loss vector -- the reference's MSE, or the criterion
         of ``recon_loss``: one pass on its own stream (two-chain schedule), or both as one grouped launch."""
         mse = self.recon_loss == "mse"
+        if self.recon_ms:                                 # the multi-scale kinds: csrc/msssim.hip, the same places and streams
+            if len(xs) == 1:
+                return (F_.MsSsimLossFn.apply(xs[0], ts[0], self.recon_ms, self.recon_w, slots[0]),)
+            return F_.MsSsimLossGroupFn.apply(len(xs), self.recon_ms, self.recon_w, *xs, *ts, *slots)
         if len(xs) == 1:
             return (F_.MSELossFn.apply(xs[0], ts[0], slots[0]) if mse else F_.ReconLossFn.apply(xs[0], ts[0], self.recon_w, slots[0]),)
         if mse:

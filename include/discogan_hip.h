@@ -645,6 +645,53 @@ int dg_recon_loss_fwd_g(int groups, const float* const* x, const float* const* t
                         float* const* loss, void* const* ws, size_t ws_bytes, dg_stream_t s);
 int dg_recon_loss_bwd_g(int groups, const float* const* x, const float* const* t, int n, int S, const float* w /* host [3] */,
                         const float* const* gout, float* const* dx, dg_stream_t s);
+/* ---- multi-scale SSIM (trainer.py --recon_loss ms_ssim / l1_ms_ssim, evaluate.py --ms_ssim; csrc/msssim.hip; Wang, Simoncelli, Bovik
+   2003).  x, t: float [n][3][S][S] (NCHW, any 4-byte alignment); M scales; level 0 is the image.
+   Pyramid.  Level j + 1 has side S_{j+1} = floor(S_j / 2); its pixel (y, x) is 0.25f * ((a + b) + (c + d)) of the 2 x 2 block
+   a = (2y, 2x), b = (2y, 2x + 1), c = (2y + 1, 2x), d = (2y + 1, 2x + 1) of level j, in fp32 in that order; a last odd row or column is
+   dropped.
+   Scales.  Every scale needs S_j >= 11: dg_ms_ssim_max_scales(S) = min(5, number of j with S >> j >= 11) (0 for S < 11; 11 -> 1,
+   22 -> 2, 64 -> 3, 176 and more -> 5), and 1 <= M <= that maximum.
+   Per scale j, image i and channel c, with the window, the constants, the "valid" corners and the factors A1, A2, B1, B2 of the
+   reconstruction loss above:
+     V_j = mean over the (S_j - 10)^2 windows of A2 / B2             for j < M - 1   (contrast-structure)
+     V_{M-1} = mean over the (S_{M-1} - 10)^2 windows of (A1 A2) / (B1 B2)            (the full SSIM at the coarsest scale)
+   Exponents: beta_j = the first M of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) divided by their sum, the division in double, rounded once
+   to fp32.
+     ms(i, c) = prod_j V_j^beta_j  if every V_j > 0;  otherwise ms(i, c) = 0 and its gradient is exactly 0 (the clamp of the usual
+     implementations with the subgradient fixed); a NaN V_j gives NaN.
+   dg_image_ms_ssim: out[i] = mean over c of ms(i, c); row i does not depend on n or on the other pairs.
+     loss = w_mse mean (x - t)^2 + w_l1 mean |x - t| + w_ms (1 - mean over i, c of ms(i, c))
+   w: three HOST floats (w_mse, w_l1, w_ms), finite, >= 0, not all 0; a term of weight 0 is not evaluated.  loss: one device float per
+   problem, written once (fp32 inside a thread, fp64 from the wave sum on, fixed order, no atomics: bitwise repeatable).
+   bwd: the gradient with respect to x only, gout a device scalar.  With k_j(i, c) = beta_j ms / V_j (0 for a channel with ms = 0) the
+   gradient at scale j is
+     g_j(q) = -w_ms k_j / (3 n (S_j - 10)^2) [ (w * a)(q) + x_j(q) (w * b)(q) + t_j(q) (w * c)(q) ]
+   in the gather form of the reconstruction loss above (a = dmu - 2 mx dsig - my dc, b = 2 dsig, c = dc), where the last scale uses that
+   loss's dmu, dsig, dc and a scale j < M - 1 those of A2 / B2 alone:  dmu = 0,  dsig = -A2 / B2^2,  dc = 2 / B2;
+     dx(q) = gout ( w_mse 2 (x - t) / N + w_l1 sign(x - t) / N + sum_j g_j(q >> j) / 4^j ),  N = 3 n S^2,
+   the term of scale j for q inside the 2^j S_j square only.  One pass overwrites dx; the combination is formed in double and rounded
+   once; gather only: no atomics, two calls give the same bits, a NaN / inf in image i stays in image i's rows of dx.
+   save: the forward fills this caller-owned buffer of dg_ms_ssim_save_bytes(n, S, M) bytes (16-byte aligned) with the pyramid levels of x
+   and t and the table k [n][3][M]; the backward reads it (and x, t).  ws: per problem, 16-byte aligned, dg_ms_ssim_workspace_bytes(n, S,
+   M) bytes for the forward and the metric, dg_ms_ssim_bwd_workspace_bytes(n, S, M) (one float per pixel of levels 1 .. M-1) for the
+   backward.  w_ms == 0: no pyramid is built, no stencil runs in either direction, save is neither written nor read.  No host synchronisation, no allocation: capturable.  The *_g forms run `groups` (1..DG_MAX_GROUPS)
+   problems of one (n, S, M, w) in one launch per kernel, bitwise the single calls.  Refused with a message and nothing launched: null or
+   misaligned pointers, n < 1, S < 11, M out of range, a short workspace or save buffer, bad weights. */
+int dg_ms_ssim_max_scales(int S);
+size_t dg_ms_ssim_workspace_bytes(int n, int S, int M);
+size_t dg_ms_ssim_bwd_workspace_bytes(int n, int S, int M);
+size_t dg_ms_ssim_save_bytes(int n, int S, int M);
+int dg_ms_ssim_loss_fwd(const float* x, const float* t, int n, int S, int M, const float* w /* host [3] */, float* loss, void* save,
+                        size_t save_bytes, void* ws, size_t ws_bytes, dg_stream_t s);
+int dg_ms_ssim_loss_bwd(const float* x, const float* t, int n, int S, int M, const float* w /* host [3] */, const float* gout, const void* save,
+                        size_t save_bytes, float* dx, void* ws, size_t ws_bytes, dg_stream_t s);
+int dg_ms_ssim_loss_fwd_g(int groups, const float* const* x, const float* const* t, int n, int S, int M, const float* w /* host [3] */,
+                          float* const* loss, void* const* save, size_t save_bytes, void* const* ws, size_t ws_bytes, dg_stream_t s);
+int dg_ms_ssim_loss_bwd_g(int groups, const float* const* x, const float* const* t, int n, int S, int M, const float* w /* host [3] */,
+                          const float* const* gout, const void* const* save, size_t save_bytes, float* const* dx, void* const* ws,
+                          size_t ws_bytes, dg_stream_t s);
+int dg_image_ms_ssim(const float* x, const float* y, int n, int S, int M, float* out /* [n] */, void* ws, size_t ws_bytes, dg_stream_t s);
 /* ---- sliced Wasserstein distance on Laplacian-pyramid patches (evaluate.py; Karras et al., ICLR 2018, "Progressive Growing of GANs",
  * section 5): a score for UNPAIRED sets, no network.  x, y: float [n][3][S][S] (NCHW), values as they are (no clamp), S >= 16.
  *
